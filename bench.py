@@ -1,9 +1,9 @@
 # -*- coding: utf-8 -*-
 """bench.py — throughput of the north-star hot path on MI355X.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-        bench.py --gpus N --steps K --warmup W
+        bench.py --gpus N --steps K --warmup W [--full]
 
 A "step" is one pass of the training hot path over one batch of synthetic interactions already resident in HBM:
 epoch-shuffle slice + dynamic negative sampling -> fused embedding gather + FM pairwise scoring + hinge + backward ->
@@ -18,13 +18,17 @@ per-slice presort (sparse regime, c4: trs_epoch_flags = ids + duplicate flags; d
 ids + item references grouped by row, + user flags; prefetched on a side stream; slices are sized to the run so a
 short run carries its proportional share).  NO kernel events are recorded in it.  `host_enqueue_ms` = the host time
 that went into enqueueing the K steps (the launches run ahead of the GPU; the rest of the window is the GPU finishing).
-After it, untimed: (1) an instrumented window of the same steps with HIP events around K1 / K2 on the launch stream
+A plain run stops there: set-up, warm-up, the K timed steps, the outputs (--dump-outputs DIR: the last timed step's loss
+sum and a fixed, seeded sample of rows of every parameter, as DIR/<name>.npy), the result line.  With --full, after it,
+untimed: (1) an instrumented window of the same steps with HIP events around K1 / K2 on the launch stream
 (>= 8 samples whatever --steps is) -> `roofline` of the dominant kernel; (2) the north-star pass alone
 (trs_score_forward = fused pos+neg gather + FM pairwise score) at the per-GPU batch and at the global batch 262 144
--> `roofline_pass`; (3) rank 0, N=1: the CPU port of the reference's loop on a bounded sample -> `cpu_baseline`.
+-> `roofline_pass`; (3) rank 0, N=1: the CPU port of the reference's loop on a bounded sample -> `cpu_baseline`;
+(4) rank 0, N=1, default c4 / SGD: short windows of the two MLP configurations -> `roofline_mlp`; (5) N > 1: the replica
+synchronisation fit() adds around the steps -> `replica_sync`.  --no-* switch single legs of --full off.
 
 Multi-GPU: one process per GPU; tables replicated; FM/Linear have no dense parameters, so a step has no
-data-path collective.  Rank 0 prints ONE JSON line.
+data-path collective.  Rank 0 prints ONE JSON line (and writes the outputs of its replica).
 """
 import argparse
 import json
@@ -198,6 +202,7 @@ def build_model(config, n_inter, dev, rank=0, world=1):
     rank's shard resident in HBM."""
     import contextlib
     import io
+    import numpy as np
     from torchrecsys_amd.model import TorchRecSys
     cfg = CONFIGS[config]
     net, n_users, n_items, D = cfg["net"], cfg["n_users"], cfg["n_items"], cfg["D"]
@@ -214,6 +219,9 @@ def build_model(config, n_inter, dev, rank=0, world=1):
         meta = torch.stack(cols, dim=1).contiguous()
     with contextlib.redirect_stdout(io.StringIO()):
         torch.manual_seed(7)
+        # static negatives (c1) are drawn from numpy's global legacy stream, as in the reference: seeded too, so that the
+        # same arguments give the same inputs at every run
+        np.random.seed(7)
         kw = dict(hidden_layers=cfg["hidden"]) if net == "mlp" else {}
         model = TorchRecSys.from_tensors(users, items, n_users=n_users, n_items=n_items, item_metadata=meta,
                                          n_factors=D, net_type=net, split_ratio=0.8, dynamic_neg_sampling=config != "c1",
@@ -281,6 +289,39 @@ def mlp_leg(config, dev, steps=24, warmup=6, n_extra=6_000_000):
             "gemm_ms_per_step": r["gemm_ms_per_step"], "gemm_launches_per_step": r["gemm_launches_per_step"]}
 
 
+DUMP_BUDGET = 48 << 20  # bytes written by --dump-outputs at most (the contract allows 64 MB)
+
+
+def dump_outputs(path, model, runner):
+    """--dump-outputs: what the timed path (FitRunner.run_steps) handed its caller in the last timed step, as
+    DIR/<name>.npy — the step's loss sum (`last_step_loss_sum`) and every entry of model.state_dict() as that step left it
+    (float32; integer buffers as float64).  A tensor with more rows than fit the budget is represented by a fixed, seeded
+    sample of its rows (the same rows for every table of that length and at every run of the same arguments): the largest
+    power-of-two row count <= 65 536 that keeps the whole dump within DUMP_BUDGET.  Returns the bytes written."""
+    import numpy as np
+    b = runner.next_batch - 1  # (run() never leaves a fresh epoch without a step: the last step's slot is this one)
+    arrays = {"last_step_loss_sum": runner.loss_sums[b:b + 1]}
+    arrays.update((k, v.detach()) for k, v in model.state_dict().items())
+
+    def nbytes(t, rows):
+        n = t.numel() if t.dim() == 0 or t.shape[0] <= rows else rows * (t.numel() // t.shape[0])
+        return n * (4 if t.is_floating_point() else 8)
+    rows = 65_536
+    while rows > 1 and sum(nbytes(t, rows) for t in arrays.values()) > DUMP_BUDGET:
+        rows //= 2
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        if t.dim() > 0 and t.shape[0] > rows:
+            idx = np.sort(np.random.default_rng(0x5eed + t.shape[0]).choice(t.shape[0], rows, replace=False))
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        a = (t.float() if t.is_floating_point() else t.double()).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= DUMP_BUDGET, total
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -291,11 +332,19 @@ def main():
     ap.add_argument("--optimizer", default="sgd", choices=["sgd", "sparse_adam", "adagrad", "adam"],
                     help="sgd = BASELINE.json's primary optimiser; sparse_adam (lazy Adam) / adagrad = secondary; adam = "
                          "torch.optim.Adam as in the reference's README (lazy rows on the tables, dense Adam on the MLP)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-events", action="store_true", help="skip the instrumented window (no roofline)")
-    ap.add_argument("--no-pass", action="store_true", help="skip the north-star pass measurement (no roofline_pass)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the untimed measurements beside the headline: roofline, "
+                         "roofline_pass, replica_sync (N > 1), cpu_baseline, roofline_mlp (file header)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss sum, sampled parameter rows) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-events", action="store_true",
+                    help="with --full: skip the instrumented window (no roofline)")
+    ap.add_argument("--no-pass", action="store_true",
+                    help="with --full: skip the north-star pass measurement (no roofline_pass)")
     ap.add_argument("--no-mlp", action="store_true",
-                    help="skip the MLP legs (roofline_mlp: short c5-shard and c3 windows after the default c4 line)")
+                    help="with --full: skip the MLP legs (roofline_mlp: short c5-shard and c3 windows after the default "
+                         "c4 line)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -413,11 +462,13 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, runner)
 
     # ---- instrumented window (untimed): the same steps with HIP events around the kernels, on the launch stream ----
     events, gemm_events = {}, None
     inst_slice = None
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         n_inst = 64 if is_mlp else 256
         if not is_mlp and "TRS_SLICE_BATCHES" not in os.environ:
             # The kernel-level measurements describe the step kernel as a fit() runs it: with the production presort
@@ -458,7 +509,7 @@ def main():
             gev.append((e0, e1))
         torch.cuda.synchronize()
         grouped_us = [1e3 * e0.elapsed_time(e1) / per_group for e0, e1 in gev]
-    frac = slice_fractions(runner) if not is_mlp else None
+    frac = slice_fractions(runner) if events and not is_mlp else None  # (what the roofline's byte counts depend on)
     runner.end_epoch()  # also raises if any id was out of range
 
     triples = args.steps * B * world
@@ -480,7 +531,7 @@ def main():
                                    f"dp{world}: interaction stream sharded by user_id % {world}, tables replicated, no "
                                    f"per-step collective (FM/Linear have no dense parameters); item tables averaged per "
                                    f"epoch, user rows gathered from their owners after fit() — both OUTSIDE the timed "
-                                   f"steps, measured in `replica_sync`"),
+                                   f"steps, measured in `replica_sync` (--full)"),
                    "rng": "device (Feistel epoch shuffle + Philox4x32-10 negative sampler)"},
     }
     out["host_enqueue_ms"] = 1e3 * enqueued  # of the timed region's `1e3 * elapsed` ms: the launches run ahead of the GPU
@@ -554,11 +605,11 @@ def main():
                                    "that follows the timed region (the timed region itself records no events); the "
                                    "instrumented window runs with the production presort slices (512 batches)"}
     # ---- the north-star pass alone: fused pos+neg gather + pairwise score (trs_score_forward), read-only ----
-    if not is_mlp and not args.no_pass and M == 0:
+    if args.full and not is_mlp and not args.no_pass and M == 0:
         out["roofline_pass"] = time_pass(model, runner, B, D, R, dev)
     # ---- data parallel: what fit() adds around the steps (not in the timed region): the per-epoch average of the tables
     # with several writers and the end-of-fit all-gather of the owners' user rows
-    if world > 1 and not is_mlp:
+    if args.full and world > 1 and not is_mlp:
         def timed(fn):
             barrier()
             t1 = time.perf_counter()
@@ -577,7 +628,7 @@ def main():
             "user_table_bytes": sum(4 * t_.numel() for t_ in model._user_tables())}
     # ---- CPU baseline: the op-sequence port of the reference's fit() loop on this box's host cores ----
     # (torch.optim.Adam rejects the sparse gradients of the CPU port's nn.Embedding(sparse=True): no CPU leg for it)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.optimizer != "adam":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.optimizer != "adam":
         from oracle import cpu_fit
         cores = min(16, len(os.sched_getaffinity(0)))  # the one-GPU box share (oversubscribing collapses torch CPU ops)
         n_rows = min(n_inter, 4_000_000)
@@ -589,7 +640,7 @@ def main():
                                "sample": f"{res['steps']} steps of batch {B} ({res['seconds']:.1f} s) on full-size "
                                          f"tables, {n_rows} synthetic interactions, oracle/cpu_fit.py"}
     # ---- MFMA evidence in the same line (N = 1, default workload only): short windows of the two MLP configurations ----
-    if rank == 0 and world == 1 and args.config == "c4" and args.optimizer == "sgd" and not args.no_mlp:
+    if args.full and rank == 0 and world == 1 and args.config == "c4" and args.optimizer == "sgd" and not args.no_mlp:
         del runner, opt, model
         import gc
         gc.collect()

@@ -175,7 +175,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
     env = dict(os.environ, TRS_BENCH_SHARE_DEVICE="1", TRS_DIST_BACKEND="gloo", TRS_FLAG_ONE_LAUNCH="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "24",
-           "--warmup", "8"]
+           "--warmup", "8", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")]

@@ -681,15 +681,16 @@ def test_fit_with_sampler_options(net_type):
 
 
 def test_bench_line_contract():
-    """`python bench.py` prints ONE JSON line with the contract's keys, a roofline object (bound / achieved / peak / unit /
-    frac / traffic) and a cpu_baseline object (value / unit / cores / kind / sample).  Run on the small c1 workload."""
+    """`python bench.py --full` prints ONE JSON line with the contract's keys, a roofline object (bound / achieved / peak /
+    unit / frac / traffic) and a cpu_baseline object (value / unit / cores / kind / sample).  Run on the small c1
+    workload."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "c1", "--steps", "64", "--warmup", "8"],
-                         capture_output=True, text=True, timeout=600, cwd=root)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "c1", "--steps", "64", "--warmup", "8",
+                          "--full"], capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1 and lines[0].startswith("{"), out.stdout[-2000:]  # nothing else on stdout
@@ -706,6 +707,43 @@ def test_bench_line_contract():
     assert r["frac"] == pytest.approx(r["achieved"] / r["peak"]) and 0.0 < r["frac"] < 1.0
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["unit"] == d["unit"] and c["cores"] >= 1 and c["value"] > 0 and c["sample"]
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain `python bench.py` (no --full) prints the headline line without the untimed legs, times exactly --steps
+    steps, and --dump-outputs DIR writes the last timed step's loss sum and the parameters as float32 / float64 .npy
+    files (at most 64 MB) — the same outputs at a second run of the same arguments.  Small c1 workload."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for run in range(2):
+        d_out = tmp_path / f"run{run}"
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "c1", "--steps", "24",
+                              "--warmup", "4", "--dump-outputs", str(d_out)],
+                             capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1 and lines[0].startswith("{"), out.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 24 and d["warmup"] == 4 and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["value"] == pytest.approx(2 * 1024 * 24 / (d["ms_per_step"] * 24 * 1e-3), rel=1e-6)
+        for k in ("roofline", "roofline_pass", "roofline_mlp", "cpu_baseline", "replica_sync"):
+            assert k not in d, k
+        files = sorted(os.listdir(d_out))
+        assert "last_step_loss_sum.npy" in files and "net.user.weight.npy" in files, files
+        arrs = {f: np.load(d_out / f) for f in files}
+        assert all(f.endswith(".npy") and a.dtype in (np.float32, np.float64) for f, a in arrs.items())
+        assert sum(a.nbytes for a in arrs.values()) <= 64e6
+        assert arrs["net.user.weight.npy"].shape == (3000, 32)  # (smaller than the sample: whole)
+        assert np.isfinite(arrs["last_step_loss_sum.npy"]).all() and arrs["last_step_loss_sum.npy"][0] > 0
+        dumps.append(arrs)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        # (float atomics on rows shared inside a batch may reorder sums from run to run: last-bit differences only)
+        assert np.allclose(dumps[0][f], dumps[1][f], rtol=1e-5, atol=1e-6), f
 
 
 @pytest.mark.parametrize("net_type", ["linear", "fm", "mlp"])

@@ -9,19 +9,19 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 B="python3 $ROOT/bench.py"
 echo "== bench lines"
-$B --gpus 1 --steps 20 --warmup 5 > $O/${R}_bench_c4_driver_cmd.json 2> $O/err.log || exit 1
-$B --gpus 1 --no-mlp > $O/${R}_bench_c4.json 2>> $O/err.log
-$B --config c2 --no-mlp > $O/${R}_bench_c2.json 2>> $O/err.log
-$B --config c5 --steps 64 --warmup 8 > $O/${R}_bench_c5.json 2>> $O/err.log
-$B --config c3 --steps 32 --warmup 4 > $O/${R}_bench_c3.json 2>> $O/err.log
-$B --config c1 --steps 256 --warmup 16 > $O/${R}_bench_c1.json 2>> $O/err.log
+$B --gpus 1 --steps 20 --warmup 5 --full > $O/${R}_bench_c4_driver_cmd.json 2> $O/err.log || exit 1
+$B --gpus 1 --full --no-mlp > $O/${R}_bench_c4.json 2>> $O/err.log
+$B --config c2 --full --no-mlp > $O/${R}_bench_c2.json 2>> $O/err.log
+$B --config c5 --steps 64 --warmup 8 --full > $O/${R}_bench_c5.json 2>> $O/err.log
+$B --config c3 --steps 32 --warmup 4 --full > $O/${R}_bench_c3.json 2>> $O/err.log
+$B --config c1 --steps 256 --warmup 16 --full > $O/${R}_bench_c1.json 2>> $O/err.log
 echo "== kernel stats"
 for cfg in c4 c2 c5 c3; do
   steps=1024; warm=32
   [ $cfg = c5 ] && { steps=64; warm=8; }
   [ $cfg = c3 ] && { steps=32; warm=4; }
   rm -rf $O/trace_$cfg
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$cfg -- python3 $ROOT/bench.py --config $cfg --steps $steps --warmup $warm --no-cpu-baseline --no-mlp > $O/${R}_bench_${cfg}_under_rocprof.json 2>> $O/err.log
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$cfg -- python3 $ROOT/bench.py --config $cfg --steps $steps --warmup $warm --full --no-cpu-baseline --no-mlp > $O/${R}_bench_${cfg}_under_rocprof.json 2>> $O/err.log
   f=$(find $O/trace_$cfg -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && python3 - "$f" $O/${R}_bench_${cfg}_kernel_stats.csv <<'PY'
 import csv, sys
