@@ -91,8 +91,10 @@ const char* trs_last_error(void);
  *   4: trs_sampler.seen_users (bounds of the seen CSR); trs_train_args.sync_dev (flag mode as one launch per step);
  *      trs_mlp_gather_gemm1_fwd, trs_tuning_set added; trs_epoch_flags takes batches up to 262 144; the presort entry
  *      points no longer use their temp buffers (no vendor sort).
- *   5: trs_epoch_flags_ordered (flagged-first batches), trs_train_args.n_flagged_dev. */
-#define TRS_ABI_VERSION 5
+ *   5: trs_epoch_flags_ordered (flagged-first batches), trs_train_args.n_flagged_dev.
+ *   6: batched top-k retrieval: trs_csr, trs_item_fold(_bytes), trs_retrieve_topk, trs_retrieve_workspace_bytes,
+ *      trs_mask_seen, trs_rank_metrics. */
+#define TRS_ABI_VERSION 6
 #define TRS_SYNC_WORDS 288
 int trs_abi_version(void);
 /* Tuning / A-B knobs of the launch paths (kernel selection, launch shapes): GRID_CAP, PASS_GRID_CAP, K1_ITERS,
@@ -443,6 +445,53 @@ int64_t trs_topk_workspace_bytes(int64_t n, int32_t k);
 int trs_topk(const float* scores_dev, int64_t n, int32_t k, int64_t* idx_out_dev, void* workspace_dev,
              int64_t workspace_bytes, void* stream);
 
+
+/* ------------------------------------------------------------------------------------- retrieval (recommend) */
+/* Batched top-k of Linear / FM scores over the whole catalogue (model.py recommend / evaluate_ranking, DESIGN.md
+ * "Retrieval").  For one user both scorers are an inner product plus constants:
+ *   Linear  score(u,i) = (<U_u, S_i> + user_bias_u) + c_i,  c_i = item_bias_i
+ *   FM      z(u,i)     = (<U_u, S_i> + linear_user_u) + c_i,
+ *           c_i = linear_item_i + sum_m linear_meta_m + 1/2 (|S_i|^2 - |item_i|^2 - sum_m |meta_m|^2),  score = sigmoid(z)
+ * with S_i = item_i + sum_m meta_m (the item's row plus the rows of its metadata).  Items are ranked by the raw Linear
+ * score and by z for FM (strict where fp32 sigmoid saturates), ties by ascending item id. */
+#define TRS_RETRIEVE_KMAX 128 /* largest k of the fused kernel (its per-user LDS candidate buffer holds KMAX + 128) */
+#define TRS_RETRIEVE_DMAX 256 /* largest D of the fused kernel */
+
+/* Rows of a sorted CSR indexed by dense user id: items of row u are items[off[u] .. off[u+1]), ascending. */
+typedef struct trs_csr {
+  const int64_t* off;   /* (n_rows + 1) */
+  const int32_t* items; /* (off[n_rows]) */
+  int64_t n_rows;
+} trs_csr;
+
+/* Bytes of the folded item buffer of a catalogue of n_items items with D factors (0 when D > TRS_RETRIEVE_DMAX): the
+ * item matrix S (n_items rounded up to 128 rows, D zero-padded to 16/32/64/128/256 columns) then c (same rows). */
+int64_t trs_item_fold_bytes(int64_t n_items, int32_t D);
+/* S and c of every item (formulas above) into fold_dev; item_meta (n_items, M) int32 gives each item's metadata ids
+ * (NULL when M == 0).  Padding rows are zero. */
+int trs_item_fold(int net, const trs_tables* tables, const int32_t* item_meta_dev, void* fold_dev, int64_t fold_bytes,
+                  void* stream);
+/* Workspace of trs_retrieve_topk for n_q query users and k (per-split partial top-k lists); monotone in n_q and k. */
+int64_t trs_retrieve_workspace_bytes(int64_t n_q, int32_t k);
+/* Top-k items of each query user users[q] (dense ids, int64), 1 <= k <= min(TRS_RETRIEVE_KMAX, n_items), from the
+ * folded buffer trs_item_fold wrote for the same tables.  seen (optional): the users' items to exclude.  Outputs
+ * ids (n_q, k) int64 and scores (n_q, k) fp32 in the scorer's output units (FM: sigmoid(z)); positions beyond the
+ * user's count of candidate items hold id -1 and score -inf.  rel (optional): the users' relevant items; metrics_out
+ * (n_q, 4) float64 = (hits, dcg, idcg, n_rel) of the returned list (trs_rank_metrics).  One fp32 MFMA kernel streams
+ * item tiles past a tile of 32 users with the top-k selection fused; a merge kernel joins the item splits. */
+int trs_retrieve_topk(int net, const trs_tables* tables, const void* fold_dev, int64_t fold_bytes,
+                      const int64_t* users_dev, int64_t n_q, int32_t k, const trs_csr* seen, const trs_csr* rel,
+                      int64_t* ids_out_dev, float* scores_out_dev, double* metrics_out_dev, void* workspace_dev,
+                      int64_t workspace_bytes, void* stream);
+/* Score rows (n_rows, n_items) fp32: row r's entries at the seen items of user users[r] become -inf (the lowest value
+ * trs_topk ranks; callers pad the positions beyond n_items - |seen_u| with -1).  Generic retrieval path (MLP, k > KMAX). */
+int trs_mask_seen(float* scores_dev, int64_t n_rows, int64_t n_items, const int64_t* users_dev, const trs_csr* seen,
+                  void* stream);
+/* Ranking metrics of given top-k lists ids (n_q, k) int64 (-1 = no item) against the relevant items rel of users[q]:
+ * metrics_out (n_q, 4) float64 = (hits = |R_u & T_u|, dcg = sum_{r<k, R_u[r] in T_u} 1/log2(r+2),
+ * idcg = sum_{r<min(k,|T_u|)} 1/log2(r+2), n_rel = |T_u|), sums in ascending r. */
+int trs_rank_metrics(const int64_t* ids_dev, int64_t n_q, int32_t k, const int64_t* users_dev, const trs_csr* rel,
+                     double* metrics_out_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------- MLP (a4, a7) */
 /* Activations of the MLP are kept for both scoring passes stacked: rows [0,B) = positive pass, rows [B,2B) =

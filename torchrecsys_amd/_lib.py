@@ -11,7 +11,9 @@ TRS_MAX_META = 8
 TRS_NET_LINEAR = 0
 TRS_NET_FM = 1
 LOSS_ID = {"hinge": 0, "bpr": 1}  # TRS_LOSS_HINGE / TRS_LOSS_BPR
-ABI_VERSION = 5  # == TRS_ABI_VERSION of include/trs.h (tests/test_abi.py)
+RETRIEVE_KMAX = 128  # TRS_RETRIEVE_KMAX: largest k of the fused retrieval kernel
+RETRIEVE_DMAX = 256  # TRS_RETRIEVE_DMAX: largest D of the fused retrieval kernel
+ABI_VERSION = 6  # == TRS_ABI_VERSION of include/trs.h (tests/test_abi.py)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libtrs_hip.so")
@@ -103,6 +105,11 @@ class TrsTrainArgs(C.Structure):
                 ("sync_count_host", C.POINTER(C.c_uint32)), ("n_flagged_dev", C.c_void_p)]
 
 
+class TrsCsr(C.Structure):
+    """struct trs_csr (include/trs.h): sorted item rows indexed by dense user id."""
+    _fields_ = [("off", C.c_void_p), ("items", C.c_void_p), ("n_rows", C.c_int64)]
+
+
 _vp, _i32, _i64, _u64, _f = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 _T, _Bp = C.POINTER(TrsTables), C.POINTER(TrsBatch)
 
@@ -149,6 +156,13 @@ PROTOTYPES = {
     "trs_topk_workspace_bytes": (C.c_int64, [_i64, _i32]),
     "trs_topk": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _vp]),
     "trs_tuning_set": (C.c_int, [C.c_char_p, _i64, _i32]),
+    "trs_item_fold_bytes": (C.c_int64, [_i64, _i32]),
+    "trs_item_fold": (C.c_int, [C.c_int, _T, _vp, _vp, _i64, _vp]),
+    "trs_retrieve_workspace_bytes": (C.c_int64, [_i64, _i32]),
+    "trs_retrieve_topk": (C.c_int, [C.c_int, _T, _vp, _i64, _vp, _i64, _i32, C.POINTER(TrsCsr), C.POINTER(TrsCsr), _vp,
+                                    _vp, _vp, _vp, _i64, _vp]),
+    "trs_mask_seen": (C.c_int, [_vp, _i64, _i64, _vp, C.POINTER(TrsCsr), _vp]),
+    "trs_rank_metrics": (C.c_int, [_vp, _i64, _i32, _vp, C.POINTER(TrsCsr), _vp, _vp]),
     "trs_mlp_gather_concat": (C.c_int, [_T, _Bp, _i32, _vp, _vp, _i64, _vp]),
     "trs_mlp_gather_gemm1_fwd": (C.c_int, [_T, _Bp, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64,
                                            _vp]),

@@ -98,22 +98,9 @@ __global__ __launch_bounds__(TRS_BLOCK) void hinge_backward_kernel(const float* 
 }
 
 // ------------------------------------------------------------------------------------------------ top-k
-// key = (orderable(score) << 32) | (0xFFFFFFFF - index): descending key order == (score desc, index asc).
-// NaN sorts first (torch.sort(descending=True) treats NaN as the largest value); -0.0 ties with +0.0.
+// Keys: trs_topk_key (trs_common.h), shared with the retrieval kernels (retrieve.hip).
 constexpr int TOPK_CHUNK = 4096;
 constexpr int TOPK_MAXK = TOPK_CHUNK / 2;
-
-__device__ __forceinline__ uint64_t topk_key(float s, uint32_t idx) {
-  uint32_t o;
-  if (s != s) {
-    o = 0xFFFFFFFFu;
-  } else {
-    if (s == 0.f) s = 0.f;
-    const uint32_t b = __float_as_uint(s);
-    o = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-  }
-  return ((uint64_t)o << 32) | (uint64_t)(0xFFFFFFFFu - idx);
-}
 
 // Each block sorts one chunk of TOPK_CHUNK keys (descending, bitonic in LDS) and emits its first k.
 // FROM_SCORES: read fp32 scores and build keys; otherwise read keys.  FINAL: write int64 indices instead of keys.
@@ -127,7 +114,7 @@ __global__ __launch_bounds__(TRS_BLOCK) void topk_chunk_kernel(const float* __re
   for (int i = threadIdx.x; i < TOPK_CHUNK; i += TRS_BLOCK) {
     const int64_t g = base + i;
     uint64_t key = 0;  // below every real key
-    if (g < n) key = FROM_SCORES ? topk_key(scores[g], (uint32_t)g) : keys_in[g];
+    if (g < n) key = FROM_SCORES ? trs_topk_key(scores[g], (uint32_t)g) : keys_in[g];
     s[i] = key;
   }
   __syncthreads();
@@ -162,7 +149,7 @@ __global__ __launch_bounds__(TRS_BLOCK) void sort_keys_kernel(const float* __res
                                                              uint64_t* __restrict__ keys) {
   const int64_t stride = (int64_t)gridDim.x * TRS_BLOCK;
   for (int64_t g = (int64_t)blockIdx.x * TRS_BLOCK + threadIdx.x; g < P; g += stride)
-    keys[g] = g < n ? topk_key(scores[g], (uint32_t)g) : 0;  // padding sorts below every real key
+    keys[g] = g < n ? trs_topk_key(scores[g], (uint32_t)g) : 0;  // padding sorts below every real key
 }
 
 __global__ __launch_bounds__(TRS_BLOCK) void sort_global_step_kernel(uint64_t* __restrict__ keys, int64_t P,

@@ -1,0 +1,550 @@
+// retrieve.hip — batched top-k retrieval over the whole catalogue with seen-item masking and ranking metrics
+// (model.py recommend / evaluate_ranking; math in include/trs.h "retrieval", design in DESIGN.md "Retrieval").
+//
+// item_fold_kernel      S (n_items_pad, Dp) = item + sum of metadata rows, c (n_items_pad) = per-item constant.
+// retrieve_topk_kernel  one workgroup = 32 query users x one split of the item tiles.  The users' rows sit in registers
+//                       as the A operand of v_mfma_f32_32x32x2_f32; each of the 4 waves multiplies them with 32 items
+//                       of a 128-item tile (B read straight from S, 16 bytes per lane).  Epilogue per score: + user and
+//                       item constants, the seen bit of the tile's LDS bitmask (filled by walking the users' sorted
+//                       seen CSR segments alongside the tiles), a compare with the user's running k-th best key, and an
+//                       append of the survivors to the user's LDS candidate buffer (RT_CAP keys).  A buffer that could
+//                       overflow in the next tile is compacted first: bitonic sort in LDS, keep k, raise the threshold.
+//                       Each workgroup writes its users' sorted top-k keys of its split to the workspace.
+// retrieve_merge_kernel joins the splits (bitonic in LDS), writes ids / scores and, given a relevance CSR, metrics.
+// mask_seen_kernel      generic path (MLP, k > KMAX): seen entries of score rows -> -inf.
+// rank_metrics_kernel   generic path: metrics of given top-k ids.
+//
+// The MFMA is an exact fp32 FMA chain (gemm.hip:1-3); the dimension order of the dot product differs from the scoring
+// kernels', so on arbitrary weights the scores agree with predict() to rounding, and exactly where all products and
+// partial sums are representable (tests/test_ranking.py).
+#include "score_kernels.h"
+
+namespace {
+
+constexpr int RT_UT = 32;                  // query users per workgroup: one 32-row MFMA block
+constexpr int RT_WAVES = 4;
+constexpr int RT_TN = RT_WAVES * 32;       // items per tile
+constexpr int RT_CAP = 256;                // candidate keys per user: KMAX + one tile of survivors
+constexpr int RT_SPLIT_TARGET = 512;       // workgroups wanted (2 per CU) when the user tiles alone are fewer
+constexpr int RT_MERGE_MAX = 4096;         // splits * k keys merged in LDS per user
+static_assert(TRS_RETRIEVE_KMAX + RT_TN <= RT_CAP, "a tile's survivors must fit behind k kept keys");
+
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+
+static inline int rt_dp(int D) {
+  if (D < 1 || D > TRS_RETRIEVE_DMAX) return 0;
+  int p = 16;
+  while (p < D) p <<= 1;
+  return p;
+}
+static inline int64_t rt_items_pad(int64_t n) { return (n + RT_TN - 1) / RT_TN * RT_TN; }
+static inline int64_t rt_user_tiles(int64_t n_q) { return (n_q + RT_UT - 1) / RT_UT; }
+static inline int64_t rt_splits(int64_t n_q, int64_t n_items, int k) {
+  int64_t s = (RT_SPLIT_TARGET + rt_user_tiles(n_q) - 1) / rt_user_tiles(n_q);
+  const int64_t tiles = rt_items_pad(n_items) / RT_TN;
+  if (s > tiles) s = tiles;
+  if (s > RT_MERGE_MAX / k) s = RT_MERGE_MAX / k;
+  return s < 1 ? 1 : s;
+}
+
+// ------------------------------------------------------------------------------------------------ fold
+// One wave per item row: lanes over the Dp columns.
+__global__ __launch_bounds__(TRS_BLOCK) void item_fold_kernel(int net, const trs_tables T, const int32_t* item_meta,
+                                                             int Dp, int64_t n_pad, float* __restrict__ S,
+                                                             float* __restrict__ c) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nwave = ((int64_t)gridDim.x * TRS_BLOCK) >> 6;
+  for (int64_t i = ((int64_t)blockIdx.x * TRS_BLOCK + threadIdx.x) >> 6; i < n_pad; i += nwave) {
+    const bool real = i < T.n_items;
+    float part = 0.f;  // FM: sum_d (S_d^2 - item_d^2 - sum_m meta_md^2)
+    float lin = 0.f;
+    for (int d = lane; d < Dp; d += 64) {
+      float s = 0.f, sq = 0.f;
+      if (real && d < T.D) {
+        const float v = T.item[i * T.D + d];
+        s = v;
+        sq = v * v;
+        for (int m = 0; m < T.M; ++m) {
+          const int64_t mid = item_meta[i * T.M + m];
+          if ((uint64_t)mid >= (uint64_t)T.n_meta[m]) continue;  // (ids were range-checked at ingest)
+          const float x = T.meta[m][mid * T.D + d];
+          s += x;
+          sq += x * x;
+        }
+      }
+      S[i * Dp + d] = s;
+      part += s * s - sq;
+    }
+    if (net == TRS_NET_FM) part = trs_wave_sum(part);
+    if (lane == 0) {
+      if (real) {
+        lin = T.item_lin[i];
+        if (net == TRS_NET_FM) {
+          for (int m = 0; m < T.M; ++m) {
+            const int64_t mid = item_meta[i * T.M + m];
+            if ((uint64_t)mid < (uint64_t)T.n_meta[m]) lin += T.meta_lin[m][mid];
+          }
+          lin += 0.5f * part;
+        }
+      }
+      c[i] = lin;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ fused top-k
+struct RetrieveArgs {
+  const float* S;
+  const float* c;
+  const float* user;
+  const float* user_lin;
+  int64_t n_users, n_items, n_tiles, tiles_per_split;
+  int D, k;
+  const int64_t* users;
+  int64_t n_q;
+  trs_csr seen;  // off == NULL: no masking
+  uint64_t* part;  // (splits, n_q, k) keys, descending
+};
+
+// Sort (descending) the candidate buffers of the users whose count exceeds `lim`, keep their first k keys and raise
+// their thresholds to the k-th key once k candidates were seen.  Called by the whole workgroup between barriers.
+__device__ void rt_compact(uint64_t* cand, uint64_t* th, int* cnt, int* flagged, int* nflag, int k, int lim) {
+  const int tid = threadIdx.x;
+  if (tid == 0) {
+    int n = 0;
+    for (int u = 0; u < RT_UT; ++u)
+      if (cnt[u] > lim) flagged[n++] = u;
+    *nflag = n;
+  }
+  __syncthreads();
+  const int nf = *nflag;
+  if (nf == 0) return;
+  for (int size = 2; size <= RT_CAP; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int i = tid; i < nf * (RT_CAP / 2); i += TRS_BLOCK) {
+        const int f = i / (RT_CAP / 2), j = i % (RT_CAP / 2);
+        uint64_t* b = cand + flagged[f] * RT_CAP;
+        const int lo = 2 * j - (j & (stride - 1));
+        const int hi = lo + stride;
+        const bool desc = (lo & size) == 0;
+        const uint64_t x = b[lo], y = b[hi];
+        if ((x < y) == desc) {
+          b[lo] = y;
+          b[hi] = x;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  for (int i = tid; i < nf * RT_CAP; i += TRS_BLOCK) {
+    const int f = i / RT_CAP, j = i % RT_CAP;
+    if (j >= k) cand[flagged[f] * RT_CAP + j] = 0;
+  }
+  if (tid < nf) {
+    const int u = flagged[tid];
+    if (cnt[u] >= k) th[u] = cand[u * RT_CAP + k - 1];
+    if (cnt[u] > k) cnt[u] = k;
+  }
+  __syncthreads();
+}
+
+template <int NQ>  // Dp = 8 * NQ
+__global__ __launch_bounds__(TRS_BLOCK, 2) void retrieve_topk_kernel(const RetrieveArgs a) {
+  constexpr int Dp = 8 * NQ;
+  __shared__ uint64_t cand[RT_UT * RT_CAP];
+  __shared__ uint64_t th[RT_UT];
+  __shared__ int cnt[RT_UT];
+  __shared__ uint32_t seenb[RT_UT * RT_WAVES];
+  __shared__ int64_t seen_p[RT_UT], seen_e[RT_UT];
+  __shared__ int flagged[RT_UT];
+  __shared__ int nflag;
+
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, col = lane & 31, h = lane >> 5;
+  const int64_t q0 = (int64_t)blockIdx.x * RT_UT;
+  const int64_t t0 = (int64_t)blockIdx.y * a.tiles_per_split;
+  const int64_t t1 = t0 + a.tiles_per_split < a.n_tiles ? t0 + a.tiles_per_split : a.n_tiles;
+
+  for (int i = tid; i < RT_UT * RT_CAP; i += TRS_BLOCK) cand[i] = 0;
+  for (int i = tid; i < RT_UT * RT_WAVES; i += TRS_BLOCK) seenb[i] = 0;
+  if (tid < RT_UT) {
+    th[tid] = 0;
+    cnt[tid] = 0;
+    int64_t lo = 0, hi = 0;
+    const int64_t q = q0 + tid;
+    if (q < a.n_q && a.seen.off) {
+      const int64_t u = a.users[q];
+      if ((uint64_t)u < (uint64_t)a.seen.n_rows) {
+        lo = a.seen.off[u];
+        hi = a.seen.off[u + 1];
+        int64_t l = lo, r = hi;  // first seen item >= the split's first item
+        const int64_t first = t0 * RT_TN;
+        while (l < r) {
+          const int64_t m = (l + r) >> 1;
+          if (a.seen.items[m] < first) l = m + 1; else r = m;
+        }
+        lo = l;
+      }
+    }
+    seen_p[tid] = lo;
+    seen_e[tid] = hi;
+  }
+
+  // A operand: lane holds U[col][8*qq + 4*h + cc] (the MFMA's k index = lane >> 5 of each float4 step)
+  float av[NQ][4];
+  {
+    const int64_t q = q0 + col;
+    const int64_t u = q < a.n_q ? a.users[q] : -1;
+    const bool ok = (uint64_t)u < (uint64_t)a.n_users;
+    const float* row = a.user + (ok ? u : 0) * (int64_t)a.D;
+#pragma unroll
+    for (int qq = 0; qq < NQ; ++qq)
+#pragma unroll
+      for (int cc = 0; cc < 4; ++cc) {
+        const int d = 8 * qq + 4 * h + cc;
+        av[qq][cc] = (ok && d < a.D) ? row[d] : 0.f;
+      }
+  }
+  // user constants of this lane's 16 accumulator rows (row = (r & 3) + 8 * (r >> 2) + 4 * h, gemm.hip epilogue map)
+  float ucon[16];
+  uint32_t live = 0;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int64_t q = q0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+    const int64_t u = q < a.n_q ? a.users[q] : -1;
+    const bool ok = (uint64_t)u < (uint64_t)a.n_users;
+    ucon[r] = ok ? a.user_lin[u] : 0.f;
+    live |= (ok ? 1u : 0u) << r;
+  }
+
+  for (int64_t t = t0; t < t1; ++t) {
+    __syncthreads();  // the previous tile's appends are done
+    rt_compact(cand, th, cnt, flagged, &nflag, a.k, RT_CAP - RT_TN);
+    const int64_t base = t * RT_TN;
+    if (tid < RT_UT && a.seen.off) {
+      uint32_t* wb = seenb + tid * RT_WAVES;
+#pragma unroll
+      for (int j = 0; j < RT_WAVES; ++j) wb[j] = 0;
+      int64_t p = seen_p[tid];
+      const int64_t e = seen_e[tid];
+      while (p < e) {
+        const int64_t it = a.seen.items[p];
+        if (it >= base + RT_TN) break;
+        if (it >= base) wb[(it - base) >> 5] |= 1u << ((it - base) & 31);
+        ++p;
+      }
+      seen_p[tid] = p;
+    }
+    __syncthreads();
+
+    const int64_t item = base + w * 32 + col;
+    const float* sb = a.S + item * Dp + 4 * h;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+    for (int qq = 0; qq < NQ; ++qq) {
+      const float4 b = *reinterpret_cast<const float4*>(sb + 8 * qq);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[qq][0], b.x, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[qq][1], b.y, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[qq][2], b.z, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[qq][3], b.w, acc, 0, 0, 0);
+    }
+    const float ci = a.c[item];
+    const bool in_range = item < a.n_items;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int ur = (r & 3) + 8 * (r >> 2) + 4 * h;
+      const bool seen = (seenb[ur * RT_WAVES + w] >> col) & 1u;
+      const float s = (acc[r] + ucon[r]) + ci;
+      const uint64_t key = (in_range && !seen && ((live >> r) & 1u)) ? trs_topk_key(s, (uint32_t)item) : 0;
+      if (key > th[ur]) {
+        const int p = atomicAdd(&cnt[ur], 1);
+        cand[ur * RT_CAP + p] = key;
+      }
+    }
+  }
+  __syncthreads();
+  rt_compact(cand, th, cnt, flagged, &nflag, a.k, 0);
+  uint64_t* out = a.part + (int64_t)blockIdx.y * a.n_q * a.k;
+  for (int i = tid; i < RT_UT * a.k; i += TRS_BLOCK) {
+    const int u = i / a.k, j = i % a.k;
+    const int64_t q = q0 + u;
+    if (q < a.n_q) out[q * a.k + j] = cand[u * RT_CAP + j];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ metrics
+// (hits, dcg, idcg, n_rel) of the list ids[0..k) (dense ids, -1 = none) against rel row u, in ascending r.
+__device__ void rt_metrics(const int64_t* ids, int k, int64_t u, const trs_csr rel, double* out) {
+  int64_t lo = 0, hi = 0;
+  if ((uint64_t)u < (uint64_t)rel.n_rows) {
+    lo = rel.off[u];
+    hi = rel.off[u + 1];
+  }
+  double hits = 0.0, dcg = 0.0, idcg = 0.0;
+  for (int r = 0; r < k; ++r) {
+    const int64_t id = ids[r];
+    bool hit = false;
+    if (id >= 0) {
+      int64_t l = lo, rr = hi;
+      while (l < rr) {
+        const int64_t m = (l + rr) >> 1;
+        const int64_t v = rel.items[m];
+        if (v == id) {
+          hit = true;
+          break;
+        }
+        if (v < id) l = m + 1; else rr = m;
+      }
+    }
+    const double g = 1.0 / log2((double)(r + 2));
+    if (hit) {
+      hits += 1.0;
+      dcg += g;
+    }
+    if (r < hi - lo) idcg += g;
+  }
+  out[0] = hits;
+  out[1] = dcg;
+  out[2] = idcg;
+  out[3] = (double)(hi - lo);
+}
+
+struct MergeArgs {
+  const uint64_t* part;
+  int64_t n_q, splits;
+  int k, fm;
+  const int64_t* users;
+  trs_csr rel;  // off == NULL: no metrics
+  int64_t* ids;
+  float* scores;
+  double* metrics;
+};
+
+// One workgroup per query user (grid-stride): the splits' k keys each -> the best k.
+__global__ __launch_bounds__(TRS_BLOCK) void retrieve_merge_kernel(const MergeArgs m) {
+  __shared__ uint64_t s[RT_MERGE_MAX];
+  __shared__ int64_t ids[TRS_RETRIEVE_KMAX];
+  const int tid = threadIdx.x;
+  const int n = (int)(m.splits * m.k);
+  int P = 1;
+  while (P < n) P <<= 1;
+  for (int64_t q = blockIdx.x; q < m.n_q; q += gridDim.x) {
+    __syncthreads();
+    for (int i = tid; i < P; i += TRS_BLOCK) {
+      uint64_t key = 0;
+      if (i < n) key = m.part[((int64_t)(i / m.k) * m.n_q + q) * m.k + i % m.k];
+      s[i] = key;
+    }
+    __syncthreads();
+    if (m.splits > 1) {
+      for (int size = 2; size <= P; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+          for (int i = tid; i < P / 2; i += TRS_BLOCK) {
+            const int lo = 2 * i - (i & (stride - 1));
+            const int hi = lo + stride;
+            const bool desc = (lo & size) == 0;
+            const uint64_t x = s[lo], y = s[hi];
+            if ((x < y) == desc) {
+              s[lo] = y;
+              s[hi] = x;
+            }
+          }
+          __syncthreads();
+        }
+      }
+    }
+    for (int j = tid; j < m.k; j += TRS_BLOCK) {
+      const uint64_t key = s[j];
+      int64_t id = -1;
+      float sc = -INFINITY;
+      if (key != 0) {
+        id = (int64_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFu));
+        sc = trs_topk_key_score(key);
+        if (m.fm) sc = trs::sigmoidf_(sc);
+      }
+      ids[j] = id;
+      m.ids[q * m.k + j] = id;
+      m.scores[q * m.k + j] = sc;
+    }
+    __syncthreads();
+    if (m.rel.off && tid == 0) rt_metrics(ids, m.k, m.users[q], m.rel, m.metrics + q * 4);
+  }
+}
+
+__global__ __launch_bounds__(TRS_BLOCK) void rank_metrics_kernel(const int64_t* ids, int64_t n_q, int k,
+                                                                const int64_t* users, const trs_csr rel,
+                                                                double* out) {
+  const int64_t stride = (int64_t)gridDim.x * TRS_BLOCK;
+  for (int64_t q = (int64_t)blockIdx.x * TRS_BLOCK + threadIdx.x; q < n_q; q += stride)
+    rt_metrics(ids + q * k, k, users[q], rel, out + q * 4);
+}
+
+// One workgroup per score row (grid-stride): the user's seen items -> -inf.
+__global__ __launch_bounds__(TRS_BLOCK) void mask_seen_kernel(float* scores, int64_t n_rows, int64_t n_items,
+                                                             const int64_t* users, const trs_csr seen) {
+  for (int64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
+    const int64_t u = users[r];
+    if ((uint64_t)u >= (uint64_t)seen.n_rows) continue;
+    const int64_t lo = seen.off[u], hi = seen.off[u + 1];
+    for (int64_t p = lo + threadIdx.x; p < hi; p += TRS_BLOCK) {
+      const int64_t it = seen.items[p];
+      if ((uint64_t)it < (uint64_t)n_items) scores[r * n_items + it] = -INFINITY;
+    }
+  }
+}
+
+static int check_csr(const trs_csr* c, const char* who, const char* what) {
+  TRS_REQUIRE(c->off && c->items && c->n_rows >= 0, "%s: %s CSR has NULL arrays", who, what);
+  return TRS_OK;
+}
+
+template <int NQ>
+static void launch_retrieve(const RetrieveArgs& a, dim3 grid, hipStream_t s) {
+  hipLaunchKernelGGL(retrieve_topk_kernel<NQ>, grid, dim3(TRS_BLOCK), 0, s, a);
+}
+
+}  // namespace
+
+extern "C" int64_t trs_item_fold_bytes(int64_t n_items, int32_t D) {
+  const int Dp = rt_dp(D);
+  if (n_items <= 0 || Dp == 0) return 0;
+  return rt_items_pad(n_items) * (int64_t)(Dp + 1) * 4;
+}
+
+extern "C" int trs_item_fold(int net, const trs_tables* T, const int32_t* item_meta_dev, void* fold_dev,
+                             int64_t fold_bytes, void* stream) {
+  TRS_REQUIRE(T != nullptr, "trs_item_fold: tables is NULL");
+  TRS_REQUIRE(net == TRS_NET_LINEAR || net == TRS_NET_FM, "trs_item_fold: net must be TRS_NET_LINEAR or TRS_NET_FM");
+  TRS_REQUIRE(T->item && T->item_lin && T->n_items > 0, "trs_item_fold: item table is NULL/empty");
+  TRS_REQUIRE(T->M >= 0 && T->M <= TRS_MAX_META, "trs_item_fold: M=%d outside 0..%d", T->M, TRS_MAX_META);
+  TRS_REQUIRE(T->M == 0 || item_meta_dev, "trs_item_fold: item_meta is NULL but M=%d", T->M);
+  for (int m = 0; m < T->M; ++m) {
+    TRS_REQUIRE(T->meta[m], "trs_item_fold: metadata table %d is NULL", m);
+    if (net == TRS_NET_FM) TRS_REQUIRE(T->meta_lin[m], "trs_item_fold: linear_metadata table %d is NULL", m);
+  }
+  const int64_t need = trs_item_fold_bytes(T->n_items, T->D);
+  TRS_REQUIRE(need > 0, "trs_item_fold: D=%d outside 1..%d", T->D, TRS_RETRIEVE_DMAX);
+  TRS_REQUIRE(fold_dev && fold_bytes >= need, "trs_item_fold: fold buffer too small (%lld < %lld)",
+              (long long)fold_bytes, (long long)need);
+  const int Dp = rt_dp(T->D);
+  const int64_t n_pad = rt_items_pad(T->n_items);
+  float* S = (float*)fold_dev;
+  hipLaunchKernelGGL(item_fold_kernel, dim3(trs_grid(n_pad, TRS_BLOCK / 64)), dim3(TRS_BLOCK), 0, (hipStream_t)stream,
+                     net, *T, item_meta_dev, Dp, n_pad, S, S + n_pad * Dp);
+  TRS_CHECK_LAUNCH("item_fold_kernel");
+  return TRS_OK;
+}
+
+extern "C" int64_t trs_retrieve_workspace_bytes(int64_t n_q, int32_t k) {
+  if (n_q <= 0 || k <= 0) return 0;
+  // splits <= ceil(TARGET / tiles) -> splits * n_q <= (TARGET + tiles) * RT_UT: a bound monotone in n_q and k
+  return (RT_SPLIT_TARGET + rt_user_tiles(n_q)) * (int64_t)RT_UT * k * 8;
+}
+
+extern "C" int trs_retrieve_topk(int net, const trs_tables* T, const void* fold_dev, int64_t fold_bytes,
+                                 const int64_t* users_dev, int64_t n_q, int32_t k, const trs_csr* seen,
+                                 const trs_csr* rel, int64_t* ids_out_dev, float* scores_out_dev,
+                                 double* metrics_out_dev, void* workspace_dev, int64_t workspace_bytes, void* stream) {
+  const char* who = "trs_retrieve_topk";
+  TRS_REQUIRE(T != nullptr, "%s: tables is NULL", who);
+  TRS_REQUIRE(net == TRS_NET_LINEAR || net == TRS_NET_FM, "%s: net must be TRS_NET_LINEAR or TRS_NET_FM", who);
+  TRS_REQUIRE(T->user && T->user_lin && T->n_users > 0 && T->n_items > 0, "%s: user table is NULL/empty", who);
+  TRS_REQUIRE(k >= 1 && k <= TRS_RETRIEVE_KMAX, "%s: k=%d outside 1..%d (larger k: score rows + trs_topk)", who, k,
+              TRS_RETRIEVE_KMAX);
+  TRS_REQUIRE(k <= T->n_items, "%s: k=%d > n_items=%lld", who, k, (long long)T->n_items);
+  TRS_REQUIRE(n_q >= 0, "%s: negative n_q", who);
+  const int64_t fneed = trs_item_fold_bytes(T->n_items, T->D);
+  TRS_REQUIRE(fneed > 0, "%s: D=%d outside 1..%d", who, T->D, TRS_RETRIEVE_DMAX);
+  TRS_REQUIRE(fold_dev && fold_bytes >= fneed, "%s: fold buffer too small (%lld < %lld)", who, (long long)fold_bytes,
+              (long long)fneed);
+  TRS_REQUIRE(workspace_bytes >= trs_retrieve_workspace_bytes(n_q, k) && (workspace_dev || n_q == 0),
+              "%s: workspace too small (%lld < %lld)", who, (long long)workspace_bytes,
+              (long long)trs_retrieve_workspace_bytes(n_q, k));
+  if (seen) {
+    const int rc = check_csr(seen, who, "seen");
+    if (rc) return rc;
+  }
+  if (rel) {
+    const int rc = check_csr(rel, who, "relevance");
+    if (rc) return rc;
+    TRS_REQUIRE(metrics_out_dev, "%s: a relevance CSR needs metrics_out", who);
+  }
+  if (n_q == 0) return TRS_OK;
+  TRS_REQUIRE(users_dev && ids_out_dev && scores_out_dev, "%s: users/ids_out/scores_out is NULL", who);
+  const int Dp = rt_dp(T->D);
+  const int64_t n_pad = rt_items_pad(T->n_items);
+  const int64_t splits = rt_splits(n_q, T->n_items, k);
+  const int64_t n_tiles = n_pad / RT_TN;
+  RetrieveArgs a = {};
+  a.S = (const float*)fold_dev;
+  a.c = a.S + n_pad * Dp;
+  a.user = T->user;
+  a.user_lin = T->user_lin;
+  a.n_users = T->n_users;
+  a.n_items = T->n_items;
+  a.n_tiles = n_tiles;
+  a.tiles_per_split = (n_tiles + splits - 1) / splits;
+  a.D = T->D;
+  a.k = k;
+  a.users = users_dev;
+  a.n_q = n_q;
+  if (seen) a.seen = *seen;
+  a.part = (uint64_t*)workspace_dev;
+  const int64_t used = (n_tiles + a.tiles_per_split - 1) / a.tiles_per_split;  // splits that own at least one tile
+  TRS_REQUIRE(rt_user_tiles(n_q) < ((int64_t)1 << 31), "%s: too many query users in one call", who);
+  const dim3 grid((unsigned)rt_user_tiles(n_q), (unsigned)used);
+  hipStream_t s = (hipStream_t)stream;
+  switch (Dp) {
+    case 16: launch_retrieve<2>(a, grid, s); break;
+    case 32: launch_retrieve<4>(a, grid, s); break;
+    case 64: launch_retrieve<8>(a, grid, s); break;
+    case 128: launch_retrieve<16>(a, grid, s); break;
+    default: launch_retrieve<32>(a, grid, s); break;
+  }
+  TRS_CHECK_LAUNCH("retrieve_topk_kernel");
+  MergeArgs m = {};
+  m.part = a.part;
+  m.n_q = n_q;
+  m.splits = used;
+  m.k = k;
+  m.fm = net == TRS_NET_FM;
+  m.users = users_dev;
+  if (rel) m.rel = *rel;
+  m.ids = ids_out_dev;
+  m.scores = scores_out_dev;
+  m.metrics = metrics_out_dev;
+  const int64_t mg = n_q < 65536 ? n_q : 65536;
+  hipLaunchKernelGGL(retrieve_merge_kernel, dim3((unsigned)mg), dim3(TRS_BLOCK), 0, s, m);
+  TRS_CHECK_LAUNCH("retrieve_merge_kernel");
+  return TRS_OK;
+}
+
+extern "C" int trs_mask_seen(float* scores_dev, int64_t n_rows, int64_t n_items, const int64_t* users_dev,
+                             const trs_csr* seen, void* stream) {
+  TRS_REQUIRE(n_rows >= 0 && n_items > 0, "trs_mask_seen: bad sizes");
+  TRS_REQUIRE(seen != nullptr, "trs_mask_seen: seen CSR is NULL");
+  const int rc = check_csr(seen, "trs_mask_seen", "seen");
+  if (rc) return rc;
+  if (n_rows == 0) return TRS_OK;
+  TRS_REQUIRE(scores_dev && users_dev, "trs_mask_seen: scores/users is NULL");
+  hipLaunchKernelGGL(mask_seen_kernel, dim3((unsigned)(n_rows < 65536 ? n_rows : 65536)), dim3(TRS_BLOCK), 0,
+                     (hipStream_t)stream, scores_dev, n_rows, n_items, users_dev, *seen);
+  TRS_CHECK_LAUNCH("mask_seen_kernel");
+  return TRS_OK;
+}
+
+extern "C" int trs_rank_metrics(const int64_t* ids_dev, int64_t n_q, int32_t k, const int64_t* users_dev,
+                                const trs_csr* rel, double* metrics_out_dev, void* stream) {
+  TRS_REQUIRE(k >= 1, "trs_rank_metrics: k=%d < 1", k);
+  TRS_REQUIRE(n_q >= 0, "trs_rank_metrics: negative n_q");
+  TRS_REQUIRE(rel != nullptr, "trs_rank_metrics: relevance CSR is NULL");
+  const int rc = check_csr(rel, "trs_rank_metrics", "relevance");
+  if (rc) return rc;
+  if (n_q == 0) return TRS_OK;
+  TRS_REQUIRE(ids_dev && users_dev && metrics_out_dev, "trs_rank_metrics: ids/users/metrics_out is NULL");
+  hipLaunchKernelGGL(rank_metrics_kernel, dim3(trs_grid(n_q, TRS_BLOCK)), dim3(TRS_BLOCK), 0, (hipStream_t)stream,
+                     ids_dev, n_q, (int)k, users_dev, *rel, metrics_out_dev);
+  TRS_CHECK_LAUNCH("rank_metrics_kernel");
+  return TRS_OK;
+}

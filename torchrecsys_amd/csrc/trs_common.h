@@ -224,6 +224,27 @@ __host__ __device__ __forceinline__ int64_t trs_feistel_perm(int64_t q, int64_t 
   return (int64_t)x;
 }
 
+// ------------------------------------------------------------------------------------------ top-k keys
+// key = (orderable(score) << 32) | (0xFFFFFFFF - index): descending key order == (score desc, index asc).
+// NaN sorts first (torch.sort(descending=True) treats NaN as the largest value); -0.0 ties with +0.0.  Key 0 is below
+// every real key (padding / excluded items).  Used by the predict() top-k (hinge_topk.hip) and retrieval (retrieve.hip).
+__device__ __forceinline__ uint64_t trs_topk_key(float s, uint32_t idx) {
+  uint32_t o;
+  if (s != s) {
+    o = 0xFFFFFFFFu;
+  } else {
+    if (s == 0.f) s = 0.f;
+    const uint32_t b = __float_as_uint(s);
+    o = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+  }
+  return ((uint64_t)o << 32) | (uint64_t)(0xFFFFFFFFu - idx);
+}
+// score of a key (inverse of the orderable map; -0.0 comes back as +0.0)
+__device__ __forceinline__ float trs_topk_key_score(uint64_t key) {
+  const uint32_t o = (uint32_t)(key >> 32);
+  return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
+}
+
 // ------------------------------------------------------------------------------------------ reductions
 // sum over the G lanes of an aligned lane group (G power of two <= 64); every lane of the group gets the sum.
 template <int G>

@@ -287,7 +287,7 @@ class TorchRecSys(torch.nn.Module):
             return None
         if 'sampler' not in self._dev_cache:
             st = self._device_stream('train')
-            seen = ops.Sampler.seen_csr(st['user'], st['pos'], self.n_users, self.n_items) if ns.get("reject_seen") else None
+            seen = self._seen_csr() if ns.get("reject_seen") else None
             self._dev_cache['sampler'] = ops.Sampler(k=ns.get("k", 1), popularity=ns.get("popularity", False), seen=seen,
                                                      stream_item=st['pos'], max_tries=ns.get("max_tries", 8))
         return self._dev_cache['sampler']
@@ -302,6 +302,14 @@ class TorchRecSys(torch.nn.Module):
             self._dev_cache['eval_sampler'] = ops.Sampler(k=1, popularity=ns.get("popularity", False), seen=sm.keep[0],
                                                           stream_item=sm.keep[1], max_tries=ns.get("max_tries", 8))
         return self._dev_cache['eval_sampler']
+
+    def _seen_csr(self):
+        """CSR of the train split's distinct (user, item) pairs (this rank's rows under data parallelism), built once:
+        the sampler's reject_seen and recommend() / evaluate_ranking() exclude the same items."""
+        if 'seen_csr' not in self._dev_cache:
+            st = self._device_stream('train')
+            self._dev_cache['seen_csr'] = ops.Sampler.seen_csr(st['user'], st['pos'], self.n_users, self.n_items)
+        return self._dev_cache['seen_csr']
 
     def _item_meta_dev(self):
         tab = self.data_processor.item_meta_table
@@ -498,6 +506,176 @@ class TorchRecSys(torch.nn.Module):
         for r, u in enumerate(users):
             out[r] = ops.topk(self.net.score_all_items(u, meta), k)
         return self._original_items(out.cpu())
+
+    # ------------------------------------------------------------------------------------------------ retrieval
+    RECOMMEND_CHUNK = 65_536  # query users per fused call: bounds the workspace ((512 + n/32) * 32 * k * 8 bytes)
+    GENERIC_CHUNK = 16        # score rows per pass of the generic path (MLP, k > KMAX)
+
+    def _dense_users(self, user_ids):
+        """Table rows of a list of caller user ids (vectorised _dense_user); IndexError on an unknown id."""
+        ids = torch.as_tensor(user_ids.tolist() if hasattr(user_ids, "tolist") else list(user_ids), dtype=torch.int64)
+        ids = ids.reshape(-1)
+        idx = getattr(self.data_processor, "user_index", None)
+        if idx is None:
+            bad = (ids < 0) | (ids >= self.n_users)
+            if bool(bad.any()):
+                raise IndexError(f"user id {int(ids[bad][0])} outside [0, {self.n_users})")
+            return ids
+        idx = idx.cpu().to(torch.int64)
+        pos = torch.searchsorted(idx, ids)
+        ok = pos < idx.numel()
+        ok[ok.clone()] = idx[pos[ok]] == ids[ok]
+        if not bool(ok.all()):
+            raise IndexError(f"user id {int(ids[~ok][0])} does not occur in the ingested interactions")
+        return pos
+
+    def _fused_retrieval(self, k):
+        return hasattr(self.net, 'table_params') and k <= ops._lib.RETRIEVE_KMAX and \
+            self.n_factors <= ops._lib.RETRIEVE_DMAX
+
+    def _rank_dense(self, users, k, exclude_seen, rel=None):
+        """Top-k of dense users (int64 GPU tensor): (ids (n,k) dense int64 with -1 padding, scores (n,k) fp32, metrics
+        (n,4) float64 or None).  Linear / FM with k <= KMAX: the fused kernel; otherwise score rows + mask + top-k."""
+        dev = users.device
+        seen = self._seen_csr() if exclude_seen else None
+        meta = self._item_meta_dev()
+        n = users.numel()
+        if self._fused_retrieval(k):
+            T = self.net.tables()
+            fold = ops.item_fold(self.net.NET, T, self.n_items, self.n_factors, dev, meta)
+            outs = [ops.retrieve_topk(self.net.NET, T, fold, users[s:s + self.RECOMMEND_CHUNK], k, seen, rel)
+                    for s in range(0, n, self.RECOMMEND_CHUNK)]
+            ids = torch.cat([o[0] for o in outs])
+            scores = torch.cat([o[1] for o in outs])
+            met = torch.cat([o[2] for o in outs]) if rel is not None else None
+            return ids, scores, met
+        # generic path: existing score rows, seen entries -> -inf, trs_topk, -1 beyond the user's unseen items.
+        # Linear / FM rank the rows of the folded form (Linear scores, FM logits z: score_all_items of a Linear scorer
+        # over S / c with the users' rows padded to Dp); FM's returned scores are its own sigmoid rows.
+        ids = torch.empty((n, k), dtype=torch.int64, device=dev)
+        scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+        ar = torch.arange(k, device=dev)
+        fold = None
+        if hasattr(self.net, 'table_params'):
+            fold = ops.item_fold(self.net.NET, self.net.tables(), self.n_items, self.n_factors, dev, meta)
+        if fold is not None:
+            S, c = ops.fold_views(fold, self.n_items, self.n_factors)
+            tp = self.net.table_params()
+        for s in range(0, n, self.GENERIC_CHUNK):
+            us = users[s:s + self.GENERIC_CHUNK]
+            if fold is None:
+                rows = torch.stack([self.net.score_all_items(int(u), meta) for u in us.tolist()])
+                out_rows = rows
+            else:
+                Ut = torch.zeros((us.numel(), S.shape[1]), dtype=torch.float32, device=dev)
+                Ut[:, :self.n_factors] = tp[0].data[us]
+                Tz, keep = ops.make_tables(Ut, S, tp[2].data[us].contiguous(), c.view(-1, 1))
+                rows = torch.stack([ops.score_all_items("linear", Tz, r, self.n_items, dev)
+                                    for r in range(us.numel())])
+                out_rows = rows if self.net.NET == "linear" else \
+                    torch.stack([self.net.score_all_items(int(u), meta) for u in us.tolist()])
+            if seen is not None:
+                ops.mask_seen(rows, us, seen)
+                n_seen = (seen[0][us + 1] - seen[0][us])
+            else:
+                n_seen = torch.zeros_like(us)
+            top = torch.stack([ops.topk(rows[r], k) for r in range(rows.shape[0])])
+            pad = ar[None, :] >= (self.n_items - n_seen)[:, None]
+            sc = torch.gather(out_rows, 1, top)
+            ids[s:s + us.numel()] = torch.where(pad, torch.full_like(top, -1), top)
+            scores[s:s + us.numel()] = torch.where(pad, torch.full_like(sc, float('-inf')), sc)
+        met = ops.rank_metrics(ids, users, rel) if rel is not None and n else None
+        return ids, scores, met
+
+    @_host_side
+    def recommend(self, user_ids, top_k: int = 10, exclude_seen: bool = True, return_scores: bool = False):
+        """Top-k item ids of several users at once: an (n, k) int64 CPU tensor of original item ids, k = min(top_k,
+        n_items); with return_scores also the (n, k) fp32 scores in the scorer's output units.  exclude_seen drops the
+        items each user has in the train split; a user with fewer than k other items gets id -1 / score -inf in the
+        remaining positions.  Ties are ordered by ascending item id as in predict().
+        Linear and FM (k <= TRS_RETRIEVE_KMAX, D <= TRS_RETRIEVE_DMAX) run one fused fp32 matrix-core kernel over user
+        tiles x item tiles with the top-k selection in its epilogue; the MLP and larger k score rows one user at a time.
+        FM ranks by the logit z before its sigmoid: this is the one place where the order can differ from predict(),
+        which sorts the fp32 sigmoid values (equal where the sigmoid saturates; recommend keeps z's order there).
+        Scores may differ from predict()'s in the last bits (another summation order over the factors)."""
+        self.net = self.net.eval()
+        ulist = user_ids.tolist() if hasattr(user_ids, "tolist") else list(user_ids)
+        k = min(int(top_k), self.n_items)
+        if k <= 0 or not ulist:
+            e = torch.empty((len(ulist), max(k, 0)), dtype=torch.int64)
+            return (e, torch.empty(e.shape, dtype=torch.float32)) if return_scores else e
+        users = self._dense_users(ulist).to(_device())
+        ids, scores, _ = self._rank_dense(users, k, exclude_seen)
+        ids = ids.cpu()
+        idx = getattr(self.data_processor, "item_index", None)
+        if idx is not None:
+            keep = ids >= 0
+            ids[keep] = idx.cpu().to(torch.int64)[ids[keep]]
+        return (ids, scores.cpu()) if return_scores else ids
+
+    def _relevance_csr(self, exclude_seen):
+        """CSR of the test split's distinct (user, item) pairs over dense users; with exclude_seen without the pairs
+        that are also in the train split (this rank's train rows: under dp_partition 'user' all rows of its users)."""
+        dev = _device()
+        td = self.data_processor.test_data
+        key = torch.unique(td['user_id'].to(torch.int64).to(dev) * int(self.n_items) + td['pos_item_id'].to(torch.int64).to(dev))
+        if exclude_seen:
+            off, items = self._seen_csr()
+            su = torch.repeat_interleave(torch.arange(self.n_users, device=dev), off[1:] - off[:-1])
+            key = key[~torch.isin(key, su * int(self.n_items) + items.long())]
+        u = torch.div(key, int(self.n_items), rounding_mode="floor")
+        off = torch.zeros(self.n_users + 1, dtype=torch.int64, device=dev)
+        off[1:] = torch.cumsum(torch.bincount(u, minlength=self.n_users), 0)
+        return off, (key - u * int(self.n_items)).to(torch.int32).contiguous()
+
+    @_host_side
+    def evaluate_ranking(self, k: int = 10, metrics=('hit_rate', 'recall', 'ndcg'), exclude_seen: bool = True,
+                         users=None):
+        """Ranking metrics of recommend() over the full catalogue against the test split; returns
+        {f'{m}@{k}': float, 'n_users': int} and prints them as evaluate() does.
+        Users: the distinct users of the test split (or `users`, caller ids).  T_u = the user's distinct test items,
+        without the ones it also has in train when exclude_seen; users with an empty T_u are skipped.  R_u = the top-k list:
+          hit_rate@k = 1[|R_u & T_u| >= 1]     recall@k = |R_u & T_u| / |T_u|
+          ndcg@k     = sum_{r<k, R_u[r] in T_u} 1/log2(r+2)  /  sum_{r<min(k,|T_u|)} 1/log2(r+2)
+        averaged over the evaluated users (per-user values from the device, sums in float64 in ascending user order).
+        Data parallel: rank r evaluates the users with user_id % world == r and the sums are all-reduced (needs
+        dp_partition='user' without pre_sharded: a rank must hold all train rows of its users)."""
+        unknown = set(metrics) - {'hit_rate', 'recall', 'ndcg'}
+        if unknown:
+            raise ValueError(f"unknown ranking metrics {sorted(unknown)}")
+        rank, world = tdist.world_info()
+        if world > 1 and (getattr(self, 'pre_sharded', False) or self.dp_partition != 'user'):
+            raise ValueError("evaluate_ranking under data parallelism needs dp_partition='user' without pre_sharded: "
+                             "a rank must hold every train and test row of the users it evaluates")
+        self.net = self.net.eval()
+        dev = _device()
+        kk = min(int(k), self.n_items)
+        rel = self._relevance_csr(exclude_seen)
+        if users is None:
+            dense = torch.unique(self.data_processor.test_data['user_id'].to(torch.int64))
+        else:
+            dense = torch.unique(self._dense_users(users))
+        if world > 1:
+            dense = dense[dense % world == rank]
+        dense = dense.to(dev)
+        dense = dense[(rel[0][dense + 1] - rel[0][dense]) > 0]
+        sums = np.zeros(4)
+        if dense.numel() and kk > 0:
+            _, _, met = self._rank_dense(dense, kk, exclude_seen, rel)
+            m = met.cpu().numpy()
+            sums = np.array([float(np.sum(m[:, 0] >= 1)), float(np.sum(m[:, 0] / m[:, 3])),
+                             float(np.sum(m[:, 1] / m[:, 2])), float(m.shape[0])])
+        if world > 1:
+            sums = np.array(tdist.allreduce_scalar_sum(sums.tolist(), dev))
+        n = int(sums[3])
+        col = {'hit_rate': 0, 'recall': 1, 'ndcg': 2}
+        results = {}
+        for metric in metrics:
+            value = float(sums[col[metric]] / n) if n else 0.0
+            results[f'{metric}@{k}'] = value
+            print(f'|--- Testing {metric}@{k}: {value:.4f}')
+        results['n_users'] = n
+        return results
 
 
 class FitRunner:

@@ -535,6 +535,78 @@ def topk(scores, k):
     return out
 
 
+
+# ------------------------------------------------------------------------------------------------- retrieval
+def csr(off, items):
+    """trs_csr of a sorted CSR (offsets int64 (n_rows+1,), items int32) on the GPU; None -> NULL."""
+    if off is None:
+        return None
+    _dev(off, "CSR offsets", torch.int64)
+    _dev(items, "CSR items", torch.int32)
+    c = _lib.TrsCsr()
+    c.off, c.items, c.n_rows = ptr(off), ptr(items), off.numel() - 1
+    return c
+
+
+def item_fold(net, T, n_items, D, device, item_meta=None):
+    """Folded item matrix S and constants c of a Linear / FM scorer (trs_item_fold) as one uint8 buffer, or None when
+    D is beyond the fused kernel."""
+    lib = _lib.load()
+    nb = lib.trs_item_fold_bytes(int(n_items), int(D))
+    if nb <= 0:
+        return None
+    buf = torch.empty(nb, dtype=torch.uint8, device=device)
+    check(lib.trs_item_fold(NET_ID[net], C.byref(T), ptr(item_meta), ptr(buf), nb, _stream()), "trs_item_fold")
+    return buf
+
+
+def fold_views(fold, n_items, D):
+    """(S (n_items, Dp) fp32, c (n_items,) fp32) views of a trs_item_fold buffer (layout: include/trs.h)."""
+    n_pad = (n_items + 127) // 128 * 128
+    Dp = fold.numel() // (4 * n_pad) - 1
+    f = fold.view(torch.float32)
+    return f[:n_items * Dp].view(n_items, Dp), f[n_pad * Dp:n_pad * Dp + n_items]
+
+
+def retrieve_topk(net, T, fold, users, k, seen=None, rel=None):
+    """Fused top-k of dense users (int64 GPU tensor) over the catalogue: (ids (n,k) int64, scores (n,k) fp32,
+    metrics (n,4) float64 or None).  seen / rel: (offsets, items) CSRs or None."""
+    lib = _lib.load()
+    _dev(users, "query users", torch.int64)
+    n = users.numel()
+    dev = users.device
+    ids = torch.empty((n, k), dtype=torch.int64, device=dev)
+    scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+    met = torch.empty((n, 4), dtype=torch.float64, device=dev) if rel is not None else None
+    ws_bytes = lib.trs_retrieve_workspace_bytes(n, k)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    cs, cr = csr(*seen) if seen is not None else None, csr(*rel) if rel is not None else None
+    check(lib.trs_retrieve_topk(NET_ID[net], C.byref(T), ptr(fold), fold.numel(), ptr(users), n, int(k),
+                                C.byref(cs) if cs is not None else None, C.byref(cr) if cr is not None else None,
+                                ptr(ids), ptr(scores), ptr(met), ptr(ws), ws_bytes, _stream()), "trs_retrieve_topk")
+    return ids, scores, met
+
+
+def mask_seen(scores, users, seen):
+    """Seen entries of score rows (n, n_items) fp32 -> -inf (trs_mask_seen), in place."""
+    _dev(scores, "score rows", torch.float32)
+    _dev(users, "users", torch.int64)
+    cs = csr(*seen)
+    check(_lib.load().trs_mask_seen(ptr(scores), scores.shape[0], scores.shape[1], ptr(users), C.byref(cs), _stream()),
+          "trs_mask_seen")
+    return scores
+
+
+def rank_metrics(ids, users, rel):
+    """(hits, dcg, idcg, n_rel) float64 (n, 4) of top-k ids (n, k) int64 (-1 = none) against rel (trs_rank_metrics)."""
+    _dev(ids, "top-k ids", torch.int64)
+    _dev(users, "users", torch.int64)
+    out = torch.empty((ids.shape[0], 4), dtype=torch.float64, device=ids.device)
+    cr = csr(*rel)
+    check(_lib.load().trs_rank_metrics(ptr(ids), ids.shape[0], ids.shape[1], ptr(users), C.byref(cr), ptr(out),
+                                       _stream()), "trs_rank_metrics")
+    return out
+
 # ------------------------------------------------------------------------------------------------- MLP kernels
 def mlp_gather_concat(T, Bt, passes, x=None, x16=None):
     """x: fp32 (rows, (2+M)D) and/or x16: the same image in bfloat16 (same row stride in elements)."""
