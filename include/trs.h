@@ -493,6 +493,46 @@ int trs_mask_seen(float* scores_dev, int64_t n_rows, int64_t n_items, const int6
 int trs_rank_metrics(const int64_t* ids_dev, int64_t n_q, int32_t k, const int64_t* users_dev, const trs_csr* rel,
                      double* metrics_out_dev, void* stream);
 
+/* ------------------------------------------------------------------------------- in-batch softmax (fit) */
+/* Training loss of fit(loss='softmax') for the Linear / FM scorers (Yi et al., RecSys 2019).  Batch
+ * rows i < B are (user u_i, positive p_i, metadata m_i) of a trs_batch (neg / neg_meta unused).  With
+ *   S_j = item_pj + sum_m meta_m[m_jm]      c_j = item_lin_pj (Linear),
+ *                                           c_j = item_lin_pj + sum_m meta_lin_m + 1/2 (|S_j|^2 - |item|^2 - sum_m |meta_m|^2) (FM)
+ * the adjusted logits are zh_ij = (<U_ui, S_j> + c_j) / tau - L_j (the user-side 1-wide term cancels in a row softmax),
+ * L_j = logq[p_j] when a log-Q table is given (else 0), and zh_ij = -inf for j != i with p_j == p_i (accidental hits).
+ *   loss_i = logsumexp_j zh_ij - zh_ii;   G_ij = (P_ij - [i == j]) / B,  P = row softmax of zh.
+ * One step, all on `stream`:
+ *   trs_softmax_stage                                Q (B, Dq) = user rows with a ones column at Dp, K (B, Dq) = S
+ *                                                    rows, cc_j = c_j / tau - L_j, item ids;
+ *   for row chunks [r0, r0 + R):  Z = Q[r0:] K^T     trs_gemm_f32(0, 1, R, B, Dp, lda = ldb = Dq);
+ *                                 trs_softmax_rows   row losses and G over Z in place;
+ *                                 dQ[r0:] = G K      trs_gemm_f32(0, 0, R, Dp, B, ldb = ldc = Dq);
+ *                                 dK (+)= G^T Q[r0:] trs_gemm_f32(1, 0, B, Dq, R, beta = 0 on the first chunk, else 1);
+ *   trs_softmax_grads                                gradient rows of the batch mean and loss_sum += sum_i loss_i.
+ * Dp = D rounded up to a power of two >= 16, Dq = Dp + 4.  Workspace (trs_softmax_workspace_bytes(B, D) bytes, 16-byte
+ * aligned), blocks of 4-byte words each starting at a multiple of 64 words: Q, K, dQ, dK (B * Dq each) | cc (B) |
+ * row losses (B) | item ids (B, int32).  Every entry point returns TRS_E_ARG (-1) for NULL tables / batch / ids /
+ * workspace, B < 1, D < 1, tau <= 0 or not finite, or a workspace smaller than trs_softmax_workspace_bytes(B, D).
+ * An id outside its table sets bit 0 of batch->err_flag_dev (its staged row is zero; no gradient row is applied to it). */
+int64_t trs_softmax_workspace_bytes(int64_t B, int32_t D);
+/* logq_dev: (n_items) fp32 log q of every item, or NULL = no log-Q correction.  Needs n_items < 2^31. */
+int trs_softmax_stage(int net, const trs_tables* tables, const trs_batch* batch, float tau, const float* logq_dev,
+                      void* workspace_dev, int64_t workspace_bytes, void* stream);
+/* Rows [row0, row0 + n_rows) of the logits: z_dev (n_rows, B) fp32 (z_bytes >= n_rows * B * 4) holds Z of those rows
+ * and receives G; writes loss_i to the workspace.  No atomics: bit-identical from run to run. */
+int trs_softmax_rows(float* z_dev, int64_t z_bytes, int64_t row0, int64_t n_rows, int64_t B, int32_t D, float tau,
+                     void* workspace_dev, int64_t workspace_bytes, void* stream);
+/* From dQ, dK of the workspace, per batch position j (fields f: 0 = user, 1 = positive item, 2+m = metadata column m):
+ *   grad_rows (2+M, B, D): f0 dQ_j / tau;  f1 dK_j / tau (+ FM: dc_j (S_j - item_pj));  f2+m dK_j / tau (+ FM:
+ *   dc_j (S_j - meta_m[m_jm])), with dc_j = sum_i G_ij / tau = dK_j[Dp] / tau;
+ *   grad_lin (2+M, B): f0 = 0 (the user-side 1-wide term has no gradient, its rows are still touched), f1 = dc_j,
+ *   f2+m = dc_j (FM) or 0 (Linear: no 1-wide metadata tables).
+ * The uncoalesced COO values of the tables' gradients, as trs_score_fwd_bwd stages them.  grad_rows / grad_lin both
+ * NULL: the loss sum only (evaluation).  loss_sum_dev += sum_i loss_i in one fixed order by one thread (no atomics). */
+int trs_softmax_grads(int net, const trs_tables* tables, const trs_batch* batch, float tau, const void* workspace_dev,
+                      int64_t workspace_bytes, float* grad_rows_dev, float* grad_lin_dev, float* loss_sum_dev,
+                      void* stream);
+
 /* ------------------------------------------------------------------------------------- MLP (a4, a7) */
 /* Activations of the MLP are kept for both scoring passes stacked: rows [0,B) = positive pass, rows [B,2B) =
  * negative pass ("passes" = 2).  BatchNorm1d statistics are per pass (the reference calls net.forward twice,

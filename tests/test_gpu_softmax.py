@@ -1,0 +1,350 @@
+# -*- coding: utf-8 -*-
+"""In-batch softmax loss of the Linear / FM scorers (fit(loss='softmax'), csrc/softmax.hip) on the MI355X against a
+float64 torch-autograd restatement of the contract written here: dense tables, the logits from the formulas of
+include/trs.h "in-batch softmax", .backward(), and for the coalescing optimisers oracle.optim's row rules."""
+import contextlib
+import io
+import re
+
+import numpy as np
+import pandas as pd
+import pytest
+import torch
+
+from conftest import rel_err
+from oracle import optim as ooptim
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+META_SIZES = (13, 7)
+
+
+def build_net(net_type, M, NU, NI, D, seed):
+    """A Linear / FM scorer with seeded random weights (biases / 1-wide terms too, so every term of the logit counts)."""
+    from torchrecsys_amd.collaborative.fm import FM
+    from torchrecsys_amd.collaborative.linear import Linear
+    cls = Linear if net_type == "linear" else FM
+    with contextlib.redirect_stdout(io.StringIO()):
+        net = cls(NU, NI, {f"m{m}": META_SIZES[m] for m in range(M)}, D, use_metadata=M > 0).to(DEV)
+    rs = np.random.RandomState(seed)
+    with torch.no_grad():
+        for p in net.table_params():
+            p.copy_(torch.from_numpy(rs.normal(0, 0.3 if p.shape[1] > 1 else 0.1, p.shape).astype(np.float32)))
+    return net
+
+
+def make_batch(B, NU, NI, M, seed, hits=True):
+    """(users, positives, positive metadata (B, M)) with forced repeated users and repeated items (accidental hits)."""
+    rs = np.random.RandomState(seed + 1000)
+    u, p = rs.randint(0, NU, B), rs.randint(0, NI, B)
+    if hits and B >= 7:
+        p[::7] = p[0]
+        p[3::11] = p[1]
+        u[1::4] = u[0]
+    item_meta = np.stack([rs.randint(0, META_SIZES[m], NI) for m in range(M)], 1) if M else np.zeros((NI, 0), int)
+    return u, p, item_meta[p]
+
+
+def oracle(net_type, W, M, u, p, pm, tau, logq):
+    """float64 autograd of the batch-mean in-batch softmax loss.  W: tables in table_params() order (numpy)."""
+    P = [torch.tensor(np.asarray(w, np.float64), requires_grad=True) for w in W]
+    U, I, UL, IL = P[:4]
+    MT = P[4:4 + M]
+    u_, p_ = torch.from_numpy(u).long(), torch.from_numpy(p).long()
+    pm_ = torch.from_numpy(np.asarray(pm)).long()
+    S = I[p_]
+    for m in range(M):
+        S = S + MT[m][pm_[:, m]]
+    if net_type == "linear":
+        c = IL[p_, 0]
+    else:
+        ML = P[4 + M:4 + 2 * M]
+        sq = (I[p_] ** 2).sum(1)
+        c = IL[p_, 0]
+        for m in range(M):
+            c = c + ML[m][pm_[:, m], 0]
+            sq = sq + (MT[m][pm_[:, m]] ** 2).sum(1)
+        c = c + 0.5 * ((S * S).sum(1) - sq)
+    z = U[u_] @ S.T + UL[u_, 0][:, None] + c[None, :]
+    zh = z / tau
+    if logq is not None:
+        zh = zh - torch.from_numpy(np.asarray(logq, np.float64))[p_][None, :]
+    B = len(u)
+    hit = (p_[:, None] == p_[None, :]) & ~torch.eye(B, dtype=torch.bool)
+    zh = zh.masked_fill(hit, float("-inf"))
+    loss = (torch.logsumexp(zh, 1) - zh.diagonal()).mean()
+    loss.backward()
+    grads = [q.grad.numpy() if q.grad is not None else np.zeros(q.shape) for q in P]
+    # the per-row constant cancels in the row softmax: its exact gradient is 0 (autograd leaves float64 rounding)
+    assert np.abs(grads[2]).max() < 1e-12
+    grads[2] = np.zeros_like(grads[2])
+    return float(loss.detach()), grads
+
+
+def touched(M, u, p, pm, n_tables):
+    rows = [np.unique(u), np.unique(p), np.unique(u), np.unique(p)]
+    rows += [np.unique(pm[:, m]) for m in range(M)]
+    rows += [np.unique(pm[:, m]) for m in range(M)][:n_tables - len(rows)]
+    return rows
+
+
+def device_ids(u, p, pm, dtype):
+    ids = {"user": torch.from_numpy(u).to(dtype).to(DEV), "pos": torch.from_numpy(p).to(dtype).to(DEV)}
+    ids["neg"] = ids["pos"]  # ignored by the softmax step
+    if pm.shape[1]:
+        ids["pos_meta"] = torch.from_numpy(np.ascontiguousarray(pm)).to(dtype).to(DEV)
+    return ids
+
+
+def trainer(net, opt, B, tau, logq, chunk=None):
+    from torchrecsys_amd.engine import SparseScorerTrainer
+    tr = SparseScorerTrainer(net, opt, B)
+    tr.softmax = (tau, None if logq is None else torch.from_numpy(np.asarray(logq, np.float32)).to(DEV))
+    tr.SOFTMAX_CHUNK_ROWS = chunk
+    return tr
+
+
+def random_logq(NI, seed):
+    rs = np.random.RandomState(seed + 7)
+    cnt = np.maximum(rs.poisson(3.0, NI), 1)
+    return np.log(cnt / cnt.sum()).astype(np.float32)
+
+
+# ------------------------------------------------------------------------------------------------ 1. one SGD step
+@pytest.mark.parametrize("net_type", ["linear", "fm"])
+@pytest.mark.parametrize("M", [0, 2])
+@pytest.mark.parametrize("B", [1, 7, 300, 1000])
+@pytest.mark.parametrize("tau", [1.0, 0.1])
+@pytest.mark.parametrize("logq_on", [False, True])
+def test_one_sgd_step_matches_autograd(net_type, M, B, tau, logq_on):
+    NU, NI, D, lr = 500, 400, (24 if M else 16), 0.5
+    seed = B * 7 + M
+    net = build_net(net_type, M, NU, NI, D, seed)
+    ps = net.table_params()
+    W0 = [p.detach().cpu().numpy().copy() for p in ps]
+    u, p, pm = make_batch(B, NU, NI, M, seed)
+    logq = random_logq(NI, seed) if logq_on else None
+    tr = trainer(net, torch.optim.SGD(net.parameters(), lr=lr), B, tau, logq)
+    loss = torch.zeros(1, device=DEV)
+    tr.softmax_step(device_ids(u, p, pm, torch.int64 if tau < 1 else torch.int32), loss)
+    tr.check_errors()
+    ref_loss, grads = oracle(net_type, W0, M, u, p, pm, tau, logq)
+    got = loss.item() / B
+    assert abs(got - ref_loss) <= 1e-5 * max(abs(ref_loss), 1e-6), (got, ref_loss)
+    rows = touched(M, u, p, pm, len(ps))
+    for k, (q, w0, g) in enumerate(zip(ps, W0, grads)):
+        new = q.detach().cpu().numpy()
+        assert rel_err(new, w0 - lr * g) <= 1e-5, k
+        if np.abs(g).max() > 0:  # the update itself, not only the table it lands on
+            assert rel_err(new - w0, -lr * g) <= 1e-3, k
+        keep = np.ones(w0.shape[0], bool)
+        keep[rows[k]] = False
+        assert np.array_equal(new[keep], w0[keep]), k  # rows no batch position touches: bit-identical
+    assert np.array_equal(ps[2].detach().cpu().numpy(), W0[2])  # the user-side 1-wide table
+
+
+# ------------------------------------------------------------------------------------------------ 2. chunking
+@pytest.mark.parametrize("net_type,M", [("fm", 2), ("linear", 0)])
+@pytest.mark.parametrize("B", [1000, 4096])
+def test_row_chunks_agree_and_repeat_bit_identically(net_type, M, B):
+    NU, NI, D = 3000, 2000, 64
+    net = build_net(net_type, M, NU, NI, D, 11)
+    u, p, pm = make_batch(B, NU, NI, M, 11)
+    ids = device_ids(u, p, pm, torch.int32)
+    logq = random_logq(NI, 3)
+    out = {}
+    for chunk in (None, 128, 128):
+        tr = trainer(net, torch.optim.SGD(net.parameters(), lr=0.0), B, 0.2, logq, chunk)
+        loss = torch.zeros(1, device=DEV)
+        tr.softmax_step(ids, loss)
+        tr.check_errors()
+        res = (loss.item(), tr._sm_rows[:(2 + M) * B * D].cpu().numpy(), tr._sm_lin[:(2 + M) * B].cpu().numpy())
+        out.setdefault(chunk, []).append(res)
+    if B > 128:
+        assert tr._sm.chunk_rows(B, 128) == 128 and tr._sm.chunk_rows(B) == B
+    one, (c1, c2) = out[None][0], out[128]
+    assert abs(c1[0] - one[0]) <= 1e-6 * abs(one[0])
+    assert rel_err(c1[1], one[1]) <= 1e-6 and rel_err(c1[2], one[2]) <= 1e-6
+    assert c1[0] == c2[0] and np.array_equal(c1[1], c2[1]) and np.array_equal(c1[2], c2[2])
+
+
+# ------------------------------------------------------------------------------------------------ 3. optimisers
+@pytest.mark.parametrize("net_type,M", [("fm", 2), ("linear", 2), ("fm", 0)])
+@pytest.mark.parametrize("kind", ["sparse_adam", "adagrad"])
+def test_three_steps_of_coalescing_optimisers(net_type, M, kind):
+    NU, NI, D, B, tau = 300, 200, 16, 256, 0.5
+    net = build_net(net_type, M, NU, NI, D, 5)
+    ps = net.table_params()
+    W = [p.detach().cpu().numpy().astype(np.float32).copy() for p in ps]
+    if kind == "sparse_adam":
+        opt = torch.optim.SparseAdam(list(net.parameters()), lr=0.01)
+        st = [[np.zeros_like(w), np.zeros_like(w)] for w in W]
+    else:
+        opt = torch.optim.Adagrad(net.parameters(), lr=0.05)
+        st = [[np.zeros_like(w)] for w in W]
+    logq = random_logq(NI, 1)
+    tr = trainer(net, opt, B, tau, logq)
+    for step in range(1, 4):
+        u, p, pm = make_batch(B, NU, NI, M, 100 + step)
+        loss = torch.zeros(1, device=DEV)
+        tr.softmax_step(device_ids(u, p, pm, torch.int32), loss)
+        tr.check_errors()
+        ref_loss, grads = oracle(net_type, W, M, u, p, pm, tau, logq)
+        assert abs(loss.item() / B - ref_loss) <= 1e-5 * abs(ref_loss)
+        for k, rows in enumerate(touched(M, u, p, pm, len(ps))):
+            g = grads[k].astype(np.float32)
+            if kind == "sparse_adam":
+                ooptim.sparse_adam_rows(W[k], g, rows, st[k][0], st[k][1], step, 0.01)
+            else:
+                ooptim.adagrad_rows(W[k], g, rows, st[k][0], step, 0.05)
+    for k, q in enumerate(ps):
+        assert rel_err(q.detach().cpu().numpy(), W[k]) <= 1e-5, k
+        s = opt.state[q]
+        names = ("exp_avg", "exp_avg_sq") if kind == "sparse_adam" else ("sum",)
+        for j, name in enumerate(names):
+            # the squared-gradient state doubles the fp32 gradient's relative error
+            tol = 1e-5 if name == "exp_avg" else 3e-5
+            assert rel_err(s[name].cpu().numpy(), st[k][j]) <= tol, (k, name)
+        assert int(s["step"]) == 3
+
+
+# ------------------------------------------------------------------------------------------------ 4. large shape
+def test_c2_sized_tables_one_step():
+    """c2 table shapes (1M users x 100K items, D = 64) at B = 16 384: the touched rows against a chunked float64 numpy
+    oracle, every untouched row bit-identical."""
+    NU, NI, D, B, tau, lr = 1_000_000, 100_000, 64, 16384, 0.1, 2.0
+    from torchrecsys_amd.collaborative.fm import FM
+    torch.manual_seed(0)
+    with contextlib.redirect_stdout(io.StringIO()):
+        net = FM(NU, NI, {}, D, use_metadata=False).to(DEV)
+    ps = net.table_params()
+    with torch.no_grad():
+        ps[2].normal_(0, 0.1)
+        ps[3].normal_(0, 0.1)
+    before = [q.detach().clone() for q in ps]
+    rs = np.random.RandomState(4)
+    u, p = rs.randint(0, NU, B), rs.randint(0, NI, B)
+    p[::97] = p[0]
+    logq = random_logq(NI, 4)
+    tr = trainer(net, torch.optim.SGD(net.parameters(), lr=lr), B, tau, logq)
+    loss = torch.zeros(1, device=DEV)
+    tr.softmax_step(device_ids(u, p, np.zeros((B, 0), int), torch.int32), loss)
+    tr.check_errors()
+    torch.cuda.synchronize()
+    # oracle: float64 numpy, 2048 logit rows at a time
+    Uu = before[0][torch.from_numpy(u).to(DEV)].double().cpu().numpy()
+    It = before[1][torch.from_numpy(p).to(DEV)].double().cpu().numpy()
+    c = before[3][torch.from_numpy(p).to(DEV), 0].double().cpu().numpy()  # FM, M = 0: c = linear_item
+    cc = c / tau - logq.astype(np.float64)[p]
+    dQ, dK, dc, tot = np.zeros_like(Uu), np.zeros_like(It), np.zeros(B), 0.0
+    for r0 in range(0, B, 2048):
+        r1 = min(B, r0 + 2048)
+        zh = (Uu[r0:r1] @ It.T) / tau + cc[None, :]
+        rr = np.arange(r0, r1)
+        zh[(p[rr][:, None] == p[None, :]) & (rr[:, None] != np.arange(B)[None, :])] = -np.inf
+        mx = zh.max(1, keepdims=True)
+        e = np.exp(zh - mx)
+        lse = mx[:, 0] + np.log(e.sum(1))
+        tot += float((lse - zh[np.arange(r1 - r0), rr]).sum())
+        G = e / e.sum(1, keepdims=True)
+        G[np.arange(r1 - r0), rr] -= 1.0
+        G /= B
+        dQ[r0:r1] = G @ It / tau
+        dK += G.T @ Uu[r0:r1] / tau
+        dc += G.sum(0) / tau
+    assert abs(loss.item() / B - tot / B) <= 1e-5 * (tot / B)
+    want = {0: (u, dQ), 1: (p, dK), 3: (p, dc[:, None])}
+    for k, (idx, g) in want.items():
+        w = before[k].double().cpu().numpy()
+        np.add.at(w, idx, -lr * g)
+        rows = np.unique(idx)
+        got = ps[k].detach()[torch.from_numpy(rows).to(DEV)].cpu().numpy()
+        assert rel_err(got, w[rows]) <= 1e-5, k
+        assert rel_err(got - before[k][torch.from_numpy(rows).to(DEV)].cpu().numpy(), w[rows] - before[k].double()
+                       .cpu().numpy()[rows]) <= 1e-3, k
+    for k, q in enumerate(ps):
+        keep = torch.ones(q.shape[0], dtype=torch.bool, device=DEV)
+        keep[torch.from_numpy(u if k in (0, 2) else p).to(DEV).long()] = False
+        assert torch.equal(q.detach()[keep], before[k][keep]), k
+    assert torch.equal(ps[2].detach(), before[2])
+
+
+# ------------------------------------------------------------------------------------------------ 5. end to end
+def _df(n_users=400, n_items=300, n=8000, seed=0):
+    rs = np.random.RandomState(seed)
+    return pd.DataFrame({"user_id": np.concatenate([np.arange(n_users), rs.randint(0, n_users, n - n_users)]),
+                         "item_id": np.concatenate([np.arange(n_items), rs.randint(0, n_items, n - n_items)]),
+                         "genre": np.concatenate([np.arange(n_items), rs.randint(0, n_items, n - n_items)]) % 5})
+
+
+def _losses(text, what):
+    return [float(x) for x in re.findall(r"%s: ([-\d.naif]+)" % what, text)]
+
+
+@pytest.mark.parametrize("net_type", ["linear", "fm"])
+def test_fit_softmax_front_doors_and_evaluate_loss(net_type):
+    from torchrecsys_amd.model import TorchRecSys
+    torch.manual_seed(0)
+    with contextlib.redirect_stdout(io.StringIO()):
+        m = TorchRecSys(_df(), "user_id", "item_id", n_factors=16, net_type=net_type, metadata_id_col=["genre"],
+                        dynamic_neg_sampling=True)
+    opt = torch.optim.Adagrad(m.parameters(), lr=0.05)
+    with contextlib.redirect_stdout(io.StringIO()) as out:
+        m.fit(opt, epochs=3, batch_size=256, loss="softmax", temperature=0.5, logq_correction=True)
+    tl = _losses(out.getvalue(), "Training Loss")
+    assert len(tl) == 3 and all(np.isfinite(tl)), out.getvalue()
+    with contextlib.redirect_stdout(io.StringIO()) as out:
+        m.evaluate(batch_size=500)
+    got = _losses(out.getvalue(), "Testing loss")[0]
+    # oracle: the test split in order (shuffle=False), one softmax per batch of 500, same tau and log-Q
+    td = m.data_processor.test_data
+    tr = m.data_processor.train_data
+    cnt = np.maximum(np.bincount(tr["pos_item_id"].numpy(), minlength=m.n_items), 1)
+    logq = np.log(cnt / tr["pos_item_id"].numel())
+    W = [q.detach().cpu().numpy() for q in m.net.table_params()]
+    u, p = td["user_id"].numpy(), td["pos_item_id"].numpy()
+    pm = td["pos_metadata_id"].numpy().reshape(len(u), -1)
+    vals = [oracle(net_type, W, 1, u[s:s + 500], p[s:s + 500], pm[s:s + 500], 0.5, logq)[0]
+            for s in range(0, len(u), 500)]
+    assert abs(got - np.mean(vals)) <= 1.5e-4, (got, np.mean(vals))
+    assert 0 < np.mean(vals) < 10
+
+
+def test_fit_softmax_from_tensors_device_rng():
+    from torchrecsys_amd.model import TorchRecSys
+    rs = np.random.RandomState(3)
+    users = torch.from_numpy(rs.randint(0, 500, 20000)).to(DEV)
+    items = torch.from_numpy(rs.randint(0, 800, 20000)).to(DEV)
+    torch.manual_seed(0)
+    with contextlib.redirect_stdout(io.StringIO()):
+        m = TorchRecSys.from_tensors(users, items, n_users=500, n_items=800, n_factors=32, net_type="fm",
+                                     dynamic_neg_sampling=True)
+    with contextlib.redirect_stdout(io.StringIO()) as out:
+        m.fit(torch.optim.SGD(m.parameters(), lr=20.0), epochs=3, batch_size=1024, loss="softmax")
+        m.evaluate(batch_size=1024)
+    tl = _losses(out.getvalue(), "Training Loss")
+    assert len(tl) == 3 and all(np.isfinite(tl)), out.getvalue()
+    assert np.isfinite(_losses(out.getvalue(), "Testing loss")[0])
+    assert np.isfinite(_losses(out.getvalue(), "Testing auc")[0])
+
+
+def test_softmax_training_recovers_planted_clusters():
+    """Planted clusters: 2 000 users and 1 000 items in 20 groups; every user interacts with 20 random items of its own
+    group.  After 8 epochs of softmax training (Linear, D = 32, SparseAdam) recall@10 on the test split must be at least
+    5x the untrained model's.  Observed on the MI355X: untrained 0.0096, trained 0.2972 (31x)."""
+    from torchrecsys_amd.model import TorchRecSys
+    rs = np.random.RandomState(0)
+    NU, NI, G = 2000, 1000, 20
+    users = np.repeat(np.arange(NU), 20)
+    items = np.array([rs.choice(np.arange(u % G, NI, G), 20, replace=False) for u in range(NU)]).reshape(-1)
+    df = pd.DataFrame({"user_id": users, "item_id": items})
+    torch.manual_seed(0)
+    with contextlib.redirect_stdout(io.StringIO()):
+        m = TorchRecSys(df, "user_id", "item_id", n_factors=32, net_type="linear", dynamic_neg_sampling=True)
+        before = m.evaluate_ranking(k=10)["recall@10"]
+        m.fit(torch.optim.SparseAdam(list(m.parameters()), lr=0.02), epochs=8, batch_size=512, loss="softmax",
+              temperature=0.2)
+        after = m.evaluate_ranking(k=10)["recall@10"]
+    print(f"recall@10 untrained {before:.4f} trained {after:.4f}")
+    assert after >= 5 * before and after > 0.1, (before, after)

@@ -163,6 +163,10 @@ PROTOTYPES = {
                                     _vp, _vp, _vp, _i64, _vp]),
     "trs_mask_seen": (C.c_int, [_vp, _i64, _i64, _vp, C.POINTER(TrsCsr), _vp]),
     "trs_rank_metrics": (C.c_int, [_vp, _i64, _i32, _vp, C.POINTER(TrsCsr), _vp, _vp]),
+    "trs_softmax_workspace_bytes": (C.c_int64, [_i64, _i32]),
+    "trs_softmax_stage": (C.c_int, [C.c_int, _T, _Bp, _f, _vp, _vp, _i64, _vp]),
+    "trs_softmax_rows": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _i32, _f, _vp, _i64, _vp]),
+    "trs_softmax_grads": (C.c_int, [C.c_int, _T, _Bp, _f, _vp, _i64, _vp, _vp, _vp, _vp]),
     "trs_mlp_gather_concat": (C.c_int, [_T, _Bp, _i32, _vp, _vp, _i64, _vp]),
     "trs_mlp_gather_gemm1_fwd": (C.c_int, [_T, _Bp, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64,
                                            _vp]),

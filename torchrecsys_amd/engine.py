@@ -500,6 +500,46 @@ class SparseScorerTrainer:
             self._per_table(ids, gr, gl, self._set_sparse_grad)
             self.opt.step()
 
+    # in-batch softmax (fit(loss='softmax')): (temperature, (n_items,) fp32 log q or None), set by fit()
+    softmax = None
+    SOFTMAX_CHUNK_ROWS = None  # logit rows per chunk (a multiple of 128); None: ops.InBatchSoftmax.CHUNK_BYTES decides
+
+    def softmax_step(self, ids, loss_slot):
+        """One step of the in-batch softmax loss on the batch's (user, positive, metadata) rows: every other positive of
+        the batch is a negative (ids["neg"] is ignored).  loss_slot receives the SUM of the row losses (caller divides
+        by B).  The gradient rows go through the same per-table paths as step()'s."""
+        tau, logq = self.softmax
+        B, D, M = ids["user"].shape[0], self.D, self.M
+        net = self.net
+        if getattr(self, "_sm", None) is None:
+            self._sm = ops.InBatchSoftmax(self.cap, D, self.dev)
+            self._sm_rows = torch.empty((2 + M) * self.cap * D, dtype=torch.float32, device=self.dev)
+            self._sm_lin = torch.empty((2 + M) * self.cap, dtype=torch.float32, device=self.dev)
+        gr = self._sm_rows[:(2 + M) * B * D].view(2 + M, B, D)
+        gl = self._sm_lin[:(2 + M) * B].view(2 + M, B)
+        T = net.tables()
+        Bt, keep = ops.make_batch(ids["user"], ids["pos"], None, ids.get("pos_meta"), None, self.err)
+        self._sm(net.NET, T, Bt, tau, logq, loss_slot, gr, gl, chunk_rows=self.SOFTMAX_CHUNK_ROWS)
+        if self.kind == "sgd":
+            fn = lambda p, idx, vals, ld: ops.rows_scatter_add(p.data, idx, vals, -_group_of(self.opt, p)["lr"], ld=ld)
+        elif self.kind in ("sparse_adam", "adagrad"):
+            fn = lambda p, idx, vals, ld: apply_rows(self.kind, self.opt, p, self.row_state[id(p)], idx, vals, ld)
+        else:
+            self.opt.zero_grad()
+            fn = self._set_sparse_grad
+        ps = self.params
+        fn(ps[0], ids["user"], gr[0], D)
+        fn(ps[1], ids["pos"], gr[1], D)
+        fn(ps[2], ids["user"], gl[0].reshape(B, 1), 1)
+        fn(ps[3], ids["pos"], gl[1].reshape(B, 1), 1)
+        for m in range(M):
+            midx = ids["pos_meta"][:, m].contiguous()
+            fn(ps[4 + m], midx, gr[2 + m], D)
+            if net_has_meta_lin(net):
+                fn(ps[4 + M + m], midx, gl[2 + m].reshape(B, 1), 1)
+        if self.kind not in ("sgd", "sparse_adam", "adagrad"):
+            self.opt.step()
+
     @staticmethod
     def _set_sparse_grad(p, idx, vals, ld):
         g = torch.sparse_coo_tensor(idx.reshape(1, -1).long(), vals, size=p.shape)

@@ -332,7 +332,7 @@ class TorchRecSys(torch.nn.Module):
 
     @_host_side
     def fit(self, optimizer, epochs=10, batch_size=512, profile_epochs: int = 0, sync_tables_every: int = 1,
-            sync_bn: bool = False, loss: str = 'hinge'):
+            sync_bn: bool = False, loss: str = 'hinge', temperature: float = 1.0, logq_correction: bool = False):
         """Fits the model (reference model.py:203-288).  Per step: [shuffle slice + negative sampling] -> fused
         gather + scoring + hinge + backward -> sparse-row optimiser update; the loss stays on the device and is
         read back once per epoch (the reference syncs every step, model.py:200).
@@ -348,17 +348,45 @@ class TorchRecSys(torch.nn.Module):
           * MLP: the dense gradients are all-reduced every step, layer by layer while the backward is still running;
             sync_bn=True takes the train-mode BatchNorm statistics over the GLOBAL batch (two all-reduces of 2*H floats
             per layer and pass), so N ranks with batch B reproduce one process with batch N*B on the dense path.
-        The printed loss is the mean over ranks."""
+        The printed loss is the mean over ranks.
+
+        loss='softmax' (Linear and FM only): in-batch softmax over the batch's positives (Yi et al., RecSys 2019).  Row i
+        scores its user against the positive item of every row j, z_ij / temperature - L_j, where L_j = log q of item
+        p_j when logq_correction (q = the item's share of this rank's train rows, at least one count) and 0 otherwise;
+        another row with the same item as row i is masked out; the row loss is logsumexp_j - the diagonal term, averaged
+        over the batch.  The batches (and the negatives the loader draws, which the loss ignores) are those of a hinge
+        run.  Under torch.distributed every rank's negatives are the positives of its OWN batch: nothing new crosses
+        ranks.  evaluate() then reports this loss per test batch (AUC stays pairwise).  Not with neg_sampling options."""
+        # loss: 'hinge' = the reference's only loss (helper/loss.py:5-9, model.py:282); 'bpr' = -log sigmoid(pos - neg),
+        # the alternative BASELINE.json's north_star names (evaluate() then reports that loss too); 'softmax' = the
+        # in-batch softmax (engine.SparseScorerTrainer.softmax_step; not a pair loss, so not in LOSS_ID)
+        from ._lib import LOSS_ID
+        if loss not in LOSS_ID and loss != 'softmax':
+            raise ValueError(f"loss must be one of {sorted(list(LOSS_ID) + ['softmax'])}")
+        if loss == 'softmax':
+            if self.net_type not in ('linear', 'fm'):
+                raise ValueError("loss='softmax' trains the Linear and FM scorers (net_type 'linear' or 'fm'), "
+                                 f"not net_type={self.net_type!r}")
+            if getattr(self, 'neg_sampling', None):
+                raise ValueError("loss='softmax' takes its negatives from the batch: it does not combine with "
+                                 "neg_sampling options (k > 1 would repeat positives inside a batch)")
+            try:
+                tau = float(temperature)
+            except (TypeError, ValueError):
+                raise ValueError(f"temperature must be a positive finite number, got {temperature!r}") from None
+            if not (math.isfinite(tau) and tau > 0):
+                raise ValueError(f"temperature must be a positive finite number, got {temperature!r}")
+        elif temperature != 1.0 or logq_correction:
+            raise ValueError("temperature and logq_correction apply to loss='softmax' only")
         if self.net_type == 'mlp':
             self.net.compute.sync_bn = bool(sync_bn)
-        # loss: 'hinge' = the reference's only loss (helper/loss.py:5-9, model.py:282); 'bpr' = -log sigmoid(pos - neg),
-        # the alternative BASELINE.json's north_star names (evaluate() then reports that loss too)
-        from ._lib import LOSS_ID
-        if loss not in LOSS_ID:
-            raise ValueError(f"loss must be one of {sorted(LOSS_ID)}")
-        self.loss = loss
         runner = self.make_runner(optimizer, batch_size)
-        runner.trainer.loss_id = LOSS_ID[loss]
+        if loss == 'softmax':
+            self._softmax = (tau, self._logq(runner.data) if logq_correction else None)
+            runner.trainer.softmax = self._softmax
+        else:
+            runner.trainer.loss_id = LOSS_ID[loss]
+        self.loss = loss
         for epoch in range(epochs):
             self.net = self.net.train()
             prof = None
@@ -387,6 +415,13 @@ class TorchRecSys(torch.nn.Module):
         if tdist.world_info()[1] > 1 and self.dp_partition == 'user':
             for t in self._user_tables():  # every replica gets the owners' user rows
                 tdist.gather_owned_rows_(t.data)
+
+    def _logq(self, data):
+        """(n_items,) fp32 log q on the device: q = max(count of the item in `data`'s rows, 1) / number of rows."""
+        dev = _device()
+        pos = data['pos_item_id'].to(dev).long()
+        counts = torch.bincount(pos, minlength=self.n_items).clamp_min(1).double()
+        return torch.log(counts / max(pos.numel(), 1)).float().contiguous()
 
     def _user_tables(self):
         """Tables indexed by user id (Linear / FM: the embedding and the 1-wide term; MLP: the embedding)."""
@@ -432,8 +467,14 @@ class TorchRecSys(torch.nn.Module):
             sample_seed = _mix64(self.seed, 0xE7A1)
         # Linear / FM score triples independently of their batch: several batches per launch (ids, scores, per-batch
         # reductions, one id-range check per group); the MLP's activations are per batch
-        group = 64 if hasattr(self.net, 'table_params') else 1
+        # fit(loss='softmax'): every test batch is its own softmax, one batch at a time
+        softmax = getattr(self, "loss", "hinge") == "softmax" and hasattr(self.net, 'table_params')
+        group = 64 if hasattr(self.net, 'table_params') and not softmax else 1
         group = max(1, min(group, (1 << 22) // max(batch_size, 1)))
+        if softmax:
+            sm_loss = torch.zeros(nb, dtype=torch.float32, device=dev)
+            sm = ops.InBatchSoftmax(min(batch_size, n_test), self.n_factors, dev)
+            err = torch.zeros(1, dtype=torch.int32, device=dev)
         for b0 in range(0, nb, group):
             b1 = min(b0 + group, nb)
             s, e = b0 * batch_size, min(b1 * batch_size, n_test)
@@ -445,7 +486,13 @@ class TorchRecSys(torch.nn.Module):
             pos, neg = self.net.score_ids(ids)
             from ._lib import LOSS_ID
             ops.hinge_auc_batches(pos, neg, batch_size, loss_sums[b0:b1], auc_counts[b0:b1],
-                                  loss=LOSS_ID[getattr(self, "loss", "hinge")])
+                                  loss=LOSS_ID.get(getattr(self, "loss", "hinge"), 0))
+            if softmax:
+                Bt, keep = ops.make_batch(ids['user'], ids['pos'], None, ids.get('pos_meta'), None, err)
+                sm(self.net.NET, self.net.tables(), Bt, self._softmax[0], self._softmax[1], sm_loss[b0:b0 + 1])
+        if softmax:
+            check_err_flag(err, "evaluate")
+            loss_sums = sm_loss
         ls, ac = loss_sums.cpu().numpy(), auc_counts.cpu().numpy()
         sizes = [min((b + 1) * batch_size, n_test) - b * batch_size for b in range(nb)]
         results = {}
@@ -782,6 +829,8 @@ class FitRunner:
         if os.environ.get("TRS_META_FAST", "1") == "0" and has_meta:
             kind = None  # tuning / fall-back knob: metadata scorers on the generic staged path
         fast = (kind == "sgd" and not has_meta) or (kind is not None and self.trainer.wants_presort(B))
+        softmax = getattr(self.trainer, "softmax", None) is not None
+        fast = fast and not softmax  # the in-batch softmax runs on the generic loop below
         if fast and m.rng == 'reference':
             fast = self.ep['user'].dtype == torch.int32
         ops.stamp("run_steps:setup")
@@ -829,7 +878,10 @@ class FitRunner:
                                         self.sample_seed, s, st['item_meta'], out, sampler=self.sampler)
                 if e - s == B:
                     self.prep_out = ids
-            self.trainer.step(ids, self.loss_sums[b:b + 1])
+            if softmax:
+                self.trainer.softmax_step(ids, self.loss_sums[b:b + 1])
+            else:
+                self.trainer.step(ids, self.loss_sums[b:b + 1])
             self.next_batch += 1
             done += 1
         return done

@@ -607,6 +607,63 @@ def rank_metrics(ids, users, rel):
                                        _stream()), "trs_rank_metrics")
     return out
 
+# ------------------------------------------------------------------------------------------------- in-batch softmax
+class InBatchSoftmax:
+    """Workspace and logit chunk of the in-batch softmax loss (csrc/softmax.hip, include/trs.h "in-batch softmax") for
+    batches of up to `capacity` rows of a D-factor scorer.  One call = stage, then per chunk of R rows Z = Q K^T, the
+    rows kernel, dQ = G K and dK += G^T Q on trs_gemm_f32, then the gradient rows and the loss sum."""
+
+    CHUNK_BYTES = 256 << 20  # largest logit chunk R * B * 4 bytes (R a multiple of 128)
+
+    def __init__(self, capacity, D, device):
+        self.cap, self.D, self.dev = int(capacity), int(D), device
+        self.Dp = 16
+        while self.Dp < self.D:
+            self.Dp *= 2
+        self.Dq = self.Dp + 4
+        self.ws_bytes = _lib.load().trs_softmax_workspace_bytes(self.cap, self.D)
+        self.ws = torch.empty(self.ws_bytes // 4, dtype=torch.float32, device=device)
+        self.z = None
+
+    def chunk_rows(self, B, chunk_rows=None):
+        """Rows per logit chunk: `chunk_rows` if given, else the most multiple-of-128 rows within CHUNK_BYTES."""
+        R = chunk_rows or max(128, self.CHUNK_BYTES // (4 * B) // 128 * 128)
+        return min(int(R), B)
+
+    def _mats(self, B):
+        """Q, K, dQ, dK (B, Dq) views of the workspace for a batch of B rows (layout of include/trs.h)."""
+        mat = (B * self.Dq + 63) // 64 * 64
+        return [self.ws[k * mat:k * mat + B * self.Dq].view(B, self.Dq) for k in range(4)]
+
+    def __call__(self, net, T, Bt, tau, logq, loss_sum, grad_rows=None, grad_lin=None, chunk_rows=None):
+        """loss_sum (1-element fp32) += sum of the batch's row losses; grad_rows (2+M, B, D) / grad_lin (2+M, B) receive
+        the gradient rows of the batch mean (both None: the loss only)."""
+        lib = _lib.load()
+        B = int(Bt.B)
+        if B < 1 or B > self.cap:
+            raise ValueError(f"in-batch softmax: batch of {B} rows outside 1..{self.cap}")
+        s = _stream()
+        check(lib.trs_softmax_stage(NET_ID[net], C.byref(T), C.byref(Bt), float(tau), ptr(logq), ptr(self.ws),
+                                    self.ws_bytes, s), "trs_softmax_stage")
+        Q, K, dQ, dK = self._mats(B)
+        Dp = self.Dp
+        R = self.chunk_rows(B, chunk_rows)
+        if self.z is None or self.z.numel() < R * B:
+            self.z = torch.empty(R * B, dtype=torch.float32, device=self.dev)
+        want = grad_rows is not None
+        for r0 in range(0, B, R):
+            n = min(R, B - r0)
+            Z = self.z[:n * B].view(n, B)
+            gemm(0, 1, Q[r0:r0 + n, :Dp], K[:, :Dp], out=Z)
+            check(lib.trs_softmax_rows(ptr(Z), Z.numel() * 4, r0, n, B, self.D, float(tau), ptr(self.ws), self.ws_bytes,
+                                       s), "trs_softmax_rows")
+            if want:
+                gemm(0, 0, Z, K[:, :Dp], out=dQ[r0:r0 + n, :Dp])
+                gemm(1, 0, Z, Q[r0:r0 + n], out=dK, beta=0.0 if r0 == 0 else 1.0)
+        check(lib.trs_softmax_grads(NET_ID[net], C.byref(T), C.byref(Bt), float(tau), ptr(self.ws), self.ws_bytes,
+                                    ptr(grad_rows), ptr(grad_lin), ptr(loss_sum), s), "trs_softmax_grads")
+
+
 # ------------------------------------------------------------------------------------------------- MLP kernels
 def mlp_gather_concat(T, Bt, passes, x=None, x16=None):
     """x: fp32 (rows, (2+M)D) and/or x16: the same image in bfloat16 (same row stride in elements)."""
