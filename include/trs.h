@@ -93,7 +93,8 @@ const char* trs_last_error(void);
  *      points no longer use their temp buffers (no vendor sort).
  *   5: trs_epoch_flags_ordered (flagged-first batches), trs_train_args.n_flagged_dev.
  *   6: batched top-k retrieval: trs_csr, trs_item_fold(_bytes), trs_retrieve_topk, trs_retrieve_workspace_bytes,
- *      trs_mask_seen, trs_rank_metrics. */
+ *      trs_mask_seen, trs_rank_metrics.  (Entry points added since without touching an existing signature or struct:
+ *      the in-batch softmax group, trs_batch_prepare_mined.) */
 #define TRS_ABI_VERSION 6
 #define TRS_SYNC_WORDS 288
 int trs_abi_version(void);
@@ -156,6 +157,36 @@ int trs_batch_prepare(const int32_t* stream_user_dev, const int32_t* stream_item
                       const int32_t* item_meta_dev, int32_t M, int32_t* user_out, int32_t* pos_out,
                       int32_t* neg_out, int32_t* pos_meta_out, int32_t* neg_meta_out, const trs_sampler* sampler,
                       void* stream);
+
+/* trs_batch_prepare with score-aware hard-negative mining (dynamic negative sampling, Zhang et al., SIGIR 2013; the
+ * reference has no such sampler): per triple, `candidates` = K negatives are drawn, scored under the tables AS THEY ARE
+ * when the launch runs, and one of the `top` = m highest-scoring ones becomes the triple's negative.  One launch.
+ * For epoch position q (user u, positive p as trs_batch_prepare derives them), sampler seed s = sample_seed and
+ * ctr = sample_offset + t, the Philox counter trs_batch_prepare uses for that position:
+ *   candidates  c_j = the sampler's draw (popularity / seen rejection / max_tries of `sampler` unchanged; every c_j
+ *               differs from p) under the seed s_j = (s + j * 0xD1B54A32D192ED03) mod 2^64, j = 0 .. K-1; the retry keys
+ *               inside a draw are s_j + t * 0x9E3779B97F4A7C15, and all (j, t) offsets for j <= 65, t <= 64 are distinct
+ *               mod 2^64.  c_0 is exactly the negative trs_batch_prepare writes.  Candidates may repeat.
+ *   scores      z_j = the scorer's negative-pass value of (u, c_j, metadata of c_j through item_meta): net =
+ *               TRS_NET_LINEAR the score, TRS_NET_FM the value BEFORE the sigmoid (strict where fp32 sigmoid saturates,
+ *               as retrieval ranks) — the arithmetic of trs_score_forward, bit for bit.
+ *   choice      candidates ordered by (z_j descending, j ascending; NaN first as torch.sort, -0.0 = +0.0); the negative
+ *               is the candidate of rank r, r = 0 if m == 1, else r = mulhi64(x, m) with x = words (y << 32 | x) of
+ *               Philox(ctr, s_K) (uniform over the m best: the usual guard against false negatives).
+ * Outputs as trs_batch_prepare (user, pos, the mined neg, both metadata rows when M > 0) and, when chosen_out (B) int32
+ * is given, the chosen candidate's index j.  candidates == 1 reproduces trs_batch_prepare bit for bit.  k_neg composes
+ * unchanged (positions, counters and the shuffle are those of the unmined epoch).  An id of the stream outside its
+ * table is never used as a row index here (the scorer of the step reports it).
+ * TRS_E_ARG, nothing launched: tables NULL; net not TRS_NET_LINEAR / TRS_NET_FM; candidates outside 1..64; top outside
+ * 1..candidates; neg_static given; M != tables->M, or M > 0 without item_meta or the metadata outputs; a D the scorer
+ * kernels do not take; NULL tables' members; n_items > tables->n_items. */
+int trs_batch_prepare_mined(const int32_t* stream_user_dev, const int32_t* stream_item_dev,
+                            const int32_t* neg_static_dev, int64_t N, uint64_t shuffle_key, int64_t t0, int64_t B,
+                            int64_t n_items, uint64_t sample_seed, uint64_t sample_offset,
+                            const int32_t* item_meta_dev, int32_t M, int32_t* user_out, int32_t* pos_out,
+                            int32_t* neg_out, int32_t* pos_meta_out, int32_t* neg_meta_out, const trs_sampler* sampler,
+                            int net, const trs_tables* tables, int32_t candidates, int32_t top, int32_t* chosen_out,
+                            void* stream);
 
 /* ------------------------------------------------------------------ scorers: forward only (a2, a3, a6) */
 /* Fused positive+negative scoring pass; the user row is gathered once for both passes.

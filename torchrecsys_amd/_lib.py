@@ -124,6 +124,9 @@ PROTOTYPES = {
     "trs_sample_neg": (C.c_int, [_vp, C.c_int, _i64, _i64, _u64, _u64, _vp, _vp]),
     "trs_batch_prepare": (C.c_int, [_vp, _vp, _vp, _i64, _u64, _i64, _i64, _i64, _u64, _u64, _vp, _i32,
                                     _vp, _vp, _vp, _vp, _vp, C.POINTER(TrsSampler), _vp]),
+    "trs_batch_prepare_mined": (C.c_int, [_vp, _vp, _vp, _i64, _u64, _i64, _i64, _i64, _u64, _u64, _vp, _i32,
+                                          _vp, _vp, _vp, _vp, _vp, C.POINTER(TrsSampler), C.c_int, _T, _i32, _i32, _vp,
+                                          _vp]),
     "trs_score_forward": (C.c_int, [C.c_int, _T, _Bp, _vp, _vp, _vp]),
     "trs_score_fwd_bwd": (C.c_int, [C.c_int, _T, _Bp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "trs_score_backward": (C.c_int, [C.c_int, _T, _Bp, _vp, _vp, _vp, _vp, _vp]),

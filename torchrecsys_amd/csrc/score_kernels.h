@@ -128,14 +128,18 @@ __device__ __forceinline__ float sigmoidf_(float z) { return 1.0f / (1.0f + expf
 // One pass (positive or negative) of a scorer for one triple, given the user row.
 //   Ssum  : FM: sum over fields of the rows (incl. user);  Linear: item + sum of metadata rows
 //   score : the pass's score (FM: sigmoid(z))
-template <int NET, int VEC, int G, int K>
-__device__ __forceinline__ float pass_forward(const trs_tables& T, const RowReg<VEC, K>& u, float u_lin,
-                                              int64_t item, const void* meta, int idx_bytes, int64_t t, bool valid,
-                                              int lig, RowReg<VEC, K>& it, RowReg<VEC, K>& Ssum, float& it_lin,
-                                              float& lin_sum, bool& ok) {
+// pass_forward_z hands back the value BEFORE the FM sigmoid (Linear: the score itself) — the order retrieval and the
+// hard-negative miner (mine.hip) rank by, strict where the fp32 sigmoid saturates; pass_forward = sigmoid of exactly
+// that value, so a score chosen by z is bit-identical to the one a later scoring pass computes.  FULL: the lane group
+// covers the row exactly (row_load).
+template <int NET, int VEC, int G, int K, bool FULL = false>
+__device__ __forceinline__ float pass_forward_z(const trs_tables& T, const RowReg<VEC, K>& u, float u_lin,
+                                                int64_t item, const void* meta, int idx_bytes, int64_t t, bool valid,
+                                                int lig, RowReg<VEC, K>& it, RowReg<VEC, K>& Ssum, float& it_lin,
+                                                float& lin_sum, bool& ok) {
   constexpr int N = K * VEC;
   const int D = T.D;
-  row_load<VEC, G, K>(it, T.item, item, D, lig);
+  row_load<VEC, G, K, FULL>(it, T.item, item, D, lig);
   it_lin = T.item_lin ? T.item_lin[item] : 0.f;
   float sq[N];  // FM: sum over fields of v^2
   if (NET == TRS_NET_FM) {
@@ -157,7 +161,7 @@ __device__ __forceinline__ float pass_forward(const trs_tables& T, const RowReg<
       mid = 0;
     }
     RowReg<VEC, K> mr;
-    row_load<VEC, G, K>(mr, T.meta[m], mid, D, lig);
+    row_load<VEC, G, K, FULL>(mr, T.meta[m], mid, D, lig);
 #pragma unroll
     for (int n = 0; n < N; ++n) {
       Ssum.v[n] += mr.v[n];
@@ -174,8 +178,18 @@ __device__ __forceinline__ float pass_forward(const trs_tables& T, const RowReg<
     for (int n = 0; n < N; ++n) part += u.v[n] * Ssum.v[n];
   }
   const float red = trs_group_sum<G>(part);
-  if (NET == TRS_NET_FM) return sigmoidf_(lin_sum + 0.5f * red);
+  if (NET == TRS_NET_FM) return lin_sum + 0.5f * red;
   return (red + u_lin) + it_lin;  // (dot + user_bias) + item_bias, linear.py:78
+}
+
+template <int NET, int VEC, int G, int K>
+__device__ __forceinline__ float pass_forward(const trs_tables& T, const RowReg<VEC, K>& u, float u_lin,
+                                              int64_t item, const void* meta, int idx_bytes, int64_t t, bool valid,
+                                              int lig, RowReg<VEC, K>& it, RowReg<VEC, K>& Ssum, float& it_lin,
+                                              float& lin_sum, bool& ok) {
+  const float z = pass_forward_z<NET, VEC, G, K>(T, u, u_lin, item, meta, idx_bytes, t, valid, lig, it, Ssum, it_lin,
+                                                 lin_sum, ok);
+  return NET == TRS_NET_FM ? sigmoidf_(z) : z;
 }
 
 // MODE 0: scores only.  MODE 1: scores + hinge/upstream grads -> staged per-triple gradient rows.

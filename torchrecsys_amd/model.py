@@ -61,6 +61,31 @@ def _mix64(a, b):
     return x or 1
 
 
+def _check_mining_options(ns, net_type):
+    """The score-aware mining keys of neg_sampling (fit() docstring): ValueError naming the offending key."""
+    if ns.get("mine") is None:
+        for key in ("candidates", "top"):
+            if key in ns:
+                raise ValueError(f"neg_sampling[{key!r}] needs neg_sampling['mine'] (= 'hardest')")
+        if "mine" in ns:
+            raise ValueError("neg_sampling['mine'] must be 'hardest'")
+        return
+    if ns["mine"] != 'hardest':
+        raise ValueError(f"neg_sampling['mine'] must be 'hardest', got {ns['mine']!r}")
+    if net_type not in ('linear', 'fm'):
+        raise ValueError("neg_sampling['mine'] scores every candidate with the Linear / FM kernels; a candidate's score "
+                         f"under net_type={net_type!r} needs the whole network (out of scope)")
+
+    def integer(key, default, lo, hi):
+        v = ns.get(key, default)
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError(f"neg_sampling[{key!r}] must be an integer in {lo}..{hi}, got {v!r}")
+        return int(v)
+
+    K = integer("candidates", 8, 1, 64)
+    integer("top", 1, 1, K)
+
+
 class TorchRecSys(torch.nn.Module):
 
     @_host_side
@@ -125,10 +150,12 @@ class TorchRecSys(torch.nn.Module):
         assert rng in ('reference', 'device'), 'rng must be "reference" or "device"'
         ns = getattr(self, "neg_sampling", None)
         if ns:
-            unknown = set(ns) - {"reject_seen", "popularity", "k", "max_tries"}
+            unknown = set(ns) - {"reject_seen", "popularity", "k", "max_tries", "mine", "candidates", "top"}
             if unknown or rng != 'device' or not dynamic_neg_sampling:
-                raise ValueError("neg_sampling takes reject_seen / popularity / k / max_tries and needs rng='device' with "
-                                 "dynamic_neg_sampling=True (the reference-RNG mode replays the reference's sampler)")
+                raise ValueError("neg_sampling takes reject_seen / popularity / k / max_tries / mine / candidates / top "
+                                 "and needs rng='device' with dynamic_neg_sampling=True (the reference-RNG mode replays "
+                                 "the reference's sampler)")
+            _check_mining_options(ns, net_type)
         self.path = path
         self.dynamic_neg_sampling = dynamic_neg_sampling
         self.use_amp = use_amp
@@ -289,13 +316,16 @@ class TorchRecSys(torch.nn.Module):
             st = self._device_stream('train')
             seen = self._seen_csr() if ns.get("reject_seen") else None
             self._dev_cache['sampler'] = ops.Sampler(k=ns.get("k", 1), popularity=ns.get("popularity", False), seen=seen,
-                                                     stream_item=st['pos'], max_tries=ns.get("max_tries", 8))
+                                                     stream_item=st['pos'], max_tries=ns.get("max_tries", 8),
+                                                     mine=ns.get("mine"), candidates=ns.get("candidates", 8),
+                                                     top=ns.get("top", 1))
         return self._dev_cache['sampler']
 
     def _eval_sampler(self):
-        """evaluate(): the same candidate rules (reject_seen / popularity), every test row once."""
+        """evaluate(): the same candidate rules (reject_seen / popularity), every test row once, never mined (candidate 0
+        of the same rules): loss and AUC stay comparable between mined and unmined runs."""
         sm = self._sampler()
-        if sm is None or sm.k == 1:
+        if sm is None or (sm.k == 1 and sm.mine is None):
             return sm
         if 'eval_sampler' not in self._dev_cache:
             ns = self.neg_sampling
@@ -356,7 +386,17 @@ class TorchRecSys(torch.nn.Module):
         another row with the same item as row i is masked out; the row loss is logsumexp_j - the diagonal term, averaged
         over the batch.  The batches (and the negatives the loader draws, which the loss ignores) are those of a hinge
         run.  Under torch.distributed every rank's negatives are the positives of its OWN batch: nothing new crosses
-        ranks.  evaluate() then reports this loss per test batch (AUC stays pairwise).  Not with neg_sampling options."""
+        ranks.  evaluate() then reports this loss per test batch (AUC stays pairwise).  Not with neg_sampling options.
+
+        neg_sampling={'mine': 'hardest', 'candidates': K, 'top': m} (constructor / from_tensors; Linear and FM, device RNG
+        with dynamic negatives): score-aware hard-negative mining.  Per triple the sampler draws K candidates
+        (1..64, default 8) under its usual rules (popularity / reject_seen / max_tries; candidate 0 is the negative an
+        unmined run draws), one launch scores them under the current tables, and the step trains on one drawn uniformly
+        among the m highest-scoring ones (1..K, default 1 = the hardest).  Hinge and BPR, every optimiser, metadata
+        scorers and `k` visits per positive work unchanged; the steps run one by one (a mining launch, then the step),
+        not on the slice-ahead presorted path, because the negative of step t depends on the tables after step t - 1.
+        evaluate() keeps drawing unmined negatives, so its loss and AUC compare across mined and unmined runs.  Under
+        torch.distributed every rank mines on its own replica with its own seed."""
         # loss: 'hinge' = the reference's only loss (helper/loss.py:5-9, model.py:282); 'bpr' = -log sigmoid(pos - neg),
         # the alternative BASELINE.json's north_star names (evaluate() then reports that loss too); 'softmax' = the
         # in-batch softmax (engine.SparseScorerTrainer.softmax_step; not a pair loss, so not in LOSS_ID)
@@ -831,6 +871,10 @@ class FitRunner:
         fast = (kind == "sgd" and not has_meta) or (kind is not None and self.trainer.wants_presort(B))
         softmax = getattr(self.trainer, "softmax", None) is not None
         fast = fast and not softmax  # the in-batch softmax runs on the generic loop below
+        # score-aware mining: the negative of step t depends on the tables after step t - 1, so neither the slice-ahead
+        # presort nor the C step loop applies — the per-step loop below, one mining launch in front of every step
+        mining = getattr(self.sampler, "mine", None) is not None
+        fast = fast and not mining
         if fast and m.rng == 'reference':
             fast = self.ep['user'].dtype == torch.int32
         ops.stamp("run_steps:setup")
@@ -874,8 +918,13 @@ class FitRunner:
             else:
                 st = self.st
                 out = self.prep_out if (self.prep_out is not None and e - s == B) else None
-                ids = ops.batch_prepare(st['user'], st['pos'], st['neg'], self.shuffle_key, s, e - s, m.n_items,
-                                        self.sample_seed, s, st['item_meta'], out, sampler=self.sampler)
+                if mining:  # K candidates scored under the tables as step b - 1 left them, one launch on this stream
+                    ids = ops.batch_prepare_mined(st['user'], st['pos'], self.shuffle_key, s, e - s, m.n_items,
+                                                  self.sample_seed, s, m.net.NET, m.net.tables(), self.sampler,
+                                                  st['item_meta'], out)
+                else:
+                    ids = ops.batch_prepare(st['user'], st['pos'], st['neg'], self.shuffle_key, s, e - s, m.n_items,
+                                            self.sample_seed, s, st['item_meta'], out, sampler=self.sampler)
                 if e - s == B:
                     self.prep_out = ids
             if softmax:

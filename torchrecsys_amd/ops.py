@@ -161,9 +161,20 @@ class Sampler:
       k            negatives per positive (the epoch then has k * N positions)
       popularity   draw candidates proportionally to the items' frequency in `stream_item`
       seen         (offsets (n_users+1,) int64, items int32 sorted per user): reject items the user has interacted with
-      max_tries    candidates tried before the last one is kept"""
+      max_tries    candidates tried before the last one is kept
+    Score-aware mining (batch_prepare_mined; not part of the C struct):
+      mine         None, or 'hardest': train on a negative the current model ranks high
+      candidates   K, negatives drawn and scored per triple (1..64)
+      top          m: the negative is drawn uniformly among the m highest-scoring candidates (1..K; 1 = the arg-max)"""
 
-    def __init__(self, k=1, popularity=False, seen=None, stream_item=None, max_tries=8):
+    def __init__(self, k=1, popularity=False, seen=None, stream_item=None, max_tries=8, mine=None, candidates=8, top=1):
+        if mine is not None and mine != 'hardest':
+            raise ValueError(f"mine must be 'hardest' or None, got {mine!r}")
+        self.mine = mine
+        self.candidates, self.top = int(candidates), int(top)
+        if mine is not None and not (1 <= self.candidates <= 64 and 1 <= self.top <= self.candidates):
+            raise ValueError(f"mining needs 1 <= candidates <= 64 and 1 <= top <= candidates, got candidates="
+                             f"{candidates!r}, top={top!r}")
         self.c = _lib.TrsSampler()
         self.c.k_neg, self.c.popularity, self.c.max_tries = int(k), int(bool(popularity)), int(max_tries)
         self.keep = [seen, stream_item]
@@ -514,6 +525,35 @@ def batch_prepare(stream_user, stream_item, neg_static, shuffle_key, t0, B, n_it
                                         ptr(item_meta), M, ptr(out["user"]), ptr(out["pos"]), ptr(out["neg"]),
                                         ptr(out.get("pos_meta")), ptr(out.get("neg_meta")), _samp(sampler), _stream()),
           "trs_batch_prepare")
+    return out
+
+
+def batch_prepare_mined(stream_user, stream_item, shuffle_key, t0, B, n_items, seed, offset, net, T, sampler,
+                        item_meta=None, out=None, return_chosen=False):
+    """batch_prepare with score-aware hard-negative mining (trs_batch_prepare_mined, one launch): `sampler.candidates`
+    negatives per triple are drawn by the sampler's rules, scored by scorer `net` ('linear' | 'fm') under the tables T as
+    they are now, and one of the `sampler.top` best becomes out["neg"].  return_chosen: out["chosen"] = the index of
+    the chosen candidate (int32).  No static negatives."""
+    dev = stream_user.device
+    if sampler is None or getattr(sampler, "mine", None) is None:
+        raise ValueError("batch_prepare_mined needs an ops.Sampler with mine='hardest'")
+    if net not in NET_ID:
+        raise ValueError(f"hard-negative mining scores candidates with the Linear / FM kernels, not net={net!r}")
+    M = 0 if item_meta is None else item_meta.shape[1]
+    if out is None:
+        out = {k: torch.empty(B, dtype=torch.int32, device=dev) for k in ("user", "pos", "neg")}
+        if M:
+            out["pos_meta"] = torch.empty((B, M), dtype=torch.int32, device=dev)
+            out["neg_meta"] = torch.empty((B, M), dtype=torch.int32, device=dev)
+    if return_chosen and "chosen" not in out:
+        out["chosen"] = torch.empty(B, dtype=torch.int32, device=dev)
+    check(_lib.load().trs_batch_prepare_mined(ptr(stream_user), ptr(stream_item), None, stream_user.numel(),
+                                              int(shuffle_key), int(t0), int(B), int(n_items), int(seed), int(offset),
+                                              ptr(item_meta), M, ptr(out["user"]), ptr(out["pos"]), ptr(out["neg"]),
+                                              ptr(out.get("pos_meta")), ptr(out.get("neg_meta")), _samp(sampler),
+                                              NET_ID[net], C.byref(T), sampler.candidates, sampler.top,
+                                              ptr(out.get("chosen")) if return_chosen else None, _stream()),
+          "trs_batch_prepare_mined")
     return out
 
 
