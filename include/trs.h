@@ -46,6 +46,8 @@ extern "C" {
  * (oracle/nets.py::bpr_loss against torch autograd), not by reference outputs. */
 #define TRS_LOSS_HINGE 0
 #define TRS_LOSS_BPR 1
+/* Sampled softmax over one positive and K sampled negatives per row (trs_score_multi_fwd_bwd only; not a pair loss). */
+#define TRS_LOSS_SAMPLED_SOFTMAX 2
 
 /* Embedding tables of one scorer.  Row-major (n_rows, D) fp32, as nn.Embedding.weight
  * (embeddings/init_embeddings.py:5-50,53-97).
@@ -94,7 +96,7 @@ const char* trs_last_error(void);
  *   5: trs_epoch_flags_ordered (flagged-first batches), trs_train_args.n_flagged_dev.
  *   6: batched top-k retrieval: trs_csr, trs_item_fold(_bytes), trs_retrieve_topk, trs_retrieve_workspace_bytes,
  *      trs_mask_seen, trs_rank_metrics.  (Entry points added since without touching an existing signature or struct:
- *      the in-batch softmax group, trs_batch_prepare_mined.) */
+ *      the in-batch softmax group, trs_batch_prepare_mined, trs_batch_prepare_multi, trs_score_multi_fwd_bwd.) */
 #define TRS_ABI_VERSION 6
 #define TRS_SYNC_WORDS 288
 int trs_abi_version(void);
@@ -187,6 +189,52 @@ int trs_batch_prepare_mined(const int32_t* stream_user_dev, const int32_t* strea
                             int32_t* neg_out, int32_t* pos_meta_out, int32_t* neg_meta_out, const trs_sampler* sampler,
                             int net, const trs_tables* tables, int32_t candidates, int32_t top, int32_t* chosen_out,
                             void* stream);
+
+/* trs_batch_prepare for K = n_neg sampled negatives per positive.  One launch: epoch shuffle ->
+ * (user u, positive p) -> K draws; no table row is read.  For epoch position q = t0 + t, seed s = sample_seed and
+ * ctr = sample_offset + t (the Philox counter trs_batch_prepare uses for that position), candidate
+ *   c_j = the sampler's draw (popularity / seen rejection / max_tries / k_neg of `sampler` unchanged; c_j != p) under the
+ *         seed s_j = (s + j * 0xD1B54A32D192ED03) mod 2^64, j = 0 .. K-1 — the candidate schedule of
+ *         trs_batch_prepare_mined; c_0 is exactly the negative trs_batch_prepare writes.  Candidates may repeat inside a
+ *         row (sampling with replacement).
+ * Outputs, all int32: user_out (B); items_out (1+K, B) slot-major — row 0 the positives, row 1+j candidate j — so the
+ * COO index list of the item tables is the block itself; meta_out (1+K, B, M) when M > 0: the metadata ids of the item
+ * in the same slot, looked up through item_meta (n_items, M).  With n_neg = 1, items_out = [pos; neg] and meta_out =
+ * [pos_meta; neg_meta] of trs_batch_prepare, bit for bit.  An id of the stream outside [0, n_items) is never used as an
+ * index here (the scorer reports it).
+ * TRS_E_ARG, nothing launched: n_neg outside 1..64; neg_static given (no static negatives); M outside
+ * 0..TRS_MAX_META, or M > 0 without item_meta / meta_out; the slice outside the epoch; bad sampler options; n_items < 2;
+ * NULL streams or outputs with B > 0. */
+int trs_batch_prepare_multi(const int32_t* stream_user_dev, const int32_t* stream_item_dev,
+                            const int32_t* neg_static_dev, int64_t N, uint64_t shuffle_key, int64_t t0, int64_t B,
+                            int64_t n_items, uint64_t sample_seed, uint64_t sample_offset,
+                            const int32_t* item_meta_dev, int32_t M, int32_t* user_out, int32_t* items_out,
+                            int32_t* meta_out, const trs_sampler* sampler, int32_t n_neg, void* stream);
+
+/* One training pass of a Linear / FM scorer over rows of one positive and K sampled negatives (the id blocks of
+ * trs_batch_prepare_multi: user (B), items (1+K, B), meta (1+K, B, M), int32), all rows read from the PRE-update tables.
+ * z(u, i) is the scorer's value of (u, i, metadata of i): Linear the score, FM the argument of its sigmoid — the
+ * arithmetic of trs_score_forward, bit for bit (FM scores below are sigmoid(z)).
+ *   loss = TRS_LOSS_SAMPLED_SOFTMAX: zh_0 = z(u,p)/tau, zh_{1+j} = z(u,c_j)/tau; row loss = logsumexp_s zh_s - zh_0;
+ *     d loss / d zh_s = (softmax_s - [s == 0]) * inv_B (row maximum subtracted); every occurrence of a repeated
+ *     candidate counts.  The user's 1-wide gradient is written as exactly 0 (z's derivative by it is 1 in every slot).
+ *   loss = TRS_LOSS_HINGE / TRS_LOSS_BPR: row loss = (1/K) sum_j pair(score_p, score_cj) of trs_score_fwd_bwd's pair
+ *     loss; tau is ignored.  With K = 1 the staged gradients and the loss are those of trs_score_fwd_bwd, bit for bit.
+ * loss_sum += the sum of the row losses (the caller divides by B); auc_count (may be NULL) += #(score_p > score_c0).
+ * Both are ACCUMULATED.  inv_B = 1/B of the mean.
+ * Staged gradients, field-major, F = 1 + (1+K)(1+M) fields: grad_rows (F, B, D) and grad_lin (F, B); field 0 the user,
+ * field 1+s the item of slot s, field 1+(1+K)+m*(1+K)+s the metadata column m of slot s — every table's entries are one
+ * contiguous ((1+K)*B, D) block in the order of its id block.  Linear has no 1-wide metadata tables: those fields are 0.
+ * grad_rows == NULL (then grad_lin must be NULL too): forward only — the same loss and AUC count, nothing staged.
+ * An id outside its table is clamped for addressing, sets bit 0 of *err_flag_dev (may be NULL) and zeroes its row's
+ * loss and gradients.
+ * TRS_E_ARG, nothing launched: tables NULL or a NULL member; net not TRS_NET_LINEAR / TRS_NET_FM; K outside 1..64; an
+ * unknown loss id; M != tables->M; a D the scorer kernels do not take; tau <= 0 or not finite; loss_sum NULL; grad_lin
+ * without grad_rows or the reverse; NULL ids with B > 0. */
+int trs_score_multi_fwd_bwd(int net, const trs_tables* tables, const int32_t* user_dev, const int32_t* items_dev,
+                            const int32_t* meta_dev, int64_t B, int32_t M, int32_t K, int32_t loss, float tau,
+                            float inv_B, float* loss_sum_dev, int32_t* auc_count_dev, float* grad_rows_dev,
+                            float* grad_lin_dev, int32_t* err_flag_dev, void* stream);
 
 /* ------------------------------------------------------------------ scorers: forward only (a2, a3, a6) */
 /* Fused positive+negative scoring pass; the user row is gathered once for both passes.

@@ -11,6 +11,7 @@ TRS_MAX_META = 8
 TRS_NET_LINEAR = 0
 TRS_NET_FM = 1
 LOSS_ID = {"hinge": 0, "bpr": 1}  # TRS_LOSS_HINGE / TRS_LOSS_BPR
+LOSS_SAMPLED_SOFTMAX = 2  # TRS_LOSS_SAMPLED_SOFTMAX (trs_score_multi_fwd_bwd only: not a pair loss)
 RETRIEVE_KMAX = 128  # TRS_RETRIEVE_KMAX: largest k of the fused retrieval kernel
 RETRIEVE_DMAX = 256  # TRS_RETRIEVE_DMAX: largest D of the fused retrieval kernel
 ABI_VERSION = 6  # == TRS_ABI_VERSION of include/trs.h (tests/test_abi.py)
@@ -127,6 +128,10 @@ PROTOTYPES = {
     "trs_batch_prepare_mined": (C.c_int, [_vp, _vp, _vp, _i64, _u64, _i64, _i64, _i64, _u64, _u64, _vp, _i32,
                                           _vp, _vp, _vp, _vp, _vp, C.POINTER(TrsSampler), C.c_int, _T, _i32, _i32, _vp,
                                           _vp]),
+    "trs_batch_prepare_multi": (C.c_int, [_vp, _vp, _vp, _i64, _u64, _i64, _i64, _i64, _u64, _u64, _vp, _i32,
+                                          _vp, _vp, _vp, C.POINTER(TrsSampler), _i32, _vp]),
+    "trs_score_multi_fwd_bwd": (C.c_int, [C.c_int, _T, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _f, _f, _vp, _vp, _vp,
+                                          _vp, _vp, _vp]),
     "trs_score_forward": (C.c_int, [C.c_int, _T, _Bp, _vp, _vp, _vp]),
     "trs_score_fwd_bwd": (C.c_int, [C.c_int, _T, _Bp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "trs_score_backward": (C.c_int, [C.c_int, _T, _Bp, _vp, _vp, _vp, _vp, _vp]),

@@ -1,0 +1,525 @@
+// multineg.hip — training on K sampled negatives per positive (trs_batch_prepare_multi, trs_score_multi_fwd_bwd;
+// include/trs.h): sampled softmax over {positive, c_0 .. c_{K-1}} and the mean of K hinge / BPR pairs.
+//
+// prepare_multi_kernel: integer work only — one thread per (candidate j, row t), rows along the lanes, so the slot-major
+// (1+K, B) id block is written in whole lines; the threads of candidate 0 also write the user and the positive.
+//
+// multineg_kernel (wave = 64): one aligned group of G lanes per row, 16-byte lanes, as score_kernel.  The user row and
+// its 1-wide term are loaded once and stay in registers.  Candidates go in rounds of C = min(G, 8, 16 / floats per lane) (slots past the last
+// candidate load it again: loads stay unconditional): lane c of the group reads candidate r0 + c's id, a shuffle hands
+// every id to the whole group, and the C item rows (+ 1-wide terms, + metadata rows) are independent unconditional
+// loads, all in flight before the first reduction (mine_kernel's pattern).  Every z is pass_forward_z's.
+//   pair losses     one sweep: candidate j's weight needs only its own score and the positive's; the user row's
+//                   gradient and the positive's weight are accumulated and written after the sweep.
+//   sampled softmax every zh before any weight: sweep 1 keeps the running (maximum, sum of exponentials) of the row.
+//                   K <= C: the single round's rows are still in registers and the gradients follow at once.
+//                   Otherwise sweep 2 re-reads the rows (L2-hot), recomputes each z — bit-identical, the same code on
+//                   the same tables — and stages the gradients.  Forward-only mode stops after sweep 1.
+// Gradients are staged, never added to a table here: every gradient of a step comes from the pre-update tables.  No LDS
+// (but the block's loss reduction), no scratch memory.
+#include "score_kernels.h"
+
+using namespace trs;
+
+namespace {
+
+#ifndef MULTI_ROW_VGPRS
+// VGPRs of candidate item rows in flight per round (with metadata the field sums take as many again).  mine_kernel holds 32;
+// here the rows stay live until their weights are known: at 32 the FM softmax kernels spill into AGPRs and run one wave
+// per SIMD, at 16 every instantiation runs at least two and the whole-row FM shapes three or four
+#define MULTI_ROW_VGPRS 16
+#endif
+
+constexpr uint64_t MULTI_KEY_STEP = 0xD1B54A32D192ED03ull;  // candidate j draws under seed + j * this (mine.hip's)
+
+struct PrepMultiArgs {
+  const int32_t* su;
+  const int32_t* si;
+  int64_t N;
+  uint64_t shuffle_key;
+  int hb;
+  int64_t t0, B, n_items;
+  uint64_t seed, offset;
+  const int32_t* item_meta;
+  int M, Kn;
+  int32_t *user, *items, *meta;
+  TrsSampler S;
+};
+
+__global__ __launch_bounds__(TRS_BLOCK) void prepare_multi_kernel(const PrepMultiArgs a) {
+  const int64_t stride = (int64_t)gridDim.x * TRS_BLOCK;
+  const int64_t total = a.B * a.Kn;
+  for (int64_t w = (int64_t)blockIdx.x * TRS_BLOCK + threadIdx.x; w < total; w += stride) {
+    const int64_t j = w / a.B;
+    const int64_t t = w - j * a.B;
+    const int64_t p = trs_feistel_perm(a.t0 + t, a.N * a.S.k_neg, a.shuffle_key, a.hb) % a.N;
+    const int32_t u = a.su[p];
+    const int32_t i = a.si[p];
+    int32_t c;
+    if (a.S.max_tries != 0 && (uint64_t)(int64_t)i >= (uint64_t)a.n_items)
+      c = 0;  // (reported by the scorer; the option paths index tables by the ids)
+    else
+      c = (int32_t)trs_sample_neg_opt(a.seed + (uint64_t)j * MULTI_KEY_STEP, a.offset + (uint64_t)t, (int64_t)u,
+                                      (int64_t)i, a.n_items, a.S);
+    a.items[(1 + j) * a.B + t] = c;
+    if (j == 0) {
+      a.user[t] = u;
+      a.items[t] = i;
+    }
+    if (a.M > 0) {
+      // an id outside the item table is reported by the scorer kernel; keep this lookup in range
+      const int64_t cc = ((uint64_t)(int64_t)c < (uint64_t)a.n_items) ? c : 0;
+      for (int m = 0; m < a.M; ++m) a.meta[((1 + j) * a.B + t) * a.M + m] = a.item_meta[cc * a.M + m];
+      if (j == 0) {
+        const int64_t ic = ((uint64_t)(int64_t)i < (uint64_t)a.n_items) ? i : 0;
+        for (int m = 0; m < a.M; ++m) a.meta[t * a.M + m] = a.item_meta[ic * a.M + m];
+      }
+    }
+  }
+}
+
+struct MultiArgs {
+  trs_tables T;
+  const int32_t* user;   // (B)
+  const int32_t* items;  // (1+K, B): row 0 the positives, row 1+j candidate j
+  const int32_t* meta;   // (1+K, B, M) or NULL
+  int64_t B;
+  int Kn;    // sampled negatives per row, 1..64
+  int loss;  // TRS_LOSS_HINGE | TRS_LOSS_BPR (SM == false)
+  float inv_tau, inv_B;
+  float* loss_sum;
+  int32_t* auc_count;
+  float* grad_rows;  // (F, B, D), F = 1 + (1+K)(1+M); NULL: forward only
+  float* grad_lin;   // (F, B)
+  int32_t* err;
+};
+
+template <int G>
+__device__ __forceinline__ int group_or(int v) {
+#pragma unroll
+  for (int o = G >> 1; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
+  return v;
+}
+
+// The forward part of one round: the ids of candidates r0 .. r0 + C - 1 (lane c of the group reads candidate r0 + c's,
+// a shuffle hands them round) and their C independent passes.
+template <int NET, int VEC, int G, int K, int C>
+__device__ __forceinline__ void round_forward(const MultiArgs& a, const RowReg<VEC, K>& ur, float u_lin, int r0,
+                                              int64_t tc, int lig, int gbase, RowReg<VEC, K> (&ir)[C],
+                                              RowReg<VEC, K> (&Ss)[C], float (&z)[C]) {
+  const int Kn = a.Kn;
+  int jm = r0 + (lig & (C - 1));
+  jm = jm < Kn ? jm : Kn - 1;  // past the last candidate: load it again (its score is not used)
+  const int32_t mine = a.items[(int64_t)(1 + jm) * a.B + tc];
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    const int32_t id = __shfl(mine, gbase + c, 64);
+    const int64_t cl = (uint64_t)(int64_t)id < (uint64_t)a.T.n_items ? id : 0;
+    const int jc = r0 + c < Kn ? r0 + c : Kn - 1;
+    float il, ls;
+    bool ok = true;  // (the row's ids were checked before the first load)
+    z[c] = pass_forward_z<NET, VEC, G, K>(a.T, ur, u_lin, cl, a.meta + (int64_t)(1 + jc) * a.B * a.T.M, 4, tc, true,
+                                          lig, ir[c], Ss[c], il, ls, ok);
+  }
+}
+
+// META = false: the tables have no metadata columns (M == 0 at compile time: the field sums of a round die with its
+// reduction instead of staying in registers beside the item rows).
+template <int NET, int VEC, int G, int K, bool SM, bool META>
+__global__ __launch_bounds__(TRS_BLOCK) void multineg_kernel(const MultiArgs a) {
+  constexpr int N = K * VEC;
+  constexpr int CR = MULTI_ROW_VGPRS / N < 8 ? (MULTI_ROW_VGPRS / N < 1 ? 1 : MULTI_ROW_VGPRS / N) : 8;  // candidate rows in flight
+  constexpr int C = G < CR ? G : CR;           // candidates per round (a power of two)
+  constexpr int TPW = TRS_WAVE / G;            // rows per wave per iteration
+  const trs_tables& T = a.T;
+  const int D = T.D;
+  const int M = META ? T.M : 0;
+  const int64_t B = a.B;
+  const int Kn = a.Kn;
+  const int S1 = 1 + Kn;
+  const int lane = threadIdx.x & 63;
+  const int lig = lane % G;
+  const int gbase = lane - lig;
+  const int64_t wave = ((int64_t)blockIdx.x * TRS_BLOCK + threadIdx.x) >> 6;
+  const int64_t nwave = ((int64_t)gridDim.x * TRS_BLOCK) >> 6;
+  const bool grad = a.grad_rows != nullptr;
+  const float invK = 1.0f / (float)Kn;
+  const float wK = a.inv_B * invK;  // weight of one pair of the mean over B rows and K pairs
+  const int64_t BD = B * (int64_t)D;
+  float* const gr = a.grad_rows;
+  float* const gl = a.grad_lin;
+
+  float loss_acc = 0.f;
+  int auc_acc = 0;
+
+  const int64_t niter = (B + TPW - 1) / TPW;
+  for (int64_t it_ = wave; it_ < niter; it_ += nwave) {
+    const int64_t t = it_ * TPW + lane / G;
+    const bool valid = t < B;
+    const int64_t tc = valid ? t : 0;  // loads stay unconditional
+
+    // every id of the row against its table first (integer work, spread over the group): a row with an id out of range
+    // carries no loss and zero gradients, as score_kernel's dead triples
+    int64_t uid = a.user[tc];
+    int bad = 0;
+    if ((uint64_t)uid >= (uint64_t)T.n_users) { bad = 1; uid = 0; }
+    for (int s = lig; s < S1; s += G) {
+      const int64_t e = (int64_t)s * B + tc;
+      if ((uint64_t)(int64_t)a.items[e] >= (uint64_t)T.n_items) bad = 1;
+      for (int m = 0; m < M; ++m)
+        if ((uint64_t)(int64_t)a.meta[e * M + m] >= (uint64_t)T.n_meta[m]) bad = 1;
+    }
+    bad = group_or<G>(bad);
+    if (valid && bad && lig == 0 && a.err) atomicOr(a.err, 1);
+    const bool live = valid && !bad;
+
+    RowReg<VEC, K> ur;
+    row_load<VEC, G, K>(ur, T.user, uid, D, lig);
+    const float u_lin = T.user_lin[uid];
+    int64_t pid = a.items[tc];
+    if ((uint64_t)pid >= (uint64_t)T.n_items) pid = 0;
+    RowReg<VEC, K> pr, Sp;
+    float p_lin, lin_p;
+    bool okp = true;
+    const float z0 = pass_forward_z<NET, VEC, G, K>(T, ur, u_lin, pid, a.meta, 4, tc, true, lig, pr, Sp, p_lin, lin_p, okp);
+    const float sp = NET == TRS_NET_FM ? sigmoidf_(z0) : z0;  // = pass_forward's score
+
+    const float zh0 = z0 * a.inv_tau;
+    float mx = zh0, sum = 1.f, inv_sum = 1.f;  // sampled softmax: running maximum and sum of exponentials of the row
+    RowReg<VEC, K> acc;  // sum over the candidates of g_j * (the row the user's gradient multiplies)
+#pragma unroll
+    for (int n = 0; n < N; ++n) acc.v[n] = 0.f;
+    float gp_acc = 0.f, gn_sum = 0.f, row_loss = 0.f, p_sum = 0.f;
+
+    // sampled softmax, the statistics of one round: running (maximum, sum of exponentials) over zh_0 .. zh_K
+    auto stats_round = [&](int r0, const float (&z)[C]) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        if (r0 + c < Kn) {
+          const float zh = z[c] * a.inv_tau;
+          const float mn = fmaxf(mx, zh);
+          sum = sum * expf(mx - mn) + expf(zh - mn);
+          mx = mn;
+          if (r0 + c == 0 && live && lig == 0) auc_acc += (sp > (NET == TRS_NET_FM ? sigmoidf_(z[c]) : z[c])) ? 1 : 0;
+        }
+      }
+    };
+    // the weights and the staged gradients of one round (pair losses: also their forward)
+    auto grad_round = [&](int r0, const RowReg<VEC, K> (&ir)[C], const RowReg<VEC, K> (&Ss)[C], const float (&z)[C]) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        const int j = r0 + c;
+        if (j < Kn) {
+          float g;  // d loss / d z_j
+          if (SM) {
+            const float pj = expf(z[c] * a.inv_tau - mx) * inv_sum;
+            p_sum += pj;
+            g = live ? (pj * a.inv_B) * a.inv_tau : 0.f;
+          } else {
+            const float sn = NET == TRS_NET_FM ? sigmoidf_(z[c]) : z[c];
+            float lval, dneg;
+            trs_pair_loss(a.loss, sp, sn, lval, dneg);
+            const float act = live ? dneg : 0.f;
+            gp_acc += -act * wK;
+            g = act * wK;
+            if (live && lig == 0) {
+              row_loss += lval;
+              if (j == 0) auc_acc += (sp > sn) ? 1 : 0;
+            }
+            if (NET == TRS_NET_FM) g = g * ((1.0f - sn) * sn);  // through the sigmoid
+          }
+          gn_sum += g;
+          // the user's share.  FM: g*(S - u) (= g*item when M == 0); Linear: g*S
+          if (NET == TRS_NET_FM) {
+            if (M == 0) {
+#pragma unroll
+              for (int n = 0; n < N; ++n) acc.v[n] += g * ir[c].v[n];
+            } else {
+#pragma unroll
+              for (int n = 0; n < N; ++n) acc.v[n] += g * (Ss[c].v[n] - ur.v[n]);
+            }
+          } else {
+#pragma unroll
+            for (int n = 0; n < N; ++n) acc.v[n] += g * Ss[c].v[n];
+          }
+          if (grad && valid) {
+            RowReg<VEC, K> gv;
+            // the candidate's item row.  FM: g*(S - item) (= g*u when M == 0); Linear: g*u
+            if (NET == TRS_NET_FM && M != 0) {
+#pragma unroll
+              for (int n = 0; n < N; ++n) gv.v[n] = g * (Ss[c].v[n] - ir[c].v[n]);
+            } else {
+#pragma unroll
+              for (int n = 0; n < N; ++n) gv.v[n] = g * ur.v[n];
+            }
+            row_store<VEC, G, K>(gv, gr + (int64_t)(2 + j) * BD + t * (int64_t)D, D, lig);
+            // metadata fields (rows re-read: they are L1/L2-hot from the forward part)
+            for (int m = 0; m < M; ++m) {
+              if (NET == TRS_NET_FM) {
+                int64_t mid = a.meta[((int64_t)(1 + j) * B + t) * M + m];
+                if ((uint64_t)mid >= (uint64_t)T.n_meta[m]) mid = 0;
+                RowReg<VEC, K> mr;
+                row_load<VEC, G, K>(mr, T.meta[m], mid, D, lig);
+#pragma unroll
+                for (int n = 0; n < N; ++n) gv.v[n] = g * (Ss[c].v[n] - mr.v[n]);
+              } else {
+#pragma unroll
+                for (int n = 0; n < N; ++n) gv.v[n] = g * ur.v[n];
+              }
+              row_store<VEC, G, K>(gv, gr + (int64_t)(1 + S1 + m * S1 + 1 + j) * BD + t * (int64_t)D, D, lig);
+            }
+            if (lig == 0) {
+              gl[(int64_t)(2 + j) * B + t] = g;
+              for (int m = 0; m < M; ++m)  // Linear has no 1-wide metadata tables: those fields stay 0
+                gl[(int64_t)(1 + S1 + m * S1 + 1 + j) * B + t] = NET == TRS_NET_FM ? g : 0.f;
+            }
+          }
+        }
+      }
+    };
+
+    if (SM) {
+      RowReg<VEC, K> ir[C], Ss[C];
+      float z[C];
+      const bool one_round = Kn <= C;  // the single round's rows stay in registers; otherwise sweep 2 re-reads them
+      for (int r0 = 0; r0 < Kn; r0 += C) {
+        round_forward<NET, VEC, G, K, C>(a, ur, u_lin, r0, tc, lig, gbase, ir, Ss, z);
+        stats_round(r0, z);
+      }
+      // logsumexp - zh_0 with the maximum taken out of the difference first (zh grows as 1 / tau)
+      if (live && lig == 0) loss_acc += (mx - zh0) + logf(sum);
+      inv_sum = 1.0f / sum;
+      if (grad) {
+        if (one_round) {
+          grad_round(0, ir, Ss, z);
+        } else {
+          for (int r0 = 0; r0 < Kn; r0 += C) {  // (each z again: bit-identical, the same code on the same tables)
+            round_forward<NET, VEC, G, K, C>(a, ur, u_lin, r0, tc, lig, gbase, ir, Ss, z);
+            grad_round(r0, ir, Ss, z);
+          }
+        }
+      }
+    } else {
+      for (int r0 = 0; r0 < Kn; r0 += C) {
+        RowReg<VEC, K> ir[C], Ss[C];
+        float z[C];
+        round_forward<NET, VEC, G, K, C>(a, ur, u_lin, r0, tc, lig, gbase, ir, Ss, z);
+        grad_round(r0, ir, Ss, z);
+      }
+    }
+    if (!SM && live && lig == 0) loss_acc += row_loss * invK;
+
+    if (grad && valid) {
+      float gp;  // d loss / d z of the positive
+      if (SM) {
+        gp = live ? (-p_sum * a.inv_B) * a.inv_tau : 0.f;  // softmax_0 - 1 = -(sum of the candidates' shares)
+      } else {
+        gp = gp_acc;
+        if (NET == TRS_NET_FM) gp = gp * ((1.0f - sp) * sp);
+      }
+      RowReg<VEC, K> gv;
+      // field 0: user
+      if (NET == TRS_NET_FM) {
+        if (M == 0) {
+#pragma unroll
+          for (int n = 0; n < N; ++n) gv.v[n] = gp * pr.v[n] + acc.v[n];
+        } else {
+#pragma unroll
+          for (int n = 0; n < N; ++n) gv.v[n] = gp * (Sp.v[n] - ur.v[n]) + acc.v[n];
+        }
+      } else {
+#pragma unroll
+        for (int n = 0; n < N; ++n) gv.v[n] = gp * Sp.v[n] + acc.v[n];
+      }
+      row_store<VEC, G, K>(gv, gr + t * (int64_t)D, D, lig);
+      // field 1: the positive's item row
+      if (NET == TRS_NET_FM && M != 0) {
+#pragma unroll
+        for (int n = 0; n < N; ++n) gv.v[n] = gp * (Sp.v[n] - pr.v[n]);
+      } else {
+#pragma unroll
+        for (int n = 0; n < N; ++n) gv.v[n] = gp * ur.v[n];
+      }
+      row_store<VEC, G, K>(gv, gr + BD + t * (int64_t)D, D, lig);
+      for (int m = 0; m < M; ++m) {
+        if (NET == TRS_NET_FM) {
+          int64_t mid = a.meta[t * M + m];
+          if ((uint64_t)mid >= (uint64_t)T.n_meta[m]) mid = 0;
+          RowReg<VEC, K> mr;
+          row_load<VEC, G, K>(mr, T.meta[m], mid, D, lig);
+#pragma unroll
+          for (int n = 0; n < N; ++n) gv.v[n] = gp * (Sp.v[n] - mr.v[n]);
+        } else {
+#pragma unroll
+          for (int n = 0; n < N; ++n) gv.v[n] = gp * ur.v[n];
+        }
+        row_store<VEC, G, K>(gv, gr + (int64_t)(1 + S1 + m * S1) * BD + t * (int64_t)D, D, lig);
+      }
+      if (lig == 0) {
+        // the user's 1-wide term enters every z of the row with derivative 1: the softmax weights sum to exactly 0
+        gl[t] = SM ? 0.f : gp + gn_sum;
+        gl[B + t] = gp;
+        for (int m = 0; m < M; ++m) gl[(int64_t)(1 + S1 + m * S1) * B + t] = NET == TRS_NET_FM ? gp : 0.f;
+      }
+    }
+  }
+
+  if (a.loss_sum) {  // as score_kernel: lanes -> wave -> block -> one atomic per block
+    __shared__ float s_loss[TRS_BLOCK / TRS_WAVE];
+    __shared__ int s_auc[TRS_BLOCK / TRS_WAVE];
+    const float wl = trs_wave_sum(loss_acc);
+    const int wa = trs_wave_sum_i(auc_acc);
+    if (lane == 0) {
+      s_loss[threadIdx.x >> 6] = wl;
+      s_auc[threadIdx.x >> 6] = wa;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      float L = 0.f;
+      int A = 0;
+#pragma unroll
+      for (int w = 0; w < TRS_BLOCK / TRS_WAVE; ++w) {
+        L += s_loss[w];
+        A += s_auc[w];
+      }
+      if (L != 0.f) atomicAdd(a.loss_sum, L);
+      if (A != 0 && a.auc_count) atomicAdd(a.auc_count, A);
+    }
+  }
+}
+
+template <int NET, bool SM>
+int launch_multi(const MultiArgs& a, hipStream_t s) {
+  RowCfg c;
+  if (!pick_row_cfg(a.T.D, c)) {
+    trs_set_error("trs_score_multi_fwd_bwd: unsupported n_factors D=%d (need 1..1024; D %% 4 != 0 only up to 256)",
+                  a.T.D);
+    return TRS_E_ARG;
+  }
+  const int tpw = TRS_WAVE / c.g;
+  const int64_t waves = (a.B + tpw - 1) / tpw;
+  const int grid = trs_grid(waves, TRS_BLOCK / TRS_WAVE);
+#define TRS_CASE(V, GG, KK)                                                                              \
+  if (c.vec == V && c.g == GG && c.k == KK) {                                                            \
+    if (a.T.M > 0)                                                                                       \
+      hipLaunchKernelGGL((multineg_kernel<NET, V, GG, KK, SM, true>), dim3(grid), dim3(TRS_BLOCK), 0, s, a);  \
+    else                                                                                                 \
+      hipLaunchKernelGGL((multineg_kernel<NET, V, GG, KK, SM, false>), dim3(grid), dim3(TRS_BLOCK), 0, s, a); \
+    TRS_CHECK_LAUNCH("multineg_kernel");                                                                 \
+    return TRS_OK;                                                                                       \
+  }
+  TRS_CASE(4, 2, 1)
+  TRS_CASE(4, 4, 1)
+  TRS_CASE(4, 8, 1)
+  TRS_CASE(4, 16, 1)
+  TRS_CASE(4, 32, 1)
+  TRS_CASE(4, 64, 1)
+  TRS_CASE(4, 64, 2)
+  TRS_CASE(4, 64, 4)
+  TRS_CASE(1, 4, 1)
+  TRS_CASE(1, 16, 1)
+  TRS_CASE(1, 64, 1)
+  TRS_CASE(1, 64, 4)
+#undef TRS_CASE
+  trs_set_error("trs_score_multi_fwd_bwd: internal: no kernel for D=%d", a.T.D);
+  return TRS_E_ARG;
+}
+
+}  // namespace
+
+extern "C" int trs_batch_prepare_multi(const int32_t* stream_user_dev, const int32_t* stream_item_dev,
+                                       const int32_t* neg_static_dev, int64_t N, uint64_t shuffle_key, int64_t t0,
+                                       int64_t B, int64_t n_items, uint64_t sample_seed, uint64_t sample_offset,
+                                       const int32_t* item_meta_dev, int32_t M, int32_t* user_out, int32_t* items_out,
+                                       int32_t* meta_out, const trs_sampler* sampler, int32_t n_neg, void* stream) {
+  const char* who = "trs_batch_prepare_multi";
+  TRS_REQUIRE(n_neg >= 1 && n_neg <= 64, "%s: n_neg=%d outside 1..64", who, n_neg);
+  TRS_REQUIRE(neg_static_dev == nullptr, "%s: no static negatives (neg_static must be NULL)", who);
+  TRS_REQUIRE(M >= 0 && M <= TRS_MAX_META, "%s: M=%d outside 0..%d", who, M, TRS_MAX_META);
+  TRS_REQUIRE(M == 0 || (item_meta_dev && meta_out), "%s: M=%d needs item_meta and the metadata output", who, M);
+  const int64_t kn = sampler && sampler->k_neg > 1 ? sampler->k_neg : 1;
+  TRS_REQUIRE(N > 0 && t0 >= 0 && B >= 0 && t0 + B <= N * kn, "%s: slice [%lld,%lld) outside [0,%lld)", who,
+              (long long)t0, (long long)(t0 + B), (long long)(N * kn));
+  TRS_REQUIRE(!sampler || (sampler->k_neg >= 1 && (!sampler->popularity || (sampler->pop_items && sampler->pop_n > 0)) &&
+                           ((sampler->seen_off == nullptr) == (sampler->seen_items == nullptr))),
+              "%s: bad sampler options", who);
+  TRS_REQUIRE(n_items >= 2, "%s: dynamic sampling needs n_items >= 2", who);
+  if (B == 0) return TRS_OK;
+  TRS_REQUIRE(stream_user_dev && stream_item_dev, "%s: stream is NULL", who);
+  TRS_REQUIRE(user_out && items_out, "%s: outputs are NULL", who);
+  PrepMultiArgs a = {};
+  a.su = stream_user_dev;
+  a.si = stream_item_dev;
+  a.N = N;
+  a.shuffle_key = shuffle_key;
+  a.hb = trs_feistel_half_bits(N * kn);
+  a.t0 = t0;
+  a.B = B;
+  a.n_items = n_items;
+  a.seed = sample_seed;
+  a.offset = sample_offset;
+  a.item_meta = item_meta_dev;
+  a.M = M;
+  a.Kn = n_neg;
+  a.user = user_out;
+  a.items = items_out;
+  a.meta = meta_out;
+  a.S = trs_sampler_args(sampler);
+  hipLaunchKernelGGL(prepare_multi_kernel, dim3(trs_grid(B * n_neg, TRS_BLOCK)), dim3(TRS_BLOCK), 0,
+                     (hipStream_t)stream, a);
+  TRS_CHECK_LAUNCH("prepare_multi_kernel");
+  return TRS_OK;
+}
+
+extern "C" int trs_score_multi_fwd_bwd(int net, const trs_tables* tables, const int32_t* user_dev,
+                                       const int32_t* items_dev, const int32_t* meta_dev, int64_t B, int32_t M,
+                                       int32_t K, int32_t loss, float tau, float inv_B, float* loss_sum_dev,
+                                       int32_t* auc_count_dev, float* grad_rows_dev, float* grad_lin_dev,
+                                       int32_t* err_flag_dev, void* stream) {
+  const char* who = "trs_score_multi_fwd_bwd";
+  TRS_REQUIRE(tables != nullptr, "%s: tables is NULL", who);
+  TRS_REQUIRE(net == TRS_NET_LINEAR || net == TRS_NET_FM, "%s: net must be TRS_NET_LINEAR or TRS_NET_FM", who);
+  TRS_REQUIRE(K >= 1 && K <= 64, "%s: K=%d outside 1..64", who, K);
+  TRS_REQUIRE(loss == TRS_LOSS_HINGE || loss == TRS_LOSS_BPR || loss == TRS_LOSS_SAMPLED_SOFTMAX,
+              "%s: unknown loss id %d", who, loss);
+  TRS_REQUIRE(M >= 0 && M <= TRS_MAX_META && M == tables->M, "%s: M=%d does not match the tables' M=%d (0..%d)", who, M,
+              tables->M, TRS_MAX_META);
+  RowCfg cfg;
+  TRS_REQUIRE(pick_row_cfg(tables->D, cfg),
+              "%s: unsupported n_factors D=%d (need 1..1024; D %% 4 != 0 only up to 256)", who, tables->D);
+  TRS_REQUIRE(tables->user && tables->item && tables->user_lin && tables->item_lin,
+              "%s: a user/item table or its 1-wide table is NULL", who);
+  TRS_REQUIRE(tables->n_users > 0 && tables->n_items > 0, "%s: empty user/item table", who);
+  for (int m = 0; m < M; ++m) {
+    TRS_REQUIRE(tables->meta[m] && tables->n_meta[m] > 0, "%s: metadata table %d is NULL/empty", who, m);
+    if (net == TRS_NET_FM) TRS_REQUIRE(tables->meta_lin[m], "%s: linear_metadata table %d is NULL", who, m);
+  }
+  TRS_REQUIRE(tau > 0.f && tau <= 3.0e38f, "%s: temperature must be positive and finite", who);
+  TRS_REQUIRE(loss_sum_dev, "%s: loss_sum is NULL", who);
+  TRS_REQUIRE((grad_rows_dev == nullptr) == (grad_lin_dev == nullptr),
+              "%s: grad_rows and grad_lin must both be given or both NULL (forward only)", who);
+  TRS_REQUIRE(B >= 0, "%s: negative batch size", who);
+  if (B == 0) return TRS_OK;
+  TRS_REQUIRE(user_dev && items_dev, "%s: user/item ids are NULL", who);
+  TRS_REQUIRE(M == 0 || meta_dev, "%s: metadata ids are NULL but M=%d", who, M);
+  MultiArgs a = {};
+  a.T = *tables;
+  a.user = user_dev;
+  a.items = items_dev;
+  a.meta = meta_dev;
+  a.B = B;
+  a.Kn = K;
+  a.loss = loss;
+  a.inv_tau = 1.0f / tau;
+  a.inv_B = inv_B;
+  a.loss_sum = loss_sum_dev;
+  a.auc_count = auc_count_dev;
+  a.grad_rows = grad_rows_dev;
+  a.grad_lin = grad_lin_dev;
+  a.err = err_flag_dev;
+  const bool sm = loss == TRS_LOSS_SAMPLED_SOFTMAX;
+  if (net == TRS_NET_FM)
+    return sm ? launch_multi<TRS_NET_FM, true>(a, (hipStream_t)stream) : launch_multi<TRS_NET_FM, false>(a, (hipStream_t)stream);
+  return sm ? launch_multi<TRS_NET_LINEAR, true>(a, (hipStream_t)stream)
+            : launch_multi<TRS_NET_LINEAR, false>(a, (hipStream_t)stream);
+}

@@ -540,6 +540,50 @@ class SparseScorerTrainer:
         if self.kind not in ("sgd", "sparse_adam", "adagrad"):
             self.opt.step()
 
+    # K sampled negatives per positive (fit(n_negatives=K) / fit(loss='sampled_softmax')): (K, loss id of
+    # trs_score_multi_fwd_bwd, temperature), set by fit()
+    multineg = None
+
+    def multineg_step(self, ids, loss_slot):
+        """One step on rows of one positive and K sampled negatives: ids = ops.batch_prepare_multi's blocks (user (B,),
+        items (1 + K, B), meta (1 + K, B, M)).  loss_slot receives the SUM of the row losses (caller divides by B).  One
+        kernel stages every gradient from the pre-update tables; the rows then go through the same per-table paths as
+        step()'s, each table's entries being one contiguous block of the staging buffer.  No host sync."""
+        K, loss_id, tau = self.multineg
+        B, D, M = ids["user"].shape[0], self.D, self.M
+        S1 = 1 + K
+        F = ops.multineg_fields(K, M)
+        if getattr(self, "_mn_rows", None) is None or self._mn_rows.numel() < F * self.cap * D:
+            self._mn_rows = torch.empty(F * self.cap * D, dtype=torch.float32, device=self.dev)
+            self._mn_lin = torch.empty(F * self.cap, dtype=torch.float32, device=self.dev)
+        gr = self._mn_rows[:F * B * D].view(F, B, D)
+        gl = self._mn_lin[:F * B].view(F, B)
+        net = self.net
+        ops.score_multi_fwd_bwd(net.NET, net.tables(), ids["user"], ids["items"], ids.get("meta"), loss_id, tau,
+                                loss_slot, None, gr, gl, self.err)
+        if self.kind == "sgd":
+            fn = lambda p, idx, vals, ld: ops.rows_scatter_add(p.data, idx, vals, -_group_of(self.opt, p)["lr"], ld=ld)
+        elif self.kind in ("sparse_adam", "adagrad"):
+            fn = lambda p, idx, vals, ld: apply_rows(self.kind, self.opt, p, self.row_state[id(p)], idx, vals, ld)
+        else:
+            self.opt.zero_grad()
+            fn = self._set_sparse_grad
+        ps = self.params
+        item_idx = ids["items"].view(-1)  # slot-major, as the staged fields 1 .. 1 + K
+        fn(ps[0], ids["user"], gr[0], D)
+        fn(ps[1], item_idx, gr[1:1 + S1].reshape(S1 * B, D), D)
+        if loss_id != ops._lib.LOSS_SAMPLED_SOFTMAX:  # (under the softmax that block is exactly 0: nothing to apply)
+            fn(ps[2], ids["user"], gl[0].reshape(B, 1), 1)
+        fn(ps[3], item_idx, gl[1:1 + S1].reshape(S1 * B, 1), 1)
+        for m in range(M):
+            midx = ids["meta"][:, :, m].contiguous().view(-1)  # one copy per column: the ids are (slot, row, column)
+            sl = slice(1 + S1 + m * S1, 1 + S1 + (m + 1) * S1)
+            fn(ps[4 + m], midx, gr[sl].reshape(S1 * B, D), D)
+            if net_has_meta_lin(net):
+                fn(ps[4 + M + m], midx, gl[sl].reshape(S1 * B, 1), 1)
+        if self.kind not in ("sgd", "sparse_adam", "adagrad"):
+            self.opt.step()
+
     @staticmethod
     def _set_sparse_grad(p, idx, vals, ld):
         g = torch.sparse_coo_tensor(idx.reshape(1, -1).long(), vals, size=p.shape)

@@ -362,7 +362,8 @@ class TorchRecSys(torch.nn.Module):
 
     @_host_side
     def fit(self, optimizer, epochs=10, batch_size=512, profile_epochs: int = 0, sync_tables_every: int = 1,
-            sync_bn: bool = False, loss: str = 'hinge', temperature: float = 1.0, logq_correction: bool = False):
+            sync_bn: bool = False, loss: str = 'hinge', temperature: float = 1.0, logq_correction: bool = False,
+            n_negatives: int = 1):
         """Fits the model (reference model.py:203-288).  Per step: [shuffle slice + negative sampling] -> fused
         gather + scoring + hinge + backward -> sparse-row optimiser update; the loss stays on the device and is
         read back once per epoch (the reference syncs every step, model.py:200).
@@ -396,13 +397,54 @@ class TorchRecSys(torch.nn.Module):
         scorers and `k` visits per positive work unchanged; the steps run one by one (a mining launch, then the step),
         not on the slice-ahead presorted path, because the negative of step t depends on the tables after step t - 1.
         evaluate() keeps drawing unmined negatives, so its loss and AUC compare across mined and unmined runs.  Under
-        torch.distributed every rank mines on its own replica with its own seed."""
+        torch.distributed every rank mines on its own replica with its own seed.
+
+        n_negatives=K (1..64) and loss='sampled_softmax' (Linear and FM, rng='device' with dynamic_neg_sampling=True;
+        DESIGN 4.8): every row trains on K sampled negatives.  Row i has user u, positive p and candidates c_0 .. c_{K-1}:
+        c_j is the sampler's draw for the row's epoch position under seed s + j * 0xD1B54A32D192ED03 (mod 2^64), the
+        candidate schedule of the mining option, so c_0 is the negative a plain run draws and popularity / reject_seen /
+        max_tries / `k` visits per positive compose unchanged.  A candidate never equals the row's positive; candidates
+        MAY repeat inside a row and every occurrence counts (sampling with replacement).
+          loss='sampled_softmax' (any K >= 1): with z the scorer's value (Linear the score, FM the argument of its
+            sigmoid, as retrieval, mining and the in-batch softmax use), zh_0 = z(u,p) / temperature and zh_{1+j} =
+            z(u,c_j) / temperature, the row loss is logsumexp_s zh_s - zh_0, averaged over the batch.  logq_correction
+            stays with loss='softmax': the popularity sampler's fallback draw makes its Q differ from the item frequency.
+          loss in ('hinge', 'bpr') with K > 1: the row loss is the mean of the K pair losses (1/K) sum_j pair(s_p, s_cj)
+            on the scores today's step uses (Linear the score, FM the sigmoid).  K = 1 is today's run, on today's paths.
+        Every optimiser and metadata scorers work; the steps run one by one (one launch draws the ids, one kernel stages
+        every gradient from the pre-update tables, then the per-table row updates).  Not with neg_sampling['mine'];
+        K > 1 not with loss='softmax'.  evaluate() then reports the same loss on the test split with K candidates drawn by
+        the evaluation sampler's rules; AUC stays pairwise on (p, c_0).  Under torch.distributed every rank draws and
+        trains on its own replica: nothing new crosses ranks."""
         # loss: 'hinge' = the reference's only loss (helper/loss.py:5-9, model.py:282); 'bpr' = -log sigmoid(pos - neg),
         # the alternative BASELINE.json's north_star names (evaluate() then reports that loss too); 'softmax' = the
         # in-batch softmax (engine.SparseScorerTrainer.softmax_step; not a pair loss, so not in LOSS_ID)
-        from ._lib import LOSS_ID
-        if loss not in LOSS_ID and loss != 'softmax':
-            raise ValueError(f"loss must be one of {sorted(list(LOSS_ID) + ['softmax'])}")
+        from ._lib import LOSS_ID, LOSS_SAMPLED_SOFTMAX
+        if loss not in LOSS_ID and loss not in ('softmax', 'sampled_softmax'):
+            raise ValueError(f"loss must be one of {sorted(list(LOSS_ID) + ['softmax', 'sampled_softmax'])}")
+        if isinstance(n_negatives, bool) or not isinstance(n_negatives, (int, np.integer)) or not 1 <= n_negatives <= 64:
+            raise ValueError(f"n_negatives must be an integer in 1..64, got {n_negatives!r}")
+        n_negatives = int(n_negatives)
+        multineg = loss == 'sampled_softmax' or n_negatives > 1
+        if loss == 'softmax' and n_negatives > 1:
+            raise ValueError("n_negatives > 1 does not combine with loss='softmax' (its negatives are the batch's other "
+                             "positives); loss='sampled_softmax' is the softmax over sampled negatives")
+        if multineg:
+            what = "loss='sampled_softmax'" if loss == 'sampled_softmax' else f"n_negatives={n_negatives}"
+            if self.net_type not in ('linear', 'fm'):
+                raise ValueError(f"{what} trains the Linear and FM scorers (net_type 'linear' or 'fm'), not "
+                                 f"net_type={self.net_type!r}")
+            if self.rng != 'device':
+                raise ValueError(f"{what} draws its negatives with the device sampler: it needs rng='device', not "
+                                 f"rng={self.rng!r}")
+            if not self.dynamic_neg_sampling:
+                raise ValueError(f"{what} needs dynamic_neg_sampling=True (there is one static negative per row)")
+            if (getattr(self, 'neg_sampling', None) or {}).get('mine') is not None:
+                raise ValueError(f"{what} trains on every candidate: it does not combine with neg_sampling['mine'] "
+                                 "(which trains on one of them)")
+            if logq_correction:
+                raise ValueError("logq_correction applies to loss='softmax' only (the popularity sampler's fallback draw "
+                                 "makes the sampled candidates' Q differ from the item frequency)")
         if loss == 'softmax':
             if self.net_type not in ('linear', 'fm'):
                 raise ValueError("loss='softmax' trains the Linear and FM scorers (net_type 'linear' or 'fm'), "
@@ -410,6 +452,7 @@ class TorchRecSys(torch.nn.Module):
             if getattr(self, 'neg_sampling', None):
                 raise ValueError("loss='softmax' takes its negatives from the batch: it does not combine with "
                                  "neg_sampling options (k > 1 would repeat positives inside a batch)")
+        if loss in ('softmax', 'sampled_softmax'):
             try:
                 tau = float(temperature)
             except (TypeError, ValueError):
@@ -417,15 +460,21 @@ class TorchRecSys(torch.nn.Module):
             if not (math.isfinite(tau) and tau > 0):
                 raise ValueError(f"temperature must be a positive finite number, got {temperature!r}")
         elif temperature != 1.0 or logq_correction:
-            raise ValueError("temperature and logq_correction apply to loss='softmax' only")
+            raise ValueError("temperature applies to loss='softmax' / 'sampled_softmax' and logq_correction to "
+                             "loss='softmax' only")
         if self.net_type == 'mlp':
             self.net.compute.sync_bn = bool(sync_bn)
         runner = self.make_runner(optimizer, batch_size)
         if loss == 'softmax':
             self._softmax = (tau, self._logq(runner.data) if logq_correction else None)
             runner.trainer.softmax = self._softmax
+        elif multineg:  # K sampled negatives per positive: engine.SparseScorerTrainer.multineg_step
+            self._multineg = (n_negatives, LOSS_ID.get(loss, LOSS_SAMPLED_SOFTMAX), tau if loss == 'sampled_softmax' else 1.0)
+            runner.trainer.multineg = self._multineg
         else:
             runner.trainer.loss_id = LOSS_ID[loss]
+        if not multineg:
+            self._multineg = None
         self.loss = loss
         for epoch in range(epochs):
             self.net = self.net.train()
@@ -484,7 +533,8 @@ class TorchRecSys(torch.nn.Module):
     @_host_side
     def evaluate(self, batch_size=512, eval_metrics=['loss', 'auc']):
         """reference model.py:292-338: eval-mode scores of the test split, hinge loss and pairwise AUC per batch,
-        unweighted means over batches, printed; returns None."""
+        unweighted means over batches, printed; returns None.  The printed values are kept at full precision in
+        `self.eval_results` ({'loss': ..., 'auc': ...}, this rank's view of the means)."""
         self.net = self.net.eval()
         if self.data_processor.test_data.get('user_id', torch.empty(0)).numel() == 0:
             print("|--- No test data to evaluate.")
@@ -509,13 +559,17 @@ class TorchRecSys(torch.nn.Module):
         # reductions, one id-range check per group); the MLP's activations are per batch
         # fit(loss='softmax'): every test batch is its own softmax, one batch at a time
         softmax = getattr(self, "loss", "hinge") == "softmax" and hasattr(self.net, 'table_params')
+        multineg = getattr(self, "_multineg", None) if hasattr(self.net, 'table_params') else None
+        multineg = multineg if self.rng == 'device' else None
+        if multineg is not None:
+            self._evaluate_multineg(multineg, st, sample_seed, nb, batch_size, n_test, loss_sums, auc_counts)
         group = 64 if hasattr(self.net, 'table_params') and not softmax else 1
         group = max(1, min(group, (1 << 22) // max(batch_size, 1)))
         if softmax:
             sm_loss = torch.zeros(nb, dtype=torch.float32, device=dev)
             sm = ops.InBatchSoftmax(min(batch_size, n_test), self.n_factors, dev)
             err = torch.zeros(1, dtype=torch.int32, device=dev)
-        for b0 in range(0, nb, group):
+        for b0 in (range(0, nb, group) if multineg is None else ()):  # (the pair / in-batch softmax batches)
             b1 = min(b0 + group, nb)
             s, e = b0 * batch_size, min(b1 * batch_size, n_test)
             if self.rng == 'reference':
@@ -541,6 +595,7 @@ class TorchRecSys(torch.nn.Module):
         if 'auc' in eval_metrics:
             results['auc'] = [float(np.float32(ac[b]) / np.float32(sizes[b])) for b in range(nb)]
         world = tdist.world_info()[1]
+        self.eval_results = {}  # the printed values at full precision (the method itself returns None, as the reference's)
         for metric in eval_metrics:
             values = results.get(metric, [])
             if world > 1:  # unweighted mean over all ranks' batches
@@ -548,7 +603,26 @@ class TorchRecSys(torch.nn.Module):
                 value = tot / cnt if cnt else 0
             else:
                 value = sum(values) / len(values) if values else 0
+            self.eval_results[metric] = value
             print(f'|--- Testing {metric}: {value:.4f}')
+
+    def _evaluate_multineg(self, multineg, st, sample_seed, nb, batch_size, n_test, loss_sums, auc_counts):
+        """evaluate() after fit(n_negatives=K) / fit(loss='sampled_softmax'): the same loss over K candidates of the
+        evaluation sampler's rules, one test batch per forward-only launch; the AUC count is pairwise on (p, c_0)."""
+        K, loss_id, tau = multineg
+        err = torch.zeros(1, dtype=torch.int32, device=loss_sums.device)
+        out = None
+        for b in range(nb):
+            s, e = b * batch_size, min((b + 1) * batch_size, n_test)
+            ids = ops.batch_prepare_multi(st['user'], st['pos'], 0, s, e - s, self.n_items, sample_seed, s, K,
+                                          st['item_meta'], out if e - s == batch_size else None,
+                                          sampler=self._eval_sampler())
+            if e - s == batch_size:
+                out = ids
+            ops.score_multi_fwd_bwd(self.net.NET, self.net.tables(), ids['user'], ids['items'], ids.get('meta'),
+                                    loss_id, tau, loss_sums[b:b + 1], auc_counts[b:b + 1], err_flag=err,
+                                    forward_only=True)
+        check_err_flag(err, "evaluate")
 
     # ------------------------------------------------------------------------------------------------ predict
     @_host_side
@@ -875,6 +949,9 @@ class FitRunner:
         # presort nor the C step loop applies — the per-step loop below, one mining launch in front of every step
         mining = getattr(self.sampler, "mine", None) is not None
         fast = fast and not mining
+        # K sampled negatives per positive: a prepare launch, then the staging kernel and the per-table row updates
+        multineg = getattr(self.trainer, "multineg", None)
+        fast = fast and multineg is None
         if fast and m.rng == 'reference':
             fast = self.ep['user'].dtype == torch.int32
         ops.stamp("run_steps:setup")
@@ -918,7 +995,11 @@ class FitRunner:
             else:
                 st = self.st
                 out = self.prep_out if (self.prep_out is not None and e - s == B) else None
-                if mining:  # K candidates scored under the tables as step b - 1 left them, one launch on this stream
+                if multineg is not None:
+                    ids = ops.batch_prepare_multi(st['user'], st['pos'], self.shuffle_key, s, e - s, m.n_items,
+                                                  self.sample_seed, s, multineg[0], st['item_meta'], out,
+                                                  sampler=self.sampler)
+                elif mining:  # K candidates scored under the tables as step b - 1 left them, one launch on this stream
                     ids = ops.batch_prepare_mined(st['user'], st['pos'], self.shuffle_key, s, e - s, m.n_items,
                                                   self.sample_seed, s, m.net.NET, m.net.tables(), self.sampler,
                                                   st['item_meta'], out)
@@ -929,6 +1010,8 @@ class FitRunner:
                     self.prep_out = ids
             if softmax:
                 self.trainer.softmax_step(ids, self.loss_sums[b:b + 1])
+            elif multineg is not None:
+                self.trainer.multineg_step(ids, self.loss_sums[b:b + 1])
             else:
                 self.trainer.step(ids, self.loss_sums[b:b + 1])
             self.next_batch += 1

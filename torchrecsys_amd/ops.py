@@ -557,6 +557,67 @@ def batch_prepare_mined(stream_user, stream_item, shuffle_key, t0, B, n_items, s
     return out
 
 
+def batch_prepare_multi(stream_user, stream_item, shuffle_key, t0, B, n_items, seed, offset, n_neg, item_meta=None,
+                        out=None, sampler=None):
+    """batch_prepare for n_neg sampled negatives per positive (trs_batch_prepare_multi, one launch).  Returns a dict of
+    int32 GPU tensors: user (B,), items (1 + n_neg, B) slot-major — row 0 the positives, row 1 + j candidate j, drawn
+    under seed + j * 0xD1B54A32D192ED03 (candidate 0 is batch_prepare's negative) — and, with item_meta (n_items, M),
+    meta (1 + n_neg, B, M).  pos / neg are views of rows 0 / 1.  Candidates may repeat inside a row.  No static
+    negatives."""
+    dev = stream_user.device
+    K = int(n_neg)
+    M = 0 if item_meta is None else item_meta.shape[1]
+    if out is None:
+        out = {"user": torch.empty(B, dtype=torch.int32, device=dev),
+               "items": torch.empty((1 + K, B), dtype=torch.int32, device=dev)}
+        if M:
+            out["meta"] = torch.empty((1 + K, B, M), dtype=torch.int32, device=dev)
+        out["pos"], out["neg"] = out["items"][0], out["items"][1] if K >= 1 else None
+    check(_lib.load().trs_batch_prepare_multi(ptr(stream_user), ptr(stream_item), None, stream_user.numel(),
+                                              int(shuffle_key), int(t0), int(B), int(n_items), int(seed), int(offset),
+                                              ptr(item_meta), M, ptr(out["user"]), ptr(out["items"]),
+                                              ptr(out.get("meta")), _samp(sampler), K, _stream()),
+          "trs_batch_prepare_multi")
+    return out
+
+
+def multineg_fields(K, M):
+    """Staged gradient fields of score_multi_fwd_bwd: 1 user + (1 + K) item slots + M * (1 + K) metadata slots."""
+    return 1 + (1 + K) * (1 + M)
+
+
+def score_multi_fwd_bwd(net, T, user, items, meta, loss, tau, loss_sum, auc_count=None, grad_rows=None, grad_lin=None,
+                        err_flag=None, forward_only=False, inv_B=None):
+    """One pass over rows of one positive and K = items.shape[0] - 1 sampled negatives (trs_score_multi_fwd_bwd).
+    user (B,), items (1 + K, B), meta (1 + K, B, M) or None: int32, the blocks of batch_prepare_multi.  loss:
+    _lib.LOSS_ID (mean of K pairs) or _lib.LOSS_SAMPLED_SOFTMAX (with temperature tau).  loss_sum / auc_count are
+    accumulated in place.  Returns (grad_rows (F, B, D), grad_lin (F, B)), F = multineg_fields(K, M), field-major: the
+    user, the 1 + K item slots, then the 1 + K slots of every metadata column; (None, None) with forward_only."""
+    _dev(user, "user ids", torch.int32)
+    _dev(items, "item id block", torch.int32)
+    _dev(meta, "metadata id block", torch.int32)
+    if items.dim() != 2 or items.shape[1] != user.shape[0] or items.shape[0] < 2:
+        raise ValueError("items must be the (1 + K, B) block of batch_prepare_multi")
+    B, K, D, M = user.shape[0], items.shape[0] - 1, T.D, T.M
+    if M and (meta is None or tuple(meta.shape) != (1 + K, B, M)):
+        raise ValueError(f"meta must be the (1 + K, B, M) = ({1 + K}, {B}, {M}) block of batch_prepare_multi")
+    if forward_only:
+        grad_rows = grad_lin = None
+    else:
+        F = multineg_fields(K, M)
+        if grad_rows is None:
+            grad_rows = torch.empty((F, B, D), dtype=torch.float32, device=user.device)
+        if grad_lin is None:
+            grad_lin = torch.empty((F, B), dtype=torch.float32, device=user.device)
+    if inv_B is None:
+        inv_B = 1.0 / B if B > 0 else 0.0
+    check(_lib.load().trs_score_multi_fwd_bwd(NET_ID[net], C.byref(T), ptr(user), ptr(items), ptr(meta) if M else None,
+                                              B, M, K, int(loss), float(tau), float(inv_B), ptr(loss_sum),
+                                              ptr(auc_count), ptr(grad_rows), ptr(grad_lin), ptr(err_flag), _stream()),
+          "trs_score_multi_fwd_bwd")
+    return grad_rows, grad_lin
+
+
 def score_all_items(net, T, user_id, n_items, device, item_meta=None, item0=0, n=None):
     n = n_items - item0 if n is None else n
     out = torch.empty(n, dtype=torch.float32, device=device)
