@@ -858,9 +858,11 @@ def test_colsum_rowdot_outer_gather():
 
 
 @pytest.mark.parametrize("net,D", [("fm", 64), ("fm", 8), ("fm", 128), ("fm", 80), ("fm", 10), ("linear", 32),
-                                   ("linear", 256), ("linear", 7)])
+                                   ("linear", 256), ("linear", 7), ("fm", 512), ("fm", 1024), ("linear", 3),
+                                   ("fm", 201)])
 def test_fast_sgd_step_matches_oracle_and_generic_path(net, D):
-    """csrc/fast_step.hip (3-kernel exact SGD step, ids given) vs the oracle and vs the generic staged path."""
+    """csrc/fast_step.hip (3-kernel exact SGD step, ids given) vs the oracle and vs the generic staged path.  The last
+    four widths are the row shapes (4,64,2), (4,64,4), (1,4,1) and (1,64,4) of csrc/score_kernels.h's table."""
     ops = _ops()
     B, lr = 777, 0.05
     p, batch, _ = make_case(net, D, 0, B, NU=90, NI=41, seed=D)

@@ -1300,37 +1300,29 @@ __global__ __launch_bounds__(TRS_BLOCK) void meta_stage_kernel(const ScoreArgs a
 template <int NET, int MT>
 static int launch_meta_stage_mt(const ScoreArgs& a, hipStream_t s) {
   RowCfg c;
-  if (!pick_row_cfg(a.T.D, c)) {
-    trs_set_error("unsupported n_factors D=%d", a.T.D);
-    return TRS_E_ARG;
-  }
+  TRS_TRY(row_cfg_for("launch_meta_stage", a.T.D, c));
   const int tpw = TRS_WAVE / c.g;
   int64_t iters = (a.Bt.B + 512 * 4 * (int64_t)tpw - 1) / (512 * 4 * (int64_t)tpw);  // as launch_fwd_stage
   iters = iters < 2 ? 2 : (iters > 8 ? 8 : iters);
   int64_t grid = ((a.Bt.B + tpw - 1) / tpw + 4 * iters - 1) / (4 * iters);
   grid = grid < 1 ? 1 : (grid > 4096 ? 4096 : grid);
   const dim3 gr((unsigned)grid), bl(TRS_BLOCK);
-#define TRS_CASE(V, GG, KK)                                                                                   \
-  if (c.vec == V && c.g == GG && c.k == KK) {                                                                 \
-    if (a.o.kind != OPT_SGD) { /* adaptive rules: whole-row shapes only */                                    \
-      if (V * GG * KK != a.T.D) return 1;                                                                     \
-      if (a.o.kind == OPT_ADAM)                                                                               \
-        hipLaunchKernelGGL((meta_stage_kernel<NET, V, GG, KK, true, MT, OPT_ADAM>), gr, bl, 0, s, a);          \
-      else                                                                                                    \
-        hipLaunchKernelGGL((meta_stage_kernel<NET, V, GG, KK, true, MT, OPT_ADAGRAD>), gr, bl, 0, s, a);       \
-    } else if (V * GG * KK == a.T.D)                                                                          \
-      hipLaunchKernelGGL((meta_stage_kernel<NET, V, GG, KK, true, MT>), gr, bl, 0, s, a);                      \
-    else                                                                                                      \
-      hipLaunchKernelGGL((meta_stage_kernel<NET, V, GG, KK, false, MT>), gr, bl, 0, s, a);                     \
-    TRS_CHECK_LAUNCH("meta_stage_kernel");                                                                    \
-    return TRS_OK;                                                                                            \
-  }
-  TRS_CASE(4, 8, 1)
-  TRS_CASE(4, 16, 1)
-  TRS_CASE(4, 32, 1)
-  TRS_CASE(4, 64, 1)
-#undef TRS_CASE
-  return 1;  // shape not instantiated: the caller falls back to the generic scorer's staging mode
+  // any other shape is not instantiated: the caller falls back to the generic scorer's staging mode
+  return for_whole_row_shape(c, [&](auto V, auto G, auto K) {
+    const bool full = V() * G() * K() == a.T.D;
+    if (a.o.kind != OPT_SGD) {  // adaptive rules: whole rows only
+      if (!full) return 1;
+      if (a.o.kind == OPT_ADAM)
+        hipLaunchKernelGGL((meta_stage_kernel<NET, V(), G(), K(), true, MT, OPT_ADAM>), gr, bl, 0, s, a);
+      else
+        hipLaunchKernelGGL((meta_stage_kernel<NET, V(), G(), K(), true, MT, OPT_ADAGRAD>), gr, bl, 0, s, a);
+    } else if (full)
+      hipLaunchKernelGGL((meta_stage_kernel<NET, V(), G(), K(), true, MT>), gr, bl, 0, s, a);
+    else
+      hipLaunchKernelGGL((meta_stage_kernel<NET, V(), G(), K(), false, MT>), gr, bl, 0, s, a);
+    TRS_CHECK_LAUNCH("meta_stage_kernel");
+    return TRS_OK;
+  });
 }
 
 // > 0: not handled here (caller uses score_kernel<MODE 2>)
@@ -1363,10 +1355,7 @@ template <int NET>
 static int launch_fwd_stage(const FastArgs& a, hipStream_t s, uint32_t* deferred = nullptr) {
   if (deferred) *deferred = 0;  // > 0: INL 3 was launched with that many workgroups (= arrivals on a.sync)
   RowCfg c;
-  if (!pick_row_cfg(a.T.D, c)) {
-    trs_set_error("unsupported n_factors D=%d", a.T.D);
-    return TRS_E_ARG;
-  }
+  TRS_TRY(row_cfg_for("launch_fwd_stage", a.T.D, c));
   const int tpw = TRS_WAVE / c.g;
   // ~8 pipelined iterations per lane group: few enough workgroups that every wave overlaps its own loads with its
   // own reductions, enough (>= 2 per CU) to fill the chip
@@ -1385,53 +1374,43 @@ static int launch_fwd_stage(const FastArgs& a, hipStream_t s, uint32_t* deferred
   // alone: no change).  TRS_K1_NT = 0 | 1 | 3 forces a setting.
   const int ntu_env = trs_tuning().k1_nt;
   const int ntu = ntu_env >= 0 ? ntu_env : ((int64_t)a.T.n_users * a.T.D * 4 > ((int64_t)512 << 20) ? 3 : 0);
-#define TRS_LAUNCH(V, GG, KK, FULL)                                                                             \
-  {                                                                                                             \
-    const dim3 gr((unsigned)grid), bl(TRS_BLOCK);                                                               \
-    if (src == 0 && a.udup_pos && a.o.kind == OPT_ADAM)                                                          \
-      hipLaunchKernelGGL((fwd_stage_kernel<NET, V, GG, KK, 0, FULL, 1, OPT_ADAM>), gr, bl, 0, s, a);              \
-    else if (src == 0 && a.udup_pos && a.o.kind == OPT_ADAGRAD)                                                  \
-      hipLaunchKernelGGL((fwd_stage_kernel<NET, V, GG, KK, 0, FULL, 1, OPT_ADAGRAD>), gr, bl, 0, s, a);           \
-    else if (src == 0 && a.udup_pos && a.idup_pos && a.sync && deferred && iters <= DEFER_ITERS) {               \
-      static const int64_t cap = defer_resident_cap(fwd_stage_kernel<NET, V, GG, KK, 0, FULL, 3>);                \
-      if (grid <= cap) {                                                                                        \
-        FastArgs b = a;                                                                                         \
-        b.sync_target = a.sync_base + (uint32_t)grid;                                                           \
-        if (ntu == 1) hipLaunchKernelGGL((fwd_stage_kernel<NET, V, GG, KK, 0, FULL, 3, OPT_SGD, 1>), gr, bl, 0, s, b); \
-        else if (ntu == 3) hipLaunchKernelGGL((fwd_stage_kernel<NET, V, GG, KK, 0, FULL, 3, OPT_SGD, 3>), gr, bl, 0, s, b); \
-        else hipLaunchKernelGGL((fwd_stage_kernel<NET, V, GG, KK, 0, FULL, 3>), gr, bl, 0, s, b);                 \
-        *deferred = (uint32_t)grid;                                                                             \
-      } else                                                                                                    \
-        hipLaunchKernelGGL((fwd_stage_kernel<NET, V, GG, KK, 0, FULL, 2>), gr, bl, 0, s, a);                      \
-    } else if (src == 0 && a.udup_pos && a.idup_pos)                                                             \
-      hipLaunchKernelGGL((fwd_stage_kernel<NET, V, GG, KK, 0, FULL, 2>), gr, bl, 0, s, a);                        \
-    else if (src == 0 && a.udup_pos) hipLaunchKernelGGL((fwd_stage_kernel<NET, V, GG, KK, 0, FULL, 1>), gr, bl, 0, s, a); \
-    else if (src == 0) hipLaunchKernelGGL((fwd_stage_kernel<NET, V, GG, KK, 0, FULL, 0>), gr, bl, 0, s, a);      \
-    else if (src == 1) hipLaunchKernelGGL((fwd_stage_kernel<NET, V, GG, KK, 1, FULL, 0>), gr, bl, 0, s, a);      \
-    else hipLaunchKernelGGL((fwd_stage_kernel<NET, V, GG, KK, 2, FULL, 0>), gr, bl, 0, s, a);                    \
-  }
-#define TRS_CASE(V, GG, KK)                                                                                     \
-  if (c.vec == V && c.g == GG && c.k == KK) {                                                                   \
-    if (V * GG * KK == a.T.D) TRS_LAUNCH(V, GG, KK, true) else TRS_LAUNCH(V, GG, KK, false)                      \
-    TRS_CHECK_LAUNCH("fwd_stage_kernel");                                                                       \
-    return TRS_OK;                                                                                              \
-  }
-  TRS_CASE(4, 2, 1)
-  TRS_CASE(4, 4, 1)
-  TRS_CASE(4, 8, 1)
-  TRS_CASE(4, 16, 1)
-  TRS_CASE(4, 32, 1)
-  TRS_CASE(4, 64, 1)
-  TRS_CASE(4, 64, 2)
-  TRS_CASE(4, 64, 4)
-  TRS_CASE(1, 4, 1)
-  TRS_CASE(1, 16, 1)
-  TRS_CASE(1, 64, 1)
-  TRS_CASE(1, 64, 4)
-#undef TRS_CASE
-#undef TRS_LAUNCH
-  trs_set_error("internal: no kernel for D=%d", a.T.D);
-  return TRS_E_ARG;
+  const dim3 gr((unsigned)grid), bl(TRS_BLOCK);
+  return for_row_shape(c, [&](auto V, auto G, auto K) {
+    constexpr int VV = V(), GG = G(), KK = K();
+    auto launch = [&](auto FULL) {
+      constexpr bool FU = FULL();
+      if (src == 0 && a.udup_pos && a.o.kind == OPT_ADAM)
+        hipLaunchKernelGGL((fwd_stage_kernel<NET, VV, GG, KK, 0, FU, 1, OPT_ADAM>), gr, bl, 0, s, a);
+      else if (src == 0 && a.udup_pos && a.o.kind == OPT_ADAGRAD)
+        hipLaunchKernelGGL((fwd_stage_kernel<NET, VV, GG, KK, 0, FU, 1, OPT_ADAGRAD>), gr, bl, 0, s, a);
+      else if (src == 0 && a.udup_pos && a.idup_pos && a.sync && deferred && iters <= DEFER_ITERS) {
+        // one value per instantiation (NET, shape, FULL): the residency of THIS kernel, asked once
+        static const int64_t cap = defer_resident_cap(fwd_stage_kernel<NET, VV, GG, KK, 0, FU, 3>);
+        if (grid <= cap) {
+          FastArgs b = a;
+          b.sync_target = a.sync_base + (uint32_t)grid;
+          if (ntu == 1)
+            hipLaunchKernelGGL((fwd_stage_kernel<NET, VV, GG, KK, 0, FU, 3, OPT_SGD, 1>), gr, bl, 0, s, b);
+          else if (ntu == 3)
+            hipLaunchKernelGGL((fwd_stage_kernel<NET, VV, GG, KK, 0, FU, 3, OPT_SGD, 3>), gr, bl, 0, s, b);
+          else
+            hipLaunchKernelGGL((fwd_stage_kernel<NET, VV, GG, KK, 0, FU, 3>), gr, bl, 0, s, b);
+          *deferred = (uint32_t)grid;
+        } else
+          hipLaunchKernelGGL((fwd_stage_kernel<NET, VV, GG, KK, 0, FU, 2>), gr, bl, 0, s, a);
+      } else if (src == 0 && a.udup_pos && a.idup_pos)
+        hipLaunchKernelGGL((fwd_stage_kernel<NET, VV, GG, KK, 0, FU, 2>), gr, bl, 0, s, a);
+      else if (src == 0 && a.udup_pos)
+        hipLaunchKernelGGL((fwd_stage_kernel<NET, VV, GG, KK, 0, FU, 1>), gr, bl, 0, s, a);
+      else if (src == 0) hipLaunchKernelGGL((fwd_stage_kernel<NET, VV, GG, KK, 0, FU, 0>), gr, bl, 0, s, a);
+      else if (src == 1) hipLaunchKernelGGL((fwd_stage_kernel<NET, VV, GG, KK, 1, FU, 0>), gr, bl, 0, s, a);
+      else hipLaunchKernelGGL((fwd_stage_kernel<NET, VV, GG, KK, 2, FU, 0>), gr, bl, 0, s, a);
+    };
+    if (VV * GG * KK == a.T.D) launch(std::true_type{});
+    else launch(std::false_type{});
+    TRS_CHECK_LAUNCH("fwd_stage_kernel");
+    return TRS_OK;
+  });
 }
 
 static int launch_flagged_update(const FastArgs& a, hipStream_t s) {
@@ -1449,40 +1428,21 @@ static int launch_flagged_update(const FastArgs& a, hipStream_t s) {
 template <int WHICH>  // 0: item owners (K2a), 1: users (K3), 2: duplicated users only (K3')
 static int launch_plain(const FastArgs& a, hipStream_t s) {
   RowCfg c;
-  if (!pick_row_cfg(a.T.D, c)) {
-    trs_set_error("unsupported n_factors D=%d", a.T.D);
-    return TRS_E_ARG;
-  }
+  TRS_TRY(row_cfg_for("launch_plain", a.T.D, c));
   const int per = (TRS_WAVE / c.g) * 2;
   const dim3 gr(trs_grid((a.B + per - 1) / per, TRS_BLOCK / TRS_WAVE)), bl(TRS_BLOCK);
-#define TRS_PL(V, GG, KK, FULL)                                                                        \
-  {                                                                                                    \
-    if (WHICH == 0) hipLaunchKernelGGL((item_owner_update_kernel<V, GG, KK, FULL>), gr, bl, 0, s, a);  \
-    else if (WHICH == 1) hipLaunchKernelGGL((user_plain_update_kernel<V, GG, KK, FULL>), gr, bl, 0, s, a); \
-    else hipLaunchKernelGGL((user_dup_update_kernel<V, GG, KK, FULL>), gr, bl, 0, s, a);               \
-  }
-#define TRS_CASE(V, GG, KK)                                                                     \
-  if (c.vec == V && c.g == GG && c.k == KK) {                                                   \
-    if (V * GG * KK == a.T.D) TRS_PL(V, GG, KK, true) else TRS_PL(V, GG, KK, false)             \
-    TRS_CHECK_LAUNCH("plain update kernel");                                                    \
-    return TRS_OK;                                                                              \
-  }
-  TRS_CASE(4, 2, 1)
-  TRS_CASE(4, 4, 1)
-  TRS_CASE(4, 8, 1)
-  TRS_CASE(4, 16, 1)
-  TRS_CASE(4, 32, 1)
-  TRS_CASE(4, 64, 1)
-  TRS_CASE(4, 64, 2)
-  TRS_CASE(4, 64, 4)
-  TRS_CASE(1, 4, 1)
-  TRS_CASE(1, 16, 1)
-  TRS_CASE(1, 64, 1)
-  TRS_CASE(1, 64, 4)
-#undef TRS_CASE
-#undef TRS_PL
-  trs_set_error("internal: no kernel for D=%d", a.T.D);
-  return TRS_E_ARG;
+  return for_row_shape(c, [&](auto V, auto G, auto K) {
+    constexpr int VV = V(), GG = G(), KK = K();
+    auto launch = [&](auto FULL) {
+      if (WHICH == 0) hipLaunchKernelGGL((item_owner_update_kernel<VV, GG, KK, FULL()>), gr, bl, 0, s, a);
+      else if (WHICH == 1) hipLaunchKernelGGL((user_plain_update_kernel<VV, GG, KK, FULL()>), gr, bl, 0, s, a);
+      else hipLaunchKernelGGL((user_dup_update_kernel<VV, GG, KK, FULL()>), gr, bl, 0, s, a);
+    };
+    if (VV * GG * KK == a.T.D) launch(std::true_type{});
+    else launch(std::false_type{});
+    TRS_CHECK_LAUNCH("plain update kernel");
+    return TRS_OK;
+  });
 }
 
 static int launch_updates(const FastArgs& a, hipStream_t s, hipEvent_t ev_k3) {
@@ -1551,7 +1511,7 @@ int trs_launch_pair_scores(int net, const ScoreArgs* ap, hipStream_t s) {
       !a.T.item_lin || a.Bt.B < 1)
     return 1;
   RowCfg c;
-  if (!pick_row_cfg(a.T.D, c) || c.vec != 4 || c.k != 1 || c.g < 8) return 1;
+  if (!pick_row_cfg(a.T.D, c)) return 1;
   const int tpw = TRS_WAVE / c.g;
   const int iters_env = trs_tuning().pass_iters;
   int64_t iters = iters_env > 0 ? iters_env : (a.Bt.B + 512 * 4 * (int64_t)tpw - 1) / (512 * 4 * (int64_t)tpw);
@@ -1567,27 +1527,22 @@ int trs_launch_pair_scores(int net, const ScoreArgs* ap, hipStream_t s) {
   // forces a setting: bit 0 user rows, bit 1 item rows)
   const int ntm_env = trs_tuning().pass_nt;
   const int ntm = ntm_env >= 0 ? ntm_env : ((int64_t)a.T.n_users * a.T.D * 4 > ((int64_t)512 << 20) ? 1 : 0);
-#define TRS_PS(NETV, V, GG)                                                                                    \
-  {                                                                                                            \
-    if (V * GG == a.T.D && ntm == 1) hipLaunchKernelGGL((pair_scores_kernel<NETV, V, GG, 1, true, 1>), gr, bl, 0, s, a); \
-    else if (V * GG == a.T.D && ntm == 2) hipLaunchKernelGGL((pair_scores_kernel<NETV, V, GG, 1, true, 2>), gr, bl, 0, s, a); \
-    else if (V * GG == a.T.D && ntm == 3) hipLaunchKernelGGL((pair_scores_kernel<NETV, V, GG, 1, true, 3>), gr, bl, 0, s, a); \
-    else if (V * GG == a.T.D) hipLaunchKernelGGL((pair_scores_kernel<NETV, V, GG, 1, true>), gr, bl, 0, s, a); \
-    else hipLaunchKernelGGL((pair_scores_kernel<NETV, V, GG, 1, false>), gr, bl, 0, s, a);                     \
-  }
-#define TRS_CASE(GG)                                                          \
-  if (c.g == GG) {                                                            \
-    if (net == TRS_NET_FM) TRS_PS(TRS_NET_FM, 4, GG) else TRS_PS(TRS_NET_LINEAR, 4, GG) \
-    TRS_CHECK_LAUNCH("pair_scores_kernel");                                   \
-    return TRS_OK;                                                            \
-  }
-  TRS_CASE(8)
-  TRS_CASE(16)
-  TRS_CASE(32)
-  TRS_CASE(64)
-#undef TRS_CASE
-#undef TRS_PS
-  return 1;
+  return for_whole_row_shape(c, [&](auto V, auto G, auto K) {
+    constexpr int VV = V(), GG = G();
+    auto launch = [&](auto NETV) {
+      constexpr int NT = NETV();
+      const bool full = VV * GG == a.T.D;
+      if (full && ntm == 1) hipLaunchKernelGGL((pair_scores_kernel<NT, VV, GG, 1, true, 1>), gr, bl, 0, s, a);
+      else if (full && ntm == 2) hipLaunchKernelGGL((pair_scores_kernel<NT, VV, GG, 1, true, 2>), gr, bl, 0, s, a);
+      else if (full && ntm == 3) hipLaunchKernelGGL((pair_scores_kernel<NT, VV, GG, 1, true, 3>), gr, bl, 0, s, a);
+      else if (full) hipLaunchKernelGGL((pair_scores_kernel<NT, VV, GG, 1, true>), gr, bl, 0, s, a);
+      else hipLaunchKernelGGL((pair_scores_kernel<NT, VV, GG, 1, false>), gr, bl, 0, s, a);
+    };
+    if (net == TRS_NET_FM) launch(std::integral_constant<int, TRS_NET_FM>{});
+    else launch(std::integral_constant<int, TRS_NET_LINEAR>{});
+    TRS_CHECK_LAUNCH("pair_scores_kernel");
+    return TRS_OK;
+  });
 }
 
 extern "C" int64_t trs_train_scratch_bytes(int64_t n_users, int64_t n_items, int64_t batch, int32_t D) {
@@ -1620,8 +1575,7 @@ extern "C" int trs_train_steps_sgd(const trs_train_args* args, void* stream) {
   const trs_opt* opt = args->opt;
   const trs_meta_stage* meta = args->meta;
   void** events = args->events;
-  TRS_REQUIRE(net == TRS_NET_LINEAR || net == TRS_NET_FM, "trs_train_steps_sgd: bad net");
-  TRS_REQUIRE(tables && tables->M >= 0 && tables->M <= TRS_MAX_META, "trs_train_steps_sgd: bad M");
+  TRS_TRY(trs_check_net("trs_train_steps_sgd", net, tables));
   TRS_REQUIRE((tables->M > 0) == (meta != nullptr), "trs_train_steps_sgd: metadata tables need the metadata staging");
   TRS_REQUIRE(tables->user && tables->item && tables->user_lin && tables->item_lin, "trs_train_steps_sgd: NULL table");
   TRS_REQUIRE(batch > 0 && batch < ((int64_t)1 << 30) && n_steps >= 0, "trs_train_steps_sgd: bad batch / n_steps");

@@ -79,12 +79,9 @@ extern "C" int trs_batch_prepare(const int32_t* stream_user_dev, const int32_t* 
                                  const int32_t* item_meta_dev, int32_t M, int32_t* user_out, int32_t* pos_out,
                                  int32_t* neg_out, int32_t* pos_meta_out, int32_t* neg_meta_out,
                                  const trs_sampler* sampler, void* stream) {
-  const int64_t kn = sampler && sampler->k_neg > 1 ? sampler->k_neg : 1;
-  TRS_REQUIRE(N > 0 && t0 >= 0 && B >= 0 && t0 + B <= N * kn, "trs_batch_prepare: slice [%lld,%lld) outside [0,%lld)",
-              (long long)t0, (long long)(t0 + B), (long long)(N * kn));
-  TRS_REQUIRE(!sampler || (sampler->k_neg >= 1 && (!sampler->popularity || (sampler->pop_items && sampler->pop_n > 0)) &&
-                           ((sampler->seen_off == nullptr) == (sampler->seen_items == nullptr))),
-              "trs_batch_prepare: bad sampler options");
+  int64_t kn;
+  TRS_TRY(trs_check_slice("trs_batch_prepare", N, t0, B, sampler, kn));
+  TRS_TRY(trs_check_sampler("trs_batch_prepare", sampler));
   TRS_REQUIRE(M >= 0 && M <= TRS_MAX_META, "trs_batch_prepare: bad M");
   if (B == 0) return TRS_OK;
   TRS_REQUIRE(stream_user_dev && stream_item_dev, "trs_batch_prepare: stream is NULL");

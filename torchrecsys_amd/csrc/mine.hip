@@ -18,8 +18,6 @@ using namespace trs;
 
 namespace {
 
-constexpr uint64_t MINE_KEY_STEP = 0xD1B54A32D192ED03ull;  // candidate j draws under seed + j * this (mod 2^64)
-
 struct MineArgs {
   const int32_t* su;
   const int32_t* si;
@@ -35,13 +33,6 @@ struct MineArgs {
   int Kc;   // candidates per triple, 1..64
   int top;  // the negative is the candidate of rank mulhi64(x, top)
 };
-
-template <int G>
-__device__ __forceinline__ int group_sum_i(int v) {
-#pragma unroll
-  for (int o = G >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 template <int NET, int VEC, int G, int K, bool FULL, bool NT>
 __global__ __launch_bounds__(TRS_BLOCK) void mine_kernel(const MineArgs a) {
@@ -89,8 +80,8 @@ __global__ __launch_bounds__(TRS_BLOCK) void mine_kernel(const MineArgs a) {
       jm = jm < Kc ? jm : Kc - 1;  // past the last candidate: draw it again (its score is not used)
       const int32_t cand =
           bad_i ? 0
-                : (int32_t)trs_sample_neg_opt(a.seed + (uint64_t)jm * MINE_KEY_STEP, ctr, (int64_t)u, (int64_t)i,
-                                              a.n_items, a.S);
+                : (int32_t)trs_sample_neg_opt(a.seed + (uint64_t)jm * TRS_CANDIDATE_KEY_STEP, ctr, (int64_t)u,
+                                              (int64_t)i, a.n_items, a.S);
       float z[C];
       int32_t cid[C];
 #pragma unroll
@@ -123,7 +114,7 @@ __global__ __launch_bounds__(TRS_BLOCK) void mine_kernel(const MineArgs a) {
     int chosen = (int)(0xFFFFFFFFu - (uint32_t)best_key);
     int32_t neg = best_c;
     if (ranked) {
-      const trs_u4 rr = trs_philox4x32_10(ctr, a.seed + (uint64_t)Kc * MINE_KEY_STEP);
+      const trs_u4 rr = trs_philox4x32_10(ctr, a.seed + (uint64_t)Kc * TRS_CANDIDATE_KEY_STEP);
       const int r = (int)trs_mulhi64(((uint64_t)rr.y << 32) | (uint64_t)rr.x, (uint64_t)a.top);
       int cnt[SL];
 #pragma unroll
@@ -144,10 +135,10 @@ __global__ __launch_bounds__(TRS_BLOCK) void mine_kernel(const MineArgs a) {
         const int j2 = s2 * G + lig;
         if (j2 < Kc && cnt[s2] == r) found = j2;
       }
-      chosen = group_sum_i<G>(found);
+      chosen = trs_group_sum_i<G>(found);
       neg = bad_i ? 0
-                  : (int32_t)trs_sample_neg_opt(a.seed + (uint64_t)chosen * MINE_KEY_STEP, ctr, (int64_t)u, (int64_t)i,
-                                                a.n_items, a.S);
+                  : (int32_t)trs_sample_neg_opt(a.seed + (uint64_t)chosen * TRS_CANDIDATE_KEY_STEP, ctr, (int64_t)u,
+                                                (int64_t)i, a.n_items, a.S);
     }
 
     if (valid && lig == 0) {
@@ -170,52 +161,23 @@ __global__ __launch_bounds__(TRS_BLOCK) void mine_kernel(const MineArgs a) {
 template <int NET>
 int launch_mine(const MineArgs& a, hipStream_t s) {
   RowCfg c;
-  if (!pick_row_cfg(a.T.D, c)) {
-    trs_set_error("trs_batch_prepare_mined: unsupported n_factors D=%d (need 1..1024; D %% 4 != 0 only up to 256)",
-                  a.T.D);
-    return TRS_E_ARG;
-  }
+  TRS_TRY(row_cfg_for("trs_batch_prepare_mined", a.T.D, c));
   const int tpw = TRS_WAVE / c.g;
   const int64_t waves = (a.B + tpw - 1) / tpw;
-  const int grid = trs_grid(waves, TRS_BLOCK / TRS_WAVE);
+  const dim3 gr(trs_grid(waves, TRS_BLOCK / TRS_WAVE)), bl(TRS_BLOCK);
   // whole rows in one 16-byte lane group: unmasked loads; user rows nontemporal when the user table is far beyond the
   // Infinity Cache (they are read once per launch), as the scoring pass does (trs_launch_pair_scores)
-  const bool full = c.vec == 4 && c.k == 1 && c.g >= 8 && c.vec * c.g == a.T.D;
+  const bool full = row_shape_is_whole(c.vec, c.g, c.k) && c.vec * c.g == a.T.D;
   const bool nt = full && (int64_t)a.T.n_users * a.T.D * 4 > ((int64_t)512 << 20);
-#define TRS_LAUNCH(V, GG, KK, FU, NTV)                                                                         \
-  {                                                                                                            \
-    hipLaunchKernelGGL((mine_kernel<NET, V, GG, KK, FU, NTV>), dim3(grid), dim3(TRS_BLOCK), 0, s, a);          \
-    TRS_CHECK_LAUNCH("mine_kernel");                                                                           \
-    return TRS_OK;                                                                                             \
-  }
-#define TRS_CASE(V, GG, KK) \
-  if (c.vec == V && c.g == GG && c.k == KK && !full) TRS_LAUNCH(V, GG, KK, false, false)
-#define TRS_CASE_FULL(GG)                                       \
-  if (full && c.g == GG) {                                      \
-    if (nt) TRS_LAUNCH(4, GG, 1, true, true)                    \
-    TRS_LAUNCH(4, GG, 1, true, false)                           \
-  }
-  TRS_CASE_FULL(8)
-  TRS_CASE_FULL(16)
-  TRS_CASE_FULL(32)
-  TRS_CASE_FULL(64)
-  TRS_CASE(4, 2, 1)
-  TRS_CASE(4, 4, 1)
-  TRS_CASE(4, 8, 1)
-  TRS_CASE(4, 16, 1)
-  TRS_CASE(4, 32, 1)
-  TRS_CASE(4, 64, 1)
-  TRS_CASE(4, 64, 2)
-  TRS_CASE(4, 64, 4)
-  TRS_CASE(1, 4, 1)
-  TRS_CASE(1, 16, 1)
-  TRS_CASE(1, 64, 1)
-  TRS_CASE(1, 64, 4)
-#undef TRS_CASE_FULL
-#undef TRS_CASE
-#undef TRS_LAUNCH
-  trs_set_error("trs_batch_prepare_mined: internal: no kernel for D=%d", a.T.D);
-  return TRS_E_ARG;
+  return for_row_shape(c, [&](auto V, auto G, auto K) {
+    if constexpr (row_shape_is_whole(V(), G(), K())) {  // (the FULL kernels exist for these shapes only)
+      if (nt) hipLaunchKernelGGL((mine_kernel<NET, V(), G(), K(), true, true>), gr, bl, 0, s, a);
+      else if (full) hipLaunchKernelGGL((mine_kernel<NET, V(), G(), K(), true, false>), gr, bl, 0, s, a);
+    }
+    if (!full) hipLaunchKernelGGL((mine_kernel<NET, V(), G(), K(), false, false>), gr, bl, 0, s, a);
+    TRS_CHECK_LAUNCH("mine_kernel");
+    return TRS_OK;
+  });
 }
 
 }  // namespace
@@ -228,33 +190,19 @@ extern "C" int trs_batch_prepare_mined(const int32_t* stream_user_dev, const int
                                        const trs_sampler* sampler, int net, const trs_tables* tables,
                                        int32_t candidates, int32_t top, int32_t* chosen_out, void* stream) {
   const char* who = "trs_batch_prepare_mined";
-  TRS_REQUIRE(tables != nullptr, "%s: tables is NULL", who);
-  TRS_REQUIRE(net == TRS_NET_LINEAR || net == TRS_NET_FM,
-              "%s: net must be TRS_NET_LINEAR or TRS_NET_FM (a candidate's MLP score needs the whole network)", who);
+  TRS_TRY(trs_check_tables(who, net, tables));
   TRS_REQUIRE(candidates >= 1 && candidates <= 64, "%s: candidates=%d outside 1..64", who, candidates);
   TRS_REQUIRE(top >= 1 && top <= candidates, "%s: top=%d outside 1..candidates=%d", who, top, candidates);
   TRS_REQUIRE(neg_static_dev == nullptr, "%s: static negatives cannot be mined (neg_static must be NULL)", who);
-  TRS_REQUIRE(M >= 0 && M <= TRS_MAX_META && M == tables->M, "%s: M=%d does not match the tables' M=%d (0..%d)", who, M,
-              tables->M, TRS_MAX_META);
+  TRS_REQUIRE(M == tables->M, "%s: M=%d does not match the tables' M=%d", who, M, tables->M);
   TRS_REQUIRE(M == 0 || (item_meta_dev && pos_meta_out && neg_meta_out),
               "%s: M=%d needs item_meta and metadata outputs", who, M);
   RowCfg cfg;
-  TRS_REQUIRE(pick_row_cfg(tables->D, cfg),
-              "%s: unsupported n_factors D=%d (need 1..1024; D %% 4 != 0 only up to 256)", who, tables->D);
-  TRS_REQUIRE(tables->user && tables->item && tables->user_lin && tables->item_lin,
-              "%s: a user/item table or its 1-wide table is NULL", who);
-  TRS_REQUIRE(tables->n_users > 0 && n_items >= 2 && n_items <= tables->n_items,
-              "%s: needs n_users > 0 and 2 <= n_items <= the item table's rows", who);
-  for (int m = 0; m < M; ++m) {
-    TRS_REQUIRE(tables->meta[m] && tables->n_meta[m] > 0, "%s: metadata table %d is NULL/empty", who, m);
-    if (net == TRS_NET_FM) TRS_REQUIRE(tables->meta_lin[m], "%s: linear_metadata table %d is NULL", who, m);
-  }
-  const int64_t kn = sampler && sampler->k_neg > 1 ? sampler->k_neg : 1;
-  TRS_REQUIRE(N > 0 && t0 >= 0 && B >= 0 && t0 + B <= N * kn, "%s: slice [%lld,%lld) outside [0,%lld)", who,
-              (long long)t0, (long long)(t0 + B), (long long)(N * kn));
-  TRS_REQUIRE(!sampler || (sampler->k_neg >= 1 && (!sampler->popularity || (sampler->pop_items && sampler->pop_n > 0)) &&
-                           ((sampler->seen_off == nullptr) == (sampler->seen_items == nullptr))),
-              "%s: bad sampler options", who);
+  TRS_TRY(row_cfg_for(who, tables->D, cfg));
+  TRS_REQUIRE(n_items >= 2 && n_items <= tables->n_items, "%s: needs 2 <= n_items <= the item table's rows", who);
+  int64_t kn;
+  TRS_TRY(trs_check_slice(who, N, t0, B, sampler, kn));
+  TRS_TRY(trs_check_sampler(who, sampler));
   if (B == 0) return TRS_OK;
   TRS_REQUIRE(stream_user_dev && stream_item_dev, "%s: stream is NULL", who);
   TRS_REQUIRE(user_out && pos_out && neg_out, "%s: outputs are NULL", who);

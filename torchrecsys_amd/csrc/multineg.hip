@@ -30,8 +30,6 @@ namespace {
 #define MULTI_ROW_VGPRS 16
 #endif
 
-constexpr uint64_t MULTI_KEY_STEP = 0xD1B54A32D192ED03ull;  // candidate j draws under seed + j * this (mine.hip's)
-
 struct PrepMultiArgs {
   const int32_t* su;
   const int32_t* si;
@@ -59,8 +57,8 @@ __global__ __launch_bounds__(TRS_BLOCK) void prepare_multi_kernel(const PrepMult
     if (a.S.max_tries != 0 && (uint64_t)(int64_t)i >= (uint64_t)a.n_items)
       c = 0;  // (reported by the scorer; the option paths index tables by the ids)
     else
-      c = (int32_t)trs_sample_neg_opt(a.seed + (uint64_t)j * MULTI_KEY_STEP, a.offset + (uint64_t)t, (int64_t)u,
-                                      (int64_t)i, a.n_items, a.S);
+      c = (int32_t)trs_sample_neg_opt(a.seed + (uint64_t)j * TRS_CANDIDATE_KEY_STEP, a.offset + (uint64_t)t,
+                                      (int64_t)u, (int64_t)i, a.n_items, a.S);
     a.items[(1 + j) * a.B + t] = c;
     if (j == 0) {
       a.user[t] = u;
@@ -93,13 +91,6 @@ struct MultiArgs {
   float* grad_lin;   // (F, B)
   int32_t* err;
 };
-
-template <int G>
-__device__ __forceinline__ int group_or(int v) {
-#pragma unroll
-  for (int o = G >> 1; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
-  return v;
-}
 
 // The forward part of one round: the ids of candidates r0 .. r0 + C - 1 (lane c of the group reads candidate r0 + c's,
 // a shuffle hands them round) and their C independent passes.
@@ -169,7 +160,7 @@ __global__ __launch_bounds__(TRS_BLOCK) void multineg_kernel(const MultiArgs a) 
       for (int m = 0; m < M; ++m)
         if ((uint64_t)(int64_t)a.meta[e * M + m] >= (uint64_t)T.n_meta[m]) bad = 1;
     }
-    bad = group_or<G>(bad);
+    bad = trs_group_or<G>(bad);
     if (valid && bad && lig == 0 && a.err) atomicOr(a.err, 1);
     const bool live = valid && !bad;
 
@@ -391,38 +382,16 @@ __global__ __launch_bounds__(TRS_BLOCK) void multineg_kernel(const MultiArgs a) 
 template <int NET, bool SM>
 int launch_multi(const MultiArgs& a, hipStream_t s) {
   RowCfg c;
-  if (!pick_row_cfg(a.T.D, c)) {
-    trs_set_error("trs_score_multi_fwd_bwd: unsupported n_factors D=%d (need 1..1024; D %% 4 != 0 only up to 256)",
-                  a.T.D);
-    return TRS_E_ARG;
-  }
+  TRS_TRY(row_cfg_for("trs_score_multi_fwd_bwd", a.T.D, c));
   const int tpw = TRS_WAVE / c.g;
   const int64_t waves = (a.B + tpw - 1) / tpw;
-  const int grid = trs_grid(waves, TRS_BLOCK / TRS_WAVE);
-#define TRS_CASE(V, GG, KK)                                                                              \
-  if (c.vec == V && c.g == GG && c.k == KK) {                                                            \
-    if (a.T.M > 0)                                                                                       \
-      hipLaunchKernelGGL((multineg_kernel<NET, V, GG, KK, SM, true>), dim3(grid), dim3(TRS_BLOCK), 0, s, a);  \
-    else                                                                                                 \
-      hipLaunchKernelGGL((multineg_kernel<NET, V, GG, KK, SM, false>), dim3(grid), dim3(TRS_BLOCK), 0, s, a); \
-    TRS_CHECK_LAUNCH("multineg_kernel");                                                                 \
-    return TRS_OK;                                                                                       \
-  }
-  TRS_CASE(4, 2, 1)
-  TRS_CASE(4, 4, 1)
-  TRS_CASE(4, 8, 1)
-  TRS_CASE(4, 16, 1)
-  TRS_CASE(4, 32, 1)
-  TRS_CASE(4, 64, 1)
-  TRS_CASE(4, 64, 2)
-  TRS_CASE(4, 64, 4)
-  TRS_CASE(1, 4, 1)
-  TRS_CASE(1, 16, 1)
-  TRS_CASE(1, 64, 1)
-  TRS_CASE(1, 64, 4)
-#undef TRS_CASE
-  trs_set_error("trs_score_multi_fwd_bwd: internal: no kernel for D=%d", a.T.D);
-  return TRS_E_ARG;
+  const dim3 gr(trs_grid(waves, TRS_BLOCK / TRS_WAVE)), bl(TRS_BLOCK);
+  return for_row_shape(c, [&](auto V, auto G, auto K) {
+    if (a.T.M > 0) hipLaunchKernelGGL((multineg_kernel<NET, V(), G(), K(), SM, true>), gr, bl, 0, s, a);
+    else hipLaunchKernelGGL((multineg_kernel<NET, V(), G(), K(), SM, false>), gr, bl, 0, s, a);
+    TRS_CHECK_LAUNCH("multineg_kernel");
+    return TRS_OK;
+  });
 }
 
 }  // namespace
@@ -437,12 +406,9 @@ extern "C" int trs_batch_prepare_multi(const int32_t* stream_user_dev, const int
   TRS_REQUIRE(neg_static_dev == nullptr, "%s: no static negatives (neg_static must be NULL)", who);
   TRS_REQUIRE(M >= 0 && M <= TRS_MAX_META, "%s: M=%d outside 0..%d", who, M, TRS_MAX_META);
   TRS_REQUIRE(M == 0 || (item_meta_dev && meta_out), "%s: M=%d needs item_meta and the metadata output", who, M);
-  const int64_t kn = sampler && sampler->k_neg > 1 ? sampler->k_neg : 1;
-  TRS_REQUIRE(N > 0 && t0 >= 0 && B >= 0 && t0 + B <= N * kn, "%s: slice [%lld,%lld) outside [0,%lld)", who,
-              (long long)t0, (long long)(t0 + B), (long long)(N * kn));
-  TRS_REQUIRE(!sampler || (sampler->k_neg >= 1 && (!sampler->popularity || (sampler->pop_items && sampler->pop_n > 0)) &&
-                           ((sampler->seen_off == nullptr) == (sampler->seen_items == nullptr))),
-              "%s: bad sampler options", who);
+  int64_t kn;
+  TRS_TRY(trs_check_slice(who, N, t0, B, sampler, kn));
+  TRS_TRY(trs_check_sampler(who, sampler));
   TRS_REQUIRE(n_items >= 2, "%s: dynamic sampling needs n_items >= 2", who);
   if (B == 0) return TRS_OK;
   TRS_REQUIRE(stream_user_dev && stream_item_dev, "%s: stream is NULL", who);
@@ -477,23 +443,13 @@ extern "C" int trs_score_multi_fwd_bwd(int net, const trs_tables* tables, const 
                                        int32_t* auc_count_dev, float* grad_rows_dev, float* grad_lin_dev,
                                        int32_t* err_flag_dev, void* stream) {
   const char* who = "trs_score_multi_fwd_bwd";
-  TRS_REQUIRE(tables != nullptr, "%s: tables is NULL", who);
-  TRS_REQUIRE(net == TRS_NET_LINEAR || net == TRS_NET_FM, "%s: net must be TRS_NET_LINEAR or TRS_NET_FM", who);
+  TRS_TRY(trs_check_tables(who, net, tables));
   TRS_REQUIRE(K >= 1 && K <= 64, "%s: K=%d outside 1..64", who, K);
   TRS_REQUIRE(loss == TRS_LOSS_HINGE || loss == TRS_LOSS_BPR || loss == TRS_LOSS_SAMPLED_SOFTMAX,
               "%s: unknown loss id %d", who, loss);
-  TRS_REQUIRE(M >= 0 && M <= TRS_MAX_META && M == tables->M, "%s: M=%d does not match the tables' M=%d (0..%d)", who, M,
-              tables->M, TRS_MAX_META);
+  TRS_REQUIRE(M == tables->M, "%s: M=%d does not match the tables' M=%d", who, M, tables->M);
   RowCfg cfg;
-  TRS_REQUIRE(pick_row_cfg(tables->D, cfg),
-              "%s: unsupported n_factors D=%d (need 1..1024; D %% 4 != 0 only up to 256)", who, tables->D);
-  TRS_REQUIRE(tables->user && tables->item && tables->user_lin && tables->item_lin,
-              "%s: a user/item table or its 1-wide table is NULL", who);
-  TRS_REQUIRE(tables->n_users > 0 && tables->n_items > 0, "%s: empty user/item table", who);
-  for (int m = 0; m < M; ++m) {
-    TRS_REQUIRE(tables->meta[m] && tables->n_meta[m] > 0, "%s: metadata table %d is NULL/empty", who, m);
-    if (net == TRS_NET_FM) TRS_REQUIRE(tables->meta_lin[m], "%s: linear_metadata table %d is NULL", who, m);
-  }
+  TRS_TRY(row_cfg_for(who, tables->D, cfg));
   TRS_REQUIRE(tau > 0.f && tau <= 3.0e38f, "%s: temperature must be positive and finite", who);
   TRS_REQUIRE(loss_sum_dev, "%s: loss_sum is NULL", who);
   TRS_REQUIRE((grad_rows_dev == nullptr) == (grad_lin_dev == nullptr),

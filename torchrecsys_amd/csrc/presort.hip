@@ -1170,15 +1170,12 @@ extern "C" int trs_epoch_presort(const int32_t* stream_ui_dev, const int32_t* ne
                                  int32_t* err_flag_dev, void** sorted_keys_out, void** sorted_vals_out,
                                  uint8_t* item_dup_flags_out_dev, const trs_sampler* sampler, void* stream) {
   TRS_REQUIRE(n_batches > 0 && batch > 0 && n_users > 0 && n_items > 0, "trs_epoch_presort: bad sizes");
-  TRS_REQUIRE(!sampler || (sampler->k_neg >= 1 && (!sampler->popularity || (sampler->pop_items && sampler->pop_n > 0)) &&
-                           ((sampler->seen_off == nullptr) == (sampler->seen_items == nullptr))),
-              "trs_epoch_presort: bad sampler options");
+  TRS_TRY(trs_check_sampler("trs_epoch_presort", sampler));
   TRS_REQUIRE(user_dev && pos_dev && neg_dev && keys_dev && vals_dev && temp_dev, "trs_epoch_presort: NULL buffer");
   TRS_REQUIRE(sorted_keys_out && sorted_vals_out, "trs_epoch_presort: NULL output");
   const int64_t n_pos = n_batches * batch;
-  const int64_t kn = sampler && sampler->k_neg > 1 ? sampler->k_neg : 1;
-  if (stream_ui_dev)
-    TRS_REQUIRE(N > 0 && first_pos >= 0 && first_pos + n_pos <= N * kn, "trs_epoch_presort: slice outside the stream");
+  int64_t kn = 1;
+  if (stream_ui_dev) TRS_TRY(trs_check_slice("trs_epoch_presort", N, first_pos, n_pos, sampler, kn));
   EpochArgs a = {};
   a.S = trs_sampler_args(sampler);
   a.sui = (const int2*)stream_ui_dev;
@@ -1275,10 +1272,7 @@ extern "C" int trs_epoch_flags_ordered(const int32_t* stream_ui_dev, const int32
                                        int32_t* pos_dev, int32_t* neg_dev, uint8_t* user_dup_flags_out_dev,
                                        uint8_t* item_dup_flags_out_dev, int32_t* n_flagged_out_dev,
                                        int32_t* err_flag_dev, const trs_sampler* sampler, void* stream) {
-  const int64_t kn = sampler && sampler->k_neg > 1 ? sampler->k_neg : 1;
-  TRS_REQUIRE(!sampler || (sampler->k_neg >= 1 && (!sampler->popularity || (sampler->pop_items && sampler->pop_n > 0)) &&
-                           ((sampler->seen_off == nullptr) == (sampler->seen_items == nullptr))),
-              "trs_epoch_flags: bad sampler options");
+  TRS_TRY(trs_check_sampler("trs_epoch_flags", sampler));
   TRS_REQUIRE(batch <= (int64_t)FLAG_THREADS * FLAG_U * FLAG_ROUNDS * FLAG_MAX_GROUPS,
               "trs_epoch_flags: batch %lld exceeds %d (one workgroup per batch keeps a bit per reference in registers)",
               (long long)batch, FLAG_THREADS * FLAG_U * FLAG_ROUNDS * FLAG_MAX_GROUPS);
@@ -1286,9 +1280,8 @@ extern "C" int trs_epoch_flags_ordered(const int32_t* stream_ui_dev, const int32
                   n_users < ((int64_t)1 << 31) && n_items < ((int64_t)1 << 31), "trs_epoch_flags: bad sizes");
   TRS_REQUIRE(user_dev && pos_dev && neg_dev && user_dup_flags_out_dev && item_dup_flags_out_dev,
               "trs_epoch_flags: NULL buffer");
-  if (stream_ui_dev)
-    TRS_REQUIRE(N > 0 && first_pos >= 0 && first_pos + n_batches * batch <= N * kn,
-                "trs_epoch_flags: slice outside the stream");
+  int64_t kn = 1;
+  if (stream_ui_dev) TRS_TRY(trs_check_slice("trs_epoch_flags", N, first_pos, n_batches * batch, sampler, kn));
   FlagArgs a = {};
   a.sui = (const int2*)stream_ui_dev;
   a.neg_static = neg_static_dev;
@@ -1499,42 +1492,27 @@ int trs_launch_sorted_item_update(const trs_tables* tables, const void* keys_ste
   a.stamp = stamp;
   a.ustage = ustage;
   RowCfg c;
-  if (!pick_row_cfg(tables->D, c)) {
-    trs_set_error("unsupported n_factors D=%d", tables->D);
-    return TRS_E_ARG;
-  }
+  TRS_TRY(row_cfg_for("trs_launch_sorted_item_update", tables->D, c));
   const int tpw = TRS_WAVE / c.g;
   const dim3 gr(trs_grid((2 * batch + tpw - 1) / tpw, TRS_BLOCK / TRS_WAVE)), bl(TRS_BLOCK);
   const dim3 gs(trs_grid((2 * batch + RUN_CHUNK - 1) / RUN_CHUNK, 1));  // staged form: one 64-reference chunk per workgroup
-#define TRS_SL(V, GG, KK, FULL)                                                                                      \
-  {                                                                                                                  \
-    if (key_bytes == 4 && ustage) hipLaunchKernelGGL((sorted_item_update_staged_kernel<uint32_t, V, GG, KK, FULL>), gs, bl, 0, s, a); \
-    else if (key_bytes == 4) hipLaunchKernelGGL((sorted_item_update_kernel<uint32_t, V, GG, KK, FULL, false>), gr, bl, 0, s, a);     \
-    else if (ustage) hipLaunchKernelGGL((sorted_item_update_staged_kernel<uint64_t, V, GG, KK, FULL>), gs, bl, 0, s, a);             \
-    else hipLaunchKernelGGL((sorted_item_update_kernel<uint64_t, V, GG, KK, FULL, false>), gr, bl, 0, s, a);                         \
-  }
-#define TRS_CASE(V, GG, KK)                                                                  \
-  if (c.vec == V && c.g == GG && c.k == KK) {                                                \
-    if (V * GG * KK == tables->D) TRS_SL(V, GG, KK, true) else TRS_SL(V, GG, KK, false)      \
-    TRS_CHECK_LAUNCH("sorted_item_update_kernel");                                           \
-    return TRS_OK;                                                                           \
-  }
-  TRS_CASE(4, 2, 1)
-  TRS_CASE(4, 4, 1)
-  TRS_CASE(4, 8, 1)
-  TRS_CASE(4, 16, 1)
-  TRS_CASE(4, 32, 1)
-  TRS_CASE(4, 64, 1)
-  TRS_CASE(4, 64, 2)
-  TRS_CASE(4, 64, 4)
-  TRS_CASE(1, 4, 1)
-  TRS_CASE(1, 16, 1)
-  TRS_CASE(1, 64, 1)
-  TRS_CASE(1, 64, 4)
-#undef TRS_CASE
-#undef TRS_SL
-  trs_set_error("internal: no kernel for D=%d", tables->D);
-  return TRS_E_ARG;
+  return for_row_shape(c, [&](auto V, auto G, auto K) {
+    constexpr int VV = V(), GG = G(), KK = K();
+    auto launch = [&](auto FULL) {
+      if (key_bytes == 4 && ustage)
+        hipLaunchKernelGGL((sorted_item_update_staged_kernel<uint32_t, VV, GG, KK, FULL()>), gs, bl, 0, s, a);
+      else if (key_bytes == 4)
+        hipLaunchKernelGGL((sorted_item_update_kernel<uint32_t, VV, GG, KK, FULL(), false>), gr, bl, 0, s, a);
+      else if (ustage)
+        hipLaunchKernelGGL((sorted_item_update_staged_kernel<uint64_t, VV, GG, KK, FULL()>), gs, bl, 0, s, a);
+      else
+        hipLaunchKernelGGL((sorted_item_update_kernel<uint64_t, VV, GG, KK, FULL(), false>), gr, bl, 0, s, a);
+    };
+    if (VV * GG * KK == tables->D) launch(std::true_type{});
+    else launch(std::false_type{});
+    TRS_CHECK_LAUNCH("sorted_item_update_kernel");
+    return TRS_OK;
+  });
 }
 
 int trs_item_bits_for(int64_t n_items) { return bits_for(n_items); }
@@ -1562,59 +1540,38 @@ int trs_launch_sorted_meta_update(const trs_tables* tables, int m, float* lin_or
   const int kind = opt ? opt->kind : OPT_SGD;
   if (opt) a.o = *opt;
   RowCfg c;
-  if (!pick_row_cfg(tables->D, c)) {
-    trs_set_error("unsupported n_factors D=%d", tables->D);
-    return TRS_E_ARG;
-  }
+  TRS_TRY(row_cfg_for("trs_launch_sorted_meta_update", tables->D, c));
   const dim3 gs(trs_grid((2 * batch + RUN_CHUNK - 1) / RUN_CHUNK, 1)), bl(TRS_BLOCK), gc(128);
   if (kind != OPT_SGD) {
     const trs_tables T = *tables;
-#define TRS_CASE(GG)                                                                                                  \
-  if (c.vec == 4 && c.g == GG && c.k == 1 && 4 * GG == tables->D) {                                                   \
-    if (kind == OPT_ADAM) {                                                                                           \
-      hipLaunchKernelGGL((sorted_item_update_staged_kernel<uint32_t, 4, GG, 1, true, OPT_ADAM>), gs, bl, 0, s, a);     \
-      hipLaunchKernelGGL((cut_rows_apply_kernel<4, GG, 1, true, OPT_ADAM>), gc, bl, 0, s, T, a.o, a.parity, a.tab,     \
-                         a.tab_lin);                                                                                  \
-    } else {                                                                                                          \
-      hipLaunchKernelGGL((sorted_item_update_staged_kernel<uint32_t, 4, GG, 1, true, OPT_ADAGRAD>), gs, bl, 0, s, a);  \
-      hipLaunchKernelGGL((cut_rows_apply_kernel<4, GG, 1, true, OPT_ADAGRAD>), gc, bl, 0, s, T, a.o, a.parity, a.tab,  \
-                         a.tab_lin);                                                                                  \
-    }                                                                                                                 \
-    TRS_CHECK_LAUNCH("sorted_item_update_staged_kernel");                                                             \
-    return TRS_OK;                                                                                                    \
-  }
-    TRS_CASE(8)
-    TRS_CASE(16)
-    TRS_CASE(32)
-    TRS_CASE(64)
-#undef TRS_CASE
+    const int rc = for_whole_row_shape(c, [&](auto V, auto G, auto K) {
+      constexpr int VV = V(), GG = G(), KK = K();
+      if (VV * GG != tables->D) return 1;
+      if (kind == OPT_ADAM) {
+        hipLaunchKernelGGL((sorted_item_update_staged_kernel<uint32_t, VV, GG, KK, true, OPT_ADAM>), gs, bl, 0, s, a);
+        hipLaunchKernelGGL((cut_rows_apply_kernel<VV, GG, KK, true, OPT_ADAM>), gc, bl, 0, s, T, a.o, a.parity, a.tab,
+                           a.tab_lin);
+      } else {
+        hipLaunchKernelGGL((sorted_item_update_staged_kernel<uint32_t, VV, GG, KK, true, OPT_ADAGRAD>), gs, bl, 0, s,
+                           a);
+        hipLaunchKernelGGL((cut_rows_apply_kernel<VV, GG, KK, true, OPT_ADAGRAD>), gc, bl, 0, s, T, a.o, a.parity,
+                           a.tab, a.tab_lin);
+      }
+      TRS_CHECK_LAUNCH("sorted_item_update_staged_kernel");
+      return TRS_OK;
+    });
+    if (rc <= 0) return rc;
     trs_set_error("adaptive rules on metadata columns need D in {32, 64, 128, 256} (got %d)", tables->D);
     return TRS_E_ARG;
   }
-#define TRS_CASE(V, GG, KK)                                                                                          \
-  if (c.vec == V && c.g == GG && c.k == KK) {                                                                        \
-    if (V * GG * KK == tables->D)                                                                                    \
-      hipLaunchKernelGGL((sorted_item_update_staged_kernel<uint32_t, V, GG, KK, true>), gs, bl, 0, s, a);            \
-    else                                                                                                             \
-      hipLaunchKernelGGL((sorted_item_update_staged_kernel<uint32_t, V, GG, KK, false>), gs, bl, 0, s, a);           \
-    TRS_CHECK_LAUNCH("sorted_item_update_staged_kernel");                                                            \
-    return TRS_OK;                                                                                                   \
-  }
-  TRS_CASE(4, 2, 1)
-  TRS_CASE(4, 4, 1)
-  TRS_CASE(4, 8, 1)
-  TRS_CASE(4, 16, 1)
-  TRS_CASE(4, 32, 1)
-  TRS_CASE(4, 64, 1)
-  TRS_CASE(4, 64, 2)
-  TRS_CASE(4, 64, 4)
-  TRS_CASE(1, 4, 1)
-  TRS_CASE(1, 16, 1)
-  TRS_CASE(1, 64, 1)
-  TRS_CASE(1, 64, 4)
-#undef TRS_CASE
-  trs_set_error("internal: no kernel for D=%d", tables->D);
-  return TRS_E_ARG;
+  return for_row_shape(c, [&](auto V, auto G, auto K) {
+    if (V() * G() * K() == tables->D)
+      hipLaunchKernelGGL((sorted_item_update_staged_kernel<uint32_t, V(), G(), K(), true>), gs, bl, 0, s, a);
+    else
+      hipLaunchKernelGGL((sorted_item_update_staged_kernel<uint32_t, V(), G(), K(), false>), gs, bl, 0, s, a);
+    TRS_CHECK_LAUNCH("sorted_item_update_staged_kernel");
+    return TRS_OK;
+  });
 }
 
 // Fused launch of the staged item update and the duplicated-user update (both with 32-bit keys).
@@ -1654,48 +1611,31 @@ int trs_launch_sorted_updates_fused(const trs_tables* tables, const void* keys_s
   ia.xpass = xpass;
   ia.fmsub = fmsub;
   RowCfg c;
-  if (!pick_row_cfg(tables->D, c)) {
-    trs_set_error("unsupported n_factors D=%d", tables->D);
-    return TRS_E_ARG;
-  }
+  TRS_TRY(row_cfg_for("trs_launch_sorted_updates_fused", tables->D, c));
   const int nu = trs_grid((batch + TRS_WAVE - 1) / TRS_WAVE, TRS_BLOCK / TRS_WAVE);
   const int ni = trs_grid((2 * batch + RUN_CHUNK - 1) / RUN_CHUNK, 1);
   const dim3 gr(nu + ni), bl(TRS_BLOCK), gc(64);
   const trs_tables T = *tables;
-#define TRS_FUSED(V, GG, KK, FULL)                                                                                \
-  {                                                                                                              \
-    if (kind == OPT_ADAM) {                                                                                      \
-      hipLaunchKernelGGL((sorted_updates_fused_kernel<V, GG, KK, FULL, OPT_ADAM>), gr, bl, 0, s, ia, ua, nu);     \
-      hipLaunchKernelGGL((cut_rows_apply_kernel<V, GG, KK, FULL, OPT_ADAM>), gc, bl, 0, s, T, ia.o, ia.parity, (float*)nullptr, (float*)nullptr); \
-    } else if (kind == OPT_ADAGRAD) {                                                                            \
-      hipLaunchKernelGGL((sorted_updates_fused_kernel<V, GG, KK, FULL, OPT_ADAGRAD>), gr, bl, 0, s, ia, ua, nu);  \
-      hipLaunchKernelGGL((cut_rows_apply_kernel<V, GG, KK, FULL, OPT_ADAGRAD>), gc, bl, 0, s, T, ia.o, ia.parity, (float*)nullptr, (float*)nullptr); \
-    } else {                                                                                                     \
-      hipLaunchKernelGGL((sorted_updates_fused_kernel<V, GG, KK, FULL>), gr, bl, 0, s, ia, ua, nu);               \
-    }                                                                                                            \
-  }
-#define TRS_CASE(V, GG, KK)                                                                                      \
-  if (c.vec == V && c.g == GG && c.k == KK) {                                                                    \
-    if (V * GG * KK == tables->D) TRS_FUSED(V, GG, KK, true) else TRS_FUSED(V, GG, KK, false)                     \
-    TRS_CHECK_LAUNCH("sorted_updates_fused_kernel");                                                             \
-    return TRS_OK;                                                                                               \
-  }
-  TRS_CASE(4, 2, 1)
-  TRS_CASE(4, 4, 1)
-  TRS_CASE(4, 8, 1)
-  TRS_CASE(4, 16, 1)
-  TRS_CASE(4, 32, 1)
-  TRS_CASE(4, 64, 1)
-  TRS_CASE(4, 64, 2)
-  TRS_CASE(4, 64, 4)
-  TRS_CASE(1, 4, 1)
-  TRS_CASE(1, 16, 1)
-  TRS_CASE(1, 64, 1)
-  TRS_CASE(1, 64, 4)
-#undef TRS_CASE
-#undef TRS_FUSED
-  trs_set_error("internal: no kernel for D=%d", tables->D);
-  return TRS_E_ARG;
+  return for_row_shape(c, [&](auto V, auto G, auto K) {
+    constexpr int VV = V(), GG = G(), KK = K();
+    auto launch = [&](auto FULL) {
+      if (kind == OPT_ADAM) {
+        hipLaunchKernelGGL((sorted_updates_fused_kernel<VV, GG, KK, FULL(), OPT_ADAM>), gr, bl, 0, s, ia, ua, nu);
+        hipLaunchKernelGGL((cut_rows_apply_kernel<VV, GG, KK, FULL(), OPT_ADAM>), gc, bl, 0, s, T, ia.o, ia.parity,
+                           (float*)nullptr, (float*)nullptr);
+      } else if (kind == OPT_ADAGRAD) {
+        hipLaunchKernelGGL((sorted_updates_fused_kernel<VV, GG, KK, FULL(), OPT_ADAGRAD>), gr, bl, 0, s, ia, ua, nu);
+        hipLaunchKernelGGL((cut_rows_apply_kernel<VV, GG, KK, FULL(), OPT_ADAGRAD>), gc, bl, 0, s, T, ia.o, ia.parity,
+                           (float*)nullptr, (float*)nullptr);
+      } else {
+        hipLaunchKernelGGL((sorted_updates_fused_kernel<VV, GG, KK, FULL()>), gr, bl, 0, s, ia, ua, nu);
+      }
+    };
+    if (VV * GG * KK == tables->D) launch(std::true_type{});
+    else launch(std::false_type{});
+    TRS_CHECK_LAUNCH("sorted_updates_fused_kernel");
+    return TRS_OK;
+  });
 }
 
 int trs_launch_sorted_user_dup_update(const trs_tables* tables, const void* ukeys_step, const void* uvals_step,
@@ -1712,36 +1652,19 @@ int trs_launch_sorted_user_dup_update(const trs_tables* tables, const void* ukey
   a.gz = gz;
   a.lr = lr;
   RowCfg c;
-  if (!pick_row_cfg(tables->D, c)) {
-    trs_set_error("unsupported n_factors D=%d", tables->D);
-    return TRS_E_ARG;
-  }
+  TRS_TRY(row_cfg_for("trs_launch_sorted_user_dup_update", tables->D, c));
   const dim3 gr(trs_grid((batch + TRS_WAVE - 1) / TRS_WAVE, TRS_BLOCK / TRS_WAVE)), bl(TRS_BLOCK);
-#define TRS_UL(V, GG, KK, FULL)                                                                                  \
-  {                                                                                                              \
-    if (key_bytes == 4) hipLaunchKernelGGL((sorted_user_dup_update_kernel<uint32_t, V, GG, KK, FULL>), gr, bl, 0, s, a); \
-    else hipLaunchKernelGGL((sorted_user_dup_update_kernel<uint64_t, V, GG, KK, FULL>), gr, bl, 0, s, a);         \
-  }
-#define TRS_CASE(V, GG, KK)                                                                  \
-  if (c.vec == V && c.g == GG && c.k == KK) {                                                \
-    if (V * GG * KK == tables->D) TRS_UL(V, GG, KK, true) else TRS_UL(V, GG, KK, false)      \
-    TRS_CHECK_LAUNCH("sorted_user_dup_update_kernel");                                       \
-    return TRS_OK;                                                                           \
-  }
-  TRS_CASE(4, 2, 1)
-  TRS_CASE(4, 4, 1)
-  TRS_CASE(4, 8, 1)
-  TRS_CASE(4, 16, 1)
-  TRS_CASE(4, 32, 1)
-  TRS_CASE(4, 64, 1)
-  TRS_CASE(4, 64, 2)
-  TRS_CASE(4, 64, 4)
-  TRS_CASE(1, 4, 1)
-  TRS_CASE(1, 16, 1)
-  TRS_CASE(1, 64, 1)
-  TRS_CASE(1, 64, 4)
-#undef TRS_CASE
-#undef TRS_UL
-  trs_set_error("internal: no kernel for D=%d", tables->D);
-  return TRS_E_ARG;
+  return for_row_shape(c, [&](auto V, auto G, auto K) {
+    constexpr int VV = V(), GG = G(), KK = K();
+    auto launch = [&](auto FULL) {
+      if (key_bytes == 4)
+        hipLaunchKernelGGL((sorted_user_dup_update_kernel<uint32_t, VV, GG, KK, FULL()>), gr, bl, 0, s, a);
+      else
+        hipLaunchKernelGGL((sorted_user_dup_update_kernel<uint64_t, VV, GG, KK, FULL()>), gr, bl, 0, s, a);
+    };
+    if (VV * GG * KK == tables->D) launch(std::true_type{});
+    else launch(std::false_type{});
+    TRS_CHECK_LAUNCH("sorted_user_dup_update_kernel");
+    return TRS_OK;
+  });
 }

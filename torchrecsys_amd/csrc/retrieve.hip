@@ -414,15 +414,8 @@ extern "C" int64_t trs_item_fold_bytes(int64_t n_items, int32_t D) {
 
 extern "C" int trs_item_fold(int net, const trs_tables* T, const int32_t* item_meta_dev, void* fold_dev,
                              int64_t fold_bytes, void* stream) {
-  TRS_REQUIRE(T != nullptr, "trs_item_fold: tables is NULL");
-  TRS_REQUIRE(net == TRS_NET_LINEAR || net == TRS_NET_FM, "trs_item_fold: net must be TRS_NET_LINEAR or TRS_NET_FM");
-  TRS_REQUIRE(T->item && T->item_lin && T->n_items > 0, "trs_item_fold: item table is NULL/empty");
-  TRS_REQUIRE(T->M >= 0 && T->M <= TRS_MAX_META, "trs_item_fold: M=%d outside 0..%d", T->M, TRS_MAX_META);
+  TRS_TRY(trs_check_tables("trs_item_fold", net, T, TRS_SKIP_USER | TRS_SKIP_META_ROWS));  // folds item-side rows only
   TRS_REQUIRE(T->M == 0 || item_meta_dev, "trs_item_fold: item_meta is NULL but M=%d", T->M);
-  for (int m = 0; m < T->M; ++m) {
-    TRS_REQUIRE(T->meta[m], "trs_item_fold: metadata table %d is NULL", m);
-    if (net == TRS_NET_FM) TRS_REQUIRE(T->meta_lin[m], "trs_item_fold: linear_metadata table %d is NULL", m);
-  }
   const int64_t need = trs_item_fold_bytes(T->n_items, T->D);
   TRS_REQUIRE(need > 0, "trs_item_fold: D=%d outside 1..%d", T->D, TRS_RETRIEVE_DMAX);
   TRS_REQUIRE(fold_dev && fold_bytes >= need, "trs_item_fold: fold buffer too small (%lld < %lld)",

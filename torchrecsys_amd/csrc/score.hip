@@ -3,20 +3,6 @@
 
 using namespace trs;
 
-static int check_tables(int net, const trs_tables* T, const char* who) {
-  TRS_REQUIRE(T != nullptr, "%s: tables is NULL", who);
-  TRS_REQUIRE(net == TRS_NET_LINEAR || net == TRS_NET_FM, "%s: net must be TRS_NET_LINEAR or TRS_NET_FM", who);
-  TRS_REQUIRE(T->M >= 0 && T->M <= TRS_MAX_META, "%s: M=%d outside 0..%d", who, T->M, TRS_MAX_META);
-  TRS_REQUIRE(T->user && T->item, "%s: user/item table is NULL", who);
-  TRS_REQUIRE(T->user_lin && T->item_lin, "%s: 1-wide user/item table (bias / linear term) is NULL", who);
-  TRS_REQUIRE(T->n_users > 0 && T->n_items > 0, "%s: empty user/item table", who);
-  for (int m = 0; m < T->M; ++m) {
-    TRS_REQUIRE(T->meta[m] && T->n_meta[m] > 0, "%s: metadata table %d is NULL/empty", who, m);
-    if (net == TRS_NET_FM) TRS_REQUIRE(T->meta_lin[m], "%s: linear_metadata table %d is NULL", who, m);
-  }
-  return TRS_OK;
-}
-
 static int check_batch(const trs_tables* T, const trs_batch* b, bool need_neg, const char* who) {
   TRS_REQUIRE(b != nullptr, "%s: batch is NULL", who);
   TRS_REQUIRE(b->B >= 0, "%s: negative batch size", who);
@@ -41,10 +27,8 @@ int trs_launch_pair_scores(int net, const trs::ScoreArgs* a, hipStream_t s);  //
 
 extern "C" int trs_score_forward(int net, const trs_tables* tables, const trs_batch* batch, float* pos_score_dev,
                                  float* neg_score_dev, void* stream) {
-  int rc = check_tables(net, tables, "trs_score_forward");
-  if (rc) return rc;
-  rc = check_batch(tables, batch, false, "trs_score_forward");
-  if (rc) return rc;
+  TRS_TRY(trs_check_tables("trs_score_forward", net, tables));
+  TRS_TRY(check_batch(tables, batch, false, "trs_score_forward"));
   TRS_REQUIRE(pos_score_dev, "trs_score_forward: pos_score is NULL");
   TRS_REQUIRE((batch->neg == nullptr) == (neg_score_dev == nullptr) || batch->B == 0,
               "trs_score_forward: neg ids and neg_score must both be given or both be NULL");
@@ -55,7 +39,7 @@ extern "C" int trs_score_forward(int net, const trs_tables* tables, const trs_ba
   a.neg_score = neg_score_dev;
   a.iota_user = -1;
   if (batch->B > 0) {  // no metadata, int32 ids, both passes: the software-pipelined form (fast_step.hip)
-    rc = trs_launch_pair_scores(net, &a, (hipStream_t)stream);
+    const int rc = trs_launch_pair_scores(net, &a, (hipStream_t)stream);
     if (rc <= 0) return rc;
   }
   return launch_net<0>(net, a, (hipStream_t)stream);
@@ -66,10 +50,8 @@ extern "C" int trs_score_fwd_bwd(int net, const trs_tables* tables, const trs_ba
                                  int32_t* auc_count_dev, float* grad_rows_dev, float* grad_lin_dev, int32_t loss,
                                  void* stream) {
   TRS_REQUIRE(loss == TRS_LOSS_HINGE || loss == TRS_LOSS_BPR, "trs_score_fwd_bwd: bad loss kind");
-  int rc = check_tables(net, tables, "trs_score_fwd_bwd");
-  if (rc) return rc;
-  rc = check_batch(tables, batch, true, "trs_score_fwd_bwd");
-  if (rc) return rc;
+  TRS_TRY(trs_check_tables("trs_score_fwd_bwd", net, tables));
+  TRS_TRY(check_batch(tables, batch, true, "trs_score_fwd_bwd"));
   TRS_REQUIRE(grad_rows_dev && grad_lin_dev, "trs_score_fwd_bwd: staging arrays are NULL");
   TRS_REQUIRE(loss_sum_dev, "trs_score_fwd_bwd: loss_sum is NULL");
   ScoreArgs a = {};
@@ -89,10 +71,8 @@ extern "C" int trs_score_fwd_bwd(int net, const trs_tables* tables, const trs_ba
 
 extern "C" int trs_score_backward(int net, const trs_tables* tables, const trs_batch* batch, const float* gpos_dev,
                                   const float* gneg_dev, float* grad_rows_dev, float* grad_lin_dev, void* stream) {
-  int rc = check_tables(net, tables, "trs_score_backward");
-  if (rc) return rc;
-  rc = check_batch(tables, batch, true, "trs_score_backward");
-  if (rc) return rc;
+  TRS_TRY(trs_check_tables("trs_score_backward", net, tables));
+  TRS_TRY(check_batch(tables, batch, true, "trs_score_backward"));
   TRS_REQUIRE(gpos_dev && gneg_dev, "trs_score_backward: upstream gradients are NULL");
   TRS_REQUIRE(grad_rows_dev && grad_lin_dev, "trs_score_backward: staging arrays are NULL");
   ScoreArgs a = {};
@@ -108,8 +88,7 @@ extern "C" int trs_score_backward(int net, const trs_tables* tables, const trs_b
 
 extern "C" int trs_score_all_items(int net, const trs_tables* tables, int64_t user_id, int64_t item0, int64_t n,
                                    const int32_t* item_meta_dev, float* score_out_dev, void* stream) {
-  int rc = check_tables(net, tables, "trs_score_all_items");
-  if (rc) return rc;
+  TRS_TRY(trs_check_tables("trs_score_all_items", net, tables));
   TRS_REQUIRE(user_id >= 0 && user_id < tables->n_users, "trs_score_all_items: user_id %lld out of range [0,%lld)",
               (long long)user_id, (long long)tables->n_users);
   TRS_REQUIRE(item0 >= 0 && n >= 0 && item0 + n <= tables->n_items,

@@ -12,6 +12,8 @@
 #include "trs_common.h"
 #include "opt_rows.h"
 
+#include <type_traits>
+
 namespace trs {
 
 template <int VEC>
@@ -440,7 +442,7 @@ __global__ __launch_bounds__(TRS_BLOCK) void score_kernel(const ScoreArgs a) {
 struct RowCfg {
   int vec, g, k;
 };
-static inline bool pick_row_cfg(int D, RowCfg& c) {
+constexpr bool pick_row_cfg(int D, RowCfg& c) {
   if (D < 1 || D > 1024) return false;
   if (D % 4 == 0) {
     const int chunks = D / 4;
@@ -464,40 +466,75 @@ static inline bool pick_row_cfg(int D, RowCfg& c) {
   else return false;  // odd D > 256 is not instantiated
   return true;
 }
+// pick_row_cfg for an entry point or launcher `who`: an unsupported width is an argument error
+static inline int row_cfg_for(const char* who, int D, RowCfg& c) {
+  TRS_REQUIRE(pick_row_cfg(D, c), "%s: unsupported n_factors D=%d (need 1..1024; D %% 4 != 0 only up to 256)", who, D);
+  return TRS_OK;
+}
+
+// THE table of row shapes (VEC, G, K): every shape pick_row_cfg returns, and so every shape a row kernel is
+// instantiated for.  It is written out here and nowhere else.
+#define TRS_ROW_SHAPES(X) \
+  X(4, 2, 1) X(4, 4, 1) X(4, 8, 1) X(4, 16, 1) X(4, 32, 1) X(4, 64, 1) X(4, 64, 2) X(4, 64, 4) \
+  X(1, 4, 1) X(1, 16, 1) X(1, 64, 1) X(1, 64, 4)
+
+// Whole-row shapes: 16-byte lanes, one chunk per lane, at least 8 lanes (D = 4 * G for G in 8..64 fills them exactly).
+constexpr bool row_shape_is_whole(int vec, int g, int k) { return vec == 4 && k == 1 && g >= 8; }
+
+// Maps a RowCfg to compile-time constants: calls f(integral_constant<int, VEC>, <int, G>, <int, K>) for the table's
+// matching entry and returns its result.  A launcher passes a generic lambda that holds what is its own (kernel,
+// further template choices, TRS_CHECK_LAUNCH).  WHOLE: only the whole-row entries exist (f is not instantiated for
+// the others) and any other shape returns 1 = "not handled here": the caller takes its general path.
+template <bool WHOLE, typename F>
+static inline int row_shape_dispatch(const RowCfg& c, F&& f) {
+#define TRS_ROW_CASE(V, G, K)                                      \
+  if constexpr (!WHOLE || row_shape_is_whole(V, G, K))             \
+    if (c.vec == V && c.g == G && c.k == K)                        \
+      return f(std::integral_constant<int, V>{}, std::integral_constant<int, G>{}, std::integral_constant<int, K>{});
+  TRS_ROW_SHAPES(TRS_ROW_CASE)
+#undef TRS_ROW_CASE
+  if (WHOLE) return 1;
+  trs_set_error("internal: no kernel for row shape (%d, %d, %d)", c.vec, c.g, c.k);  // unreachable: see below
+  return TRS_E_ARG;
+}
+template <typename F>
+static inline int for_row_shape(const RowCfg& c, F&& f) {
+  return row_shape_dispatch<false>(c, f);
+}
+template <typename F>
+static inline int for_whole_row_shape(const RowCfg& c, F&& f) {
+  return row_shape_dispatch<true>(c, f);
+}
+
+// The table is exhaustive: every shape pick_row_cfg returns for D = 1..1024 is one of its entries.
+constexpr bool row_shapes_exhaustive() {
+  for (int D = 1; D <= 1024; ++D) {
+    RowCfg c{};
+    if (!pick_row_cfg(D, c)) continue;
+    bool listed = false;
+#define TRS_ROW_CASE(V, G, K) listed = listed || (c.vec == V && c.g == G && c.k == K);
+    TRS_ROW_SHAPES(TRS_ROW_CASE)
+#undef TRS_ROW_CASE
+    if (!listed) return false;
+  }
+  return true;
+}
+static_assert(row_shapes_exhaustive(), "pick_row_cfg returns a shape that TRS_ROW_SHAPES does not list");
 
 template <int NET, int MODE>
 static inline int launch_score(const ScoreArgs& a, hipStream_t s) {
   RowCfg c;
-  if (!pick_row_cfg(a.T.D, c)) {
-    trs_set_error("unsupported n_factors D=%d (need 1..1024; D %% 4 != 0 only up to 256)", a.T.D);
-    return TRS_E_ARG;
-  }
+  TRS_TRY(row_cfg_for("launch_score", a.T.D, c));
   const int64_t B = a.Bt.B;
   if (B == 0) return TRS_OK;
   const int tpw = TRS_WAVE / c.g;
   const int64_t waves = (B + tpw - 1) / tpw;
   const int grid = trs_grid(waves, TRS_BLOCK / TRS_WAVE);
-#define TRS_CASE(V, GG, KK)                                                                        \
-  if (c.vec == V && c.g == GG && c.k == KK) {                                                      \
-    hipLaunchKernelGGL((score_kernel<NET, V, GG, KK, MODE>), dim3(grid), dim3(TRS_BLOCK), 0, s, a); \
-    TRS_CHECK_LAUNCH("score_kernel");                                                              \
-    return TRS_OK;                                                                                 \
-  }
-  TRS_CASE(4, 2, 1)
-  TRS_CASE(4, 4, 1)
-  TRS_CASE(4, 8, 1)
-  TRS_CASE(4, 16, 1)
-  TRS_CASE(4, 32, 1)
-  TRS_CASE(4, 64, 1)
-  TRS_CASE(4, 64, 2)
-  TRS_CASE(4, 64, 4)
-  TRS_CASE(1, 4, 1)
-  TRS_CASE(1, 16, 1)
-  TRS_CASE(1, 64, 1)
-  TRS_CASE(1, 64, 4)
-#undef TRS_CASE
-  trs_set_error("internal: no kernel for D=%d", a.T.D);
-  return TRS_E_ARG;
+  return for_row_shape(c, [&](auto V, auto G, auto K) {
+    hipLaunchKernelGGL((score_kernel<NET, V(), G(), K(), MODE>), dim3(grid), dim3(TRS_BLOCK), 0, s, a);
+    TRS_CHECK_LAUNCH("score_kernel");
+    return TRS_OK;
+  });
 }
 
 }  // namespace trs

@@ -275,22 +275,15 @@ static int sm_check_common(const char* who, int64_t B, int32_t D, float tau, con
   return TRS_OK;
 }
 
+// need_ids: the kernel reads the tables and the batch's ids (softmax: no 1-wide user table — it cancels in every
+// row — and item ids that fit the int32 id column of the workspace)
 static int sm_check_tables(const char* who, int net, const trs_tables* T, const trs_batch* b, bool need_ids) {
-  TRS_REQUIRE(T != nullptr, "%s: tables is NULL", who);
+  TRS_TRY(need_ids ? trs_check_tables(who, net, T, TRS_SKIP_USER_LIN, INT32_MAX) : trs_check_net(who, net, T));
   TRS_REQUIRE(b != nullptr, "%s: batch is NULL", who);
-  TRS_REQUIRE(net == TRS_NET_LINEAR || net == TRS_NET_FM, "%s: net must be TRS_NET_LINEAR or TRS_NET_FM", who);
-  TRS_REQUIRE(T->M >= 0 && T->M <= TRS_MAX_META, "%s: M=%d outside 0..%d", who, T->M, TRS_MAX_META);
   TRS_REQUIRE(b->idx_bytes == 4 || b->idx_bytes == 8, "%s: idx_bytes must be 4 or 8", who);
   if (!need_ids) return TRS_OK;
-  TRS_REQUIRE(T->user && T->item && T->item_lin, "%s: user/item table or 1-wide item table is NULL", who);
-  TRS_REQUIRE(T->n_users > 0 && T->n_items > 0 && T->n_items <= INT32_MAX, "%s: n_users/n_items outside 1..2^31-1",
-              who);
   TRS_REQUIRE(b->user && b->pos, "%s: user/pos ids are NULL", who);
   TRS_REQUIRE(T->M == 0 || b->pos_meta, "%s: pos_meta ids are NULL but M=%d", who, T->M);
-  for (int m = 0; m < T->M; ++m) {
-    TRS_REQUIRE(T->meta[m] && T->n_meta[m] > 0, "%s: metadata table %d is NULL/empty", who, m);
-    if (net == TRS_NET_FM) TRS_REQUIRE(T->meta_lin[m], "%s: linear_metadata table %d is NULL", who, m);
-  }
   return TRS_OK;
 }
 
@@ -304,10 +297,8 @@ extern "C" int64_t trs_softmax_workspace_bytes(int64_t B, int32_t D) {
 extern "C" int trs_softmax_stage(int net, const trs_tables* tables, const trs_batch* batch, float tau,
                                  const float* logq_dev, void* workspace_dev, int64_t workspace_bytes, void* stream) {
   const char* who = "trs_softmax_stage";
-  int rc = sm_check_tables(who, net, tables, batch, true);
-  if (rc) return rc;
-  rc = sm_check_common(who, batch->B, tables->D, tau, workspace_dev, workspace_bytes);
-  if (rc) return rc;
+  TRS_TRY(sm_check_tables(who, net, tables, batch, true));
+  TRS_TRY(sm_check_common(who, batch->B, tables->D, tau, workspace_dev, workspace_bytes));
   const SmLayout L = sm_layout(batch->B, tables->D);
   float* w = (float*)workspace_dev;
   StageArgs a;
@@ -331,8 +322,7 @@ extern "C" int trs_softmax_stage(int net, const trs_tables* tables, const trs_ba
 extern "C" int trs_softmax_rows(float* z_dev, int64_t z_bytes, int64_t row0, int64_t n_rows, int64_t B, int32_t D,
                                 float tau, void* workspace_dev, int64_t workspace_bytes, void* stream) {
   const char* who = "trs_softmax_rows";
-  const int rc = sm_check_common(who, B, D, tau, workspace_dev, workspace_bytes);
-  if (rc) return rc;
+  TRS_TRY(sm_check_common(who, B, D, tau, workspace_dev, workspace_bytes));
   TRS_REQUIRE(z_dev != nullptr, "%s: logits are NULL", who);
   TRS_REQUIRE(row0 >= 0 && n_rows >= 1 && row0 + n_rows <= B, "%s: rows [%lld, %lld) outside [0, %lld)", who,
               (long long)row0, (long long)(row0 + n_rows), (long long)B);
@@ -364,10 +354,8 @@ extern "C" int trs_softmax_grads(int net, const trs_tables* tables, const trs_ba
                                  float* grad_lin_dev, float* loss_sum_dev, void* stream) {
   const char* who = "trs_softmax_grads";
   const bool grads = grad_rows_dev || grad_lin_dev;
-  int rc = sm_check_tables(who, net, tables, batch, grads);
-  if (rc) return rc;
-  rc = sm_check_common(who, batch->B, tables->D, tau, workspace_dev, workspace_bytes);
-  if (rc) return rc;
+  TRS_TRY(sm_check_tables(who, net, tables, batch, grads));
+  TRS_TRY(sm_check_common(who, batch->B, tables->D, tau, workspace_dev, workspace_bytes));
   TRS_REQUIRE(loss_sum_dev != nullptr, "%s: loss_sum is NULL", who);
   TRS_REQUIRE(!grads || (grad_rows_dev && grad_lin_dev), "%s: grad_rows and grad_lin must both be given or both NULL",
               who);

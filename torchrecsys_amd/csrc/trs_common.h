@@ -22,7 +22,14 @@ void trs_set_error(const char* fmt, ...);
     }                                 \
   } while (0)
 
-#define TRS_CHECK_LAUNCH(name)                                             \
+// a check that has set the error itself: hand its code on
+#define TRS_TRY(expr)           \
+  do {                          \
+    const int rc__ = (expr);    \
+    if (rc__) return rc__;      \
+  } while (0)
+
+#define TRS_CHECK_LAUNCH(name)                                           \
   do {                                                                     \
     hipError_t e__ = hipGetLastError();                                    \
     if (e__ != hipSuccess) {                                               \
@@ -154,6 +161,59 @@ static inline TrsSampler trs_sampler_args(const trs_sampler* s) {
   }
   return r;
 }
+// candidate j of a triple (mine.hip, multineg.hip) draws under seed + j * this (mod 2^64); restated in
+// tests/mining_ref.py and tests/multineg_ref.py
+constexpr uint64_t TRS_CANDIDATE_KEY_STEP = 0xD1B54A32D192ED03ull;
+
+// ------------------------------------------------------------------------------------------ argument checks
+// The host-side checks every entry point shares; `who` is the entry point's name, the prefix of every message.
+static inline int trs_check_sampler(const char* who, const trs_sampler* s) {
+  TRS_REQUIRE(!s || (s->k_neg >= 1 && (!s->popularity || (s->pop_items && s->pop_n > 0)) &&
+                     ((s->seen_off == nullptr) == (s->seen_items == nullptr))),
+              "%s: bad sampler options", who);
+  return TRS_OK;
+}
+// positions [t0, t0 + B) of an epoch of N * k_neg positions; kn = the sampler's k_neg (1 without options)
+static inline int trs_check_slice(const char* who, int64_t N, int64_t t0, int64_t B, const trs_sampler* s,
+                                  int64_t& kn) {
+  kn = s && s->k_neg > 1 ? s->k_neg : 1;
+  TRS_REQUIRE(N > 0 && t0 >= 0 && B >= 0 && t0 + B <= N * kn, "%s: slice [%lld,%lld) outside [0,%lld)", who,
+              (long long)t0, (long long)(t0 + B), (long long)(N * kn));
+  return TRS_OK;
+}
+// tables non-NULL, net a Linear / FM scorer, M in range: what every entry point needs before it reads *T
+static inline int trs_check_net(const char* who, int net, const trs_tables* T) {
+  TRS_REQUIRE(T != nullptr, "%s: tables is NULL", who);
+  TRS_REQUIRE(net == TRS_NET_LINEAR || net == TRS_NET_FM, "%s: net must be TRS_NET_LINEAR or TRS_NET_FM", who);
+  TRS_REQUIRE(T->M >= 0 && T->M <= TRS_MAX_META, "%s: M=%d outside 0..%d", who, T->M, TRS_MAX_META);
+  return TRS_OK;
+}
+// trs_check_net + the tables a scorer reads: user / item rows with their 1-wide tables, non-empty, and every metadata
+// column (FM: with its 1-wide table).  `skip`: what a caller does not read.
+enum {
+  TRS_SKIP_USER = 1,        // the user table and its 1-wide table (trs_item_fold folds item-side rows only)
+  TRS_SKIP_USER_LIN = 2,    // the 1-wide user table (in-batch softmax: it cancels in every row)
+  TRS_SKIP_META_ROWS = 4,   // n_meta[m] > 0 (trs_item_fold never compares an id against it)
+};
+static inline int trs_check_tables(const char* who, int net, const trs_tables* T, unsigned skip = 0,
+                                   int64_t max_items = INT64_MAX) {
+  TRS_TRY(trs_check_net(who, net, T));
+  const bool user = !(skip & TRS_SKIP_USER);
+  TRS_REQUIRE((!user || T->user) && T->item, "%s: user/item table is NULL", who);
+  TRS_REQUIRE(!user || (skip & TRS_SKIP_USER_LIN) || T->user_lin, "%s: 1-wide user table (bias / linear term) is NULL",
+              who);
+  TRS_REQUIRE(T->item_lin, "%s: 1-wide item table (bias / linear term) is NULL", who);
+  TRS_REQUIRE((!user || T->n_users > 0) && T->n_items > 0, "%s: empty user/item table", who);
+  TRS_REQUIRE(T->n_items <= max_items, "%s: n_items=%lld above %lld", who, (long long)T->n_items,
+              (long long)max_items);
+  for (int m = 0; m < T->M; ++m) {
+    TRS_REQUIRE(T->meta[m] && ((skip & TRS_SKIP_META_ROWS) || T->n_meta[m] > 0), "%s: metadata table %d is NULL/empty",
+                who, m);
+    if (net == TRS_NET_FM) TRS_REQUIRE(T->meta_lin[m], "%s: linear_metadata table %d is NULL", who, m);
+  }
+  return TRS_OK;
+}
+
 __device__ __forceinline__ bool trs_user_has_item(const TrsSampler& S, int64_t u, int64_t item) {
   // a user id outside the CSR (reported by the scorer's id check later) has seen nothing: no read beyond seen_off
   if ((uint64_t)u >= (uint64_t)S.seen_users) return false;
@@ -253,9 +313,18 @@ __device__ __forceinline__ float trs_group_sum(float v) {
   for (int o = G >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
-__device__ __forceinline__ float trs_wave_sum(float v) { return trs_group_sum<64>(v); }
-__device__ __forceinline__ int trs_wave_sum_i(int v) {
+template <int G>
+__device__ __forceinline__ int trs_group_sum_i(int v) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  for (int o = G >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+template <int G>
+__device__ __forceinline__ int trs_group_or(int v) {
+#pragma unroll
+  for (int o = G >> 1; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ float trs_wave_sum(float v) { return trs_group_sum<64>(v); }
+__device__ __forceinline__ int trs_wave_sum_i(int v) { return trs_group_sum_i<64>(v); }
+
