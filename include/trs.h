@@ -48,6 +48,8 @@ extern "C" {
 #define TRS_LOSS_BPR 1
 /* Sampled softmax over one positive and K sampled negatives per row (trs_score_multi_fwd_bwd only; not a pair loss). */
 #define TRS_LOSS_SAMPLED_SOFTMAX 2
+/* WARP, the rank-weighted first violator among K sampled negatives (trs_score_warp_fwd_bwd only; not a pair loss). */
+#define TRS_LOSS_WARP 3
 
 /* Embedding tables of one scorer.  Row-major (n_rows, D) fp32, as nn.Embedding.weight
  * (embeddings/init_embeddings.py:5-50,53-97).
@@ -96,7 +98,8 @@ const char* trs_last_error(void);
  *   5: trs_epoch_flags_ordered (flagged-first batches), trs_train_args.n_flagged_dev.
  *   6: batched top-k retrieval: trs_csr, trs_item_fold(_bytes), trs_retrieve_topk, trs_retrieve_workspace_bytes,
  *      trs_mask_seen, trs_rank_metrics.  (Entry points added since without touching an existing signature or struct:
- *      the in-batch softmax group, trs_batch_prepare_mined, trs_batch_prepare_multi, trs_score_multi_fwd_bwd.) */
+ *      the in-batch softmax group, trs_batch_prepare_mined, trs_batch_prepare_multi, trs_score_multi_fwd_bwd,
+ *      trs_score_warp_fwd_bwd, TRS_LOSS_WARP.) */
 #define TRS_ABI_VERSION 6
 #define TRS_SYNC_WORDS 288
 int trs_abi_version(void);
@@ -235,6 +238,39 @@ int trs_score_multi_fwd_bwd(int net, const trs_tables* tables, const int32_t* us
                             const int32_t* meta_dev, int64_t B, int32_t M, int32_t K, int32_t loss, float tau,
                             float inv_B, float* loss_sum_dev, int32_t* auc_count_dev, float* grad_rows_dev,
                             float* grad_lin_dev, int32_t* err_flag_dev, void* stream);
+
+/* WARP (Weighted Approximate-Rank Pairwise loss, Weston et al. 2011: WSABIE) of a Linear / FM scorer over
+ * rows of one positive p and K candidates c_0 .. c_{K-1} (the id blocks of trs_batch_prepare_multi, unchanged: user (B),
+ * items (1+K, B), meta (1+K, B, M), int32), all rows read from the PRE-update tables.  z(u, i) is pass_forward_z's value:
+ * Linear the score, FM the argument of its sigmoid (as sampled softmax, mining and retrieval; on the sigmoid itself a
+ * margin of 1 would always be violated).
+ *   violation  h_j = (z(u,c_j) - z(u,p)) + margin; candidate j violates iff h_j > 0 (a NaN does not); J = the smallest
+ *              violating j; trials = J + 1, or 0 when no candidate violates.
+ *   weight     w = rank_weight[J]: K floats on the device, supplied by the caller (the rank estimate of a row that needed
+ *              J + 1 draws; no clipping).
+ *   loss       row loss = w * h_J, or 0 without a violator.  d loss / d z(u,c_J) = +w * inv_B, d loss / d z(u,p) =
+ *              -w * inv_B (no sigmoid factor), through z's derivatives.  The user's 1-wide term enters both z with
+ *              derivative 1: its gradient is written as exactly 0.
+ * loss_sum += the sum of the row losses (the caller divides by B); auc_count (may be NULL) += #(score_p > score_c0), on
+ * the scores trs_score_fwd_bwd counts (FM: sigmoid(z)).  Both are ACCUMULATED.
+ * Outputs: neg_out (B) the chosen candidate c_J's id and neg_meta_out (B, M) its metadata ids (c_0's without a violator,
+ * so the index lists stay valid); trials_out (B, may be NULL).  Staged gradients in trs_score_fwd_bwd's order, R = 3 + 2M
+ * fields: grad_rows (R, B, D) and grad_lin (R, B) — user, positive, chosen candidate, then per metadata column the
+ * positive's and the chosen candidate's; the positive's ids are slot 0 of the input blocks.  A row without a violator
+ * stages zeros.  Linear has no 1-wide metadata tables: those fields are 0.
+ * grad_rows == NULL (then grad_lin must be NULL too): forward only — the same loss, AUC count, neg_out, neg_meta_out and
+ * trials_out, nothing staged.
+ * An id outside its table is clamped for addressing, sets bit 0 of *err_flag_dev (may be NULL) and zeroes its row's loss
+ * and gradients; its trials = 0 and its neg_out = c_0 as given.
+ * TRS_E_ARG, nothing launched: the grounds of trs_score_multi_fwd_bwd (tables NULL or a NULL member; net not
+ * TRS_NET_LINEAR / TRS_NET_FM; K outside 1..64; M != tables->M; a D the scorer kernels do not take; loss_sum NULL;
+ * grad_lin without grad_rows or the reverse; NULL ids with B > 0) and: margin not finite; rank_weight NULL; neg_out NULL
+ * (or neg_meta_out NULL with M > 0). */
+int trs_score_warp_fwd_bwd(int net, const trs_tables* tables, const int32_t* user_dev, const int32_t* items_dev,
+                           const int32_t* meta_dev, int64_t B, int32_t M, int32_t K, float margin,
+                           const float* rank_weight_dev, float inv_B, float* loss_sum_dev, int32_t* auc_count_dev,
+                           int32_t* neg_out, int32_t* neg_meta_out, int32_t* trials_out, float* grad_rows_dev,
+                           float* grad_lin_dev, int32_t* err_flag_dev, void* stream);
 
 /* ------------------------------------------------------------------ scorers: forward only (a2, a3, a6) */
 /* Fused positive+negative scoring pass; the user row is gathered once for both passes.

@@ -12,6 +12,7 @@ TRS_NET_LINEAR = 0
 TRS_NET_FM = 1
 LOSS_ID = {"hinge": 0, "bpr": 1}  # TRS_LOSS_HINGE / TRS_LOSS_BPR
 LOSS_SAMPLED_SOFTMAX = 2  # TRS_LOSS_SAMPLED_SOFTMAX (trs_score_multi_fwd_bwd only: not a pair loss)
+LOSS_WARP = 3  # TRS_LOSS_WARP (trs_score_warp_fwd_bwd only: not a pair loss)
 RETRIEVE_KMAX = 128  # TRS_RETRIEVE_KMAX: largest k of the fused retrieval kernel
 RETRIEVE_DMAX = 256  # TRS_RETRIEVE_DMAX: largest D of the fused retrieval kernel
 ABI_VERSION = 6  # == TRS_ABI_VERSION of include/trs.h (tests/test_abi.py)
@@ -132,6 +133,8 @@ PROTOTYPES = {
                                           _vp, _vp, _vp, C.POINTER(TrsSampler), _i32, _vp]),
     "trs_score_multi_fwd_bwd": (C.c_int, [C.c_int, _T, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _f, _f, _vp, _vp, _vp,
                                           _vp, _vp, _vp]),
+    "trs_score_warp_fwd_bwd": (C.c_int, [C.c_int, _T, _vp, _vp, _vp, _i64, _i32, _i32, _f, _vp, _f, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _vp]),
     "trs_score_forward": (C.c_int, [C.c_int, _T, _Bp, _vp, _vp, _vp]),
     "trs_score_fwd_bwd": (C.c_int, [C.c_int, _T, _Bp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "trs_score_backward": (C.c_int, [C.c_int, _T, _Bp, _vp, _vp, _vp, _vp, _vp]),

@@ -17,6 +17,9 @@
 //                   the same tables — and stages the gradients.  Forward-only mode stops after sweep 1.
 // Gradients are staged, never added to a table here: every gradient of a step comes from the pre-update tables.  No LDS
 // (but the block's loss reduction), no scratch memory.
+//
+// warp_kernel (trs_score_warp_fwd_bwd): the same mapping and round_forward for the WARP loss — the
+// first candidate that violates the margin is trained on alone, weighted by a rank estimate; described above the kernel.
 #include "score_kernels.h"
 
 using namespace trs;
@@ -94,8 +97,9 @@ struct MultiArgs {
 
 // The forward part of one round: the ids of candidates r0 .. r0 + C - 1 (lane c of the group reads candidate r0 + c's,
 // a shuffle hands them round) and their C independent passes.
-template <int NET, int VEC, int G, int K, int C>
-__device__ __forceinline__ void round_forward(const MultiArgs& a, const RowReg<VEC, K>& ur, float u_lin, int r0,
+// (A: MultiArgs or WarpArgs — the id blocks, B, Kn and the tables are named alike)
+template <int NET, int VEC, int G, int K, int C, typename A>
+__device__ __forceinline__ void round_forward(const A& a, const RowReg<VEC, K>& ur, float u_lin, int r0,
                                               int64_t tc, int lig, int gbase, RowReg<VEC, K> (&ir)[C],
                                               RowReg<VEC, K> (&Ss)[C], float (&z)[C]) {
   const int Kn = a.Kn;
@@ -394,6 +398,280 @@ int launch_multi(const MultiArgs& a, hipStream_t s) {
   });
 }
 
+
+// ------------------------------------------------------------------------------------------------ WARP
+struct WarpArgs {
+  trs_tables T;
+  const int32_t* user;   // (B)
+  const int32_t* items;  // (1+K, B): row 0 the positives, row 1+j candidate j
+  const int32_t* meta;   // (1+K, B, M) or NULL
+  int64_t B;
+  int Kn;  // candidates per row, 1..64
+  float margin, inv_B;
+  const float* rank_weight;  // (K): the weight of a row whose first violator is candidate j
+  float* loss_sum;
+  int32_t* auc_count;
+  int32_t* neg_out;       // (B): the chosen candidate's id (c_0 without a violator)
+  int32_t* neg_meta_out;  // (B, M)
+  int32_t* trials_out;    // (B) or NULL: J + 1, 0 without a violator
+  float* grad_rows;       // (3 + 2M, B, D), trs_score_fwd_bwd's field order; NULL: forward only
+  float* grad_lin;        // (3 + 2M, B)
+  int32_t* err;
+};
+
+// warp_kernel (wave = 64): multineg_kernel's mapping — one aligned group of G lanes per row, the user row and the
+// positive's pass in registers, candidates in rounds of C, every z pass_forward_z's.  What differs:
+//   first violator  within a round the lowest j with (z_j - z_p) + margin > 0, found by selects from the last slot down;
+//                   a group that has its J keeps scoring with its wave (the loads and shuffles stay whole-wave) and
+//                   ignores what it sees, again by select.
+//   one sweep       the weight depends on J alone, so the group stages (user, positive, chosen candidate) in the round
+//                   where it finds J, from that round's registers: the chosen row is picked by a chain of selects (a
+//                   register array indexed at run time would go to scratch), the stores sit under the group-uniform
+//                   predicate.  No user or item row is read twice; FM with metadata reads the chosen slot's metadata
+//                   rows again, as score_kernel does (pass_forward_z does not hand them back).
+//   early exit      the round loop ends when __all lanes of the wave are done (J found, t >= B or a bad id): the vote is
+//                   wave-uniform, so no shuffle of a later round runs with part of a group inactive.
+// rank_weight is read by an ordinary vector load.  No LDS (but the block's loss reduction), no scratch memory.
+template <int NET, int VEC, int G, int K, bool META>
+__global__ __launch_bounds__(TRS_BLOCK) void warp_kernel(const WarpArgs a) {
+  constexpr int N = K * VEC;
+  constexpr int CR = MULTI_ROW_VGPRS / N < 8 ? (MULTI_ROW_VGPRS / N < 1 ? 1 : MULTI_ROW_VGPRS / N) : 8;
+  constexpr int C = G < CR ? G : CR;  // candidates per round (a power of two)
+  constexpr int TPW = TRS_WAVE / G;
+  constexpr bool FM = NET == TRS_NET_FM;
+  const trs_tables& T = a.T;
+  const int D = T.D;
+  const int M = META ? T.M : 0;
+  const int64_t B = a.B;
+  const int Kn = a.Kn;
+  const int S1 = 1 + Kn;
+  const int lane = threadIdx.x & 63;
+  const int lig = lane % G;
+  const int gbase = lane - lig;
+  const int64_t wave = ((int64_t)blockIdx.x * TRS_BLOCK + threadIdx.x) >> 6;
+  const int64_t nwave = ((int64_t)gridDim.x * TRS_BLOCK) >> 6;
+  const bool grad = a.grad_rows != nullptr;
+  const int64_t BD = B * (int64_t)D;
+  float* const gr = a.grad_rows;
+  float* const gl = a.grad_lin;
+
+  float loss_acc = 0.f;
+  int auc_acc = 0;
+
+  const int64_t niter = (B + TPW - 1) / TPW;
+  for (int64_t it_ = wave; it_ < niter; it_ += nwave) {
+    const int64_t t = it_ * TPW + lane / G;
+    const bool valid = t < B;
+    const int64_t tc = valid ? t : 0;  // loads stay unconditional
+
+    // every id of the row against its table first, as multineg_kernel
+    int64_t uid = a.user[tc];
+    int bad = 0;
+    if ((uint64_t)uid >= (uint64_t)T.n_users) { bad = 1; uid = 0; }
+    for (int s = lig; s < S1; s += G) {
+      const int64_t e = (int64_t)s * B + tc;
+      if ((uint64_t)(int64_t)a.items[e] >= (uint64_t)T.n_items) bad = 1;
+      for (int m = 0; m < M; ++m)
+        if ((uint64_t)(int64_t)a.meta[e * M + m] >= (uint64_t)T.n_meta[m]) bad = 1;
+    }
+    bad = trs_group_or<G>(bad);
+    if (valid && bad && lig == 0 && a.err) atomicOr(a.err, 1);
+    const bool live = valid && !bad;
+
+    RowReg<VEC, K> ur;
+    row_load<VEC, G, K>(ur, T.user, uid, D, lig);
+    const float u_lin = T.user_lin[uid];
+    int64_t pid = a.items[tc];
+    if ((uint64_t)pid >= (uint64_t)T.n_items) pid = 0;
+    RowReg<VEC, K> pr, Sp;
+    float p_lin, lin_p;
+    bool okp = true;
+    const float z0 = pass_forward_z<NET, VEC, G, K>(T, ur, u_lin, pid, a.meta, 4, tc, true, lig, pr, Sp, p_lin, lin_p, okp);
+    const float sp = FM ? sigmoidf_(z0) : z0;  // = pass_forward's score (the AUC count is on the scores, as today)
+
+    bool done = !live;  // group-uniform: J found, the row past the batch, or a bad id
+    int trials = 0;
+
+    for (int r0 = 0; r0 < Kn; r0 += C) {
+      if (__all(done)) break;  // wave-uniform
+      RowReg<VEC, K> ir[C], Ss[C];
+      float z[C];
+      round_forward<NET, VEC, G, K, C>(a, ur, u_lin, r0, tc, lig, gbase, ir, Ss, z);
+      if (r0 == 0 && live && lig == 0) auc_acc += (sp > (FM ? sigmoidf_(z[0]) : z[0])) ? 1 : 0;
+      // the lowest violating slot of the round, its hinge operand and its rows (selects; a NaN does not violate)
+      int cf = -1;
+      float hJ = 0.f;
+      RowReg<VEC, K> ni, Sn;
+#pragma unroll
+      for (int n = 0; n < N; ++n) ni.v[n] = Sn.v[n] = 0.f;
+#pragma unroll
+      for (int c = C - 1; c >= 0; --c) {
+        const float h = (z[c] - z0) + a.margin;
+        const bool v = r0 + c < Kn && h > 0.f;
+        cf = v ? c : cf;
+        hJ = v ? h : hJ;
+#pragma unroll
+        for (int n = 0; n < N; ++n) {
+          if (FM) ni.v[n] = v ? ir[c].v[n] : ni.v[n];
+          if (!FM || META) Sn.v[n] = v ? Ss[c].v[n] : Sn.v[n];
+        }
+      }
+      const bool hit = !done && cf >= 0;
+      const int J = hit ? r0 + cf : 0;
+      const float w = a.rank_weight[J];  // unconditional, inside the table; used under `hit` only
+      if (hit) {
+        done = true;
+        trials = J + 1;
+        if (lig == 0) {
+          loss_acc += w * hJ;
+          a.neg_out[t] = a.items[(int64_t)(1 + J) * B + t];
+          for (int m = 0; m < M; ++m) a.neg_meta_out[t * M + m] = a.meta[((int64_t)(1 + J) * B + t) * M + m];
+        }
+        if (grad) {
+          // d loss / d z: + w / B at the chosen candidate, - w / B at the positive (no sigmoid factor: the hinge is on z)
+          const float gn = w * a.inv_B, gp = -gn;
+          RowReg<VEC, K> g;
+          // field 0: user.  FM: gp*(Sp-u) + gn*(Sn-u) (= gp*i + gn*j when M == 0); Linear: gp*Sp + gn*Sn
+          if (FM) {
+            if (M == 0) {
+#pragma unroll
+              for (int n = 0; n < N; ++n) g.v[n] = gp * pr.v[n] + gn * ni.v[n];
+            } else {
+#pragma unroll
+              for (int n = 0; n < N; ++n) g.v[n] = gp * (Sp.v[n] - ur.v[n]) + gn * (Sn.v[n] - ur.v[n]);
+            }
+          } else {
+#pragma unroll
+            for (int n = 0; n < N; ++n) g.v[n] = gp * Sp.v[n] + gn * Sn.v[n];
+          }
+          row_store<VEC, G, K>(g, gr + t * (int64_t)D, D, lig);
+          // field 1 / 2: the positive / the chosen candidate.  FM: g*(S - item) (= g*u when M == 0); Linear: g*u
+          if (FM && M != 0) {
+#pragma unroll
+            for (int n = 0; n < N; ++n) g.v[n] = gp * (Sp.v[n] - pr.v[n]);
+          } else {
+#pragma unroll
+            for (int n = 0; n < N; ++n) g.v[n] = gp * ur.v[n];
+          }
+          row_store<VEC, G, K>(g, gr + BD + t * (int64_t)D, D, lig);
+          if (FM && M != 0) {
+#pragma unroll
+            for (int n = 0; n < N; ++n) g.v[n] = gn * (Sn.v[n] - ni.v[n]);
+          } else {
+#pragma unroll
+            for (int n = 0; n < N; ++n) g.v[n] = gn * ur.v[n];
+          }
+          row_store<VEC, G, K>(g, gr + 2 * BD + t * (int64_t)D, D, lig);
+          for (int m = 0; m < M; ++m) {
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+              const float gs = s ? gn : gp;
+              const RowReg<VEC, K>& S = s ? Sn : Sp;
+              if (FM) {  // (the slot's metadata row again: L1/L2-hot from the forward part)
+                int64_t mid = a.meta[((int64_t)(s ? 1 + J : 0) * B + t) * M + m];
+                if ((uint64_t)mid >= (uint64_t)T.n_meta[m]) mid = 0;
+                RowReg<VEC, K> mr;
+                row_load<VEC, G, K>(mr, T.meta[m], mid, D, lig);
+#pragma unroll
+                for (int n = 0; n < N; ++n) g.v[n] = gs * (S.v[n] - mr.v[n]);
+              } else {
+#pragma unroll
+                for (int n = 0; n < N; ++n) g.v[n] = gs * ur.v[n];
+              }
+              row_store<VEC, G, K>(g, gr + (int64_t)(3 + 2 * m + s) * BD + t * (int64_t)D, D, lig);
+            }
+          }
+          if (lig == 0) {
+            gl[t] = 0.f;  // the user's 1-wide term enters both z with derivative 1: exactly 0
+            gl[B + t] = gp;
+            gl[2 * B + t] = gn;
+            for (int m = 0; m < M; ++m) {  // Linear has no 1-wide metadata tables: those fields stay 0
+              gl[(int64_t)(3 + 2 * m) * B + t] = FM ? gp : 0.f;
+              gl[(int64_t)(4 + 2 * m) * B + t] = FM ? gn : 0.f;
+            }
+          }
+        }
+      }
+    }
+
+    if (valid && lig == 0 && a.trials_out) a.trials_out[t] = trials;
+    if (valid && trials == 0) {  // no violator (or a dead row): c_0 keeps the index lists valid, every gradient is 0
+      if (lig == 0) {
+        a.neg_out[t] = a.items[B + t];
+        for (int m = 0; m < M; ++m) a.neg_meta_out[t * M + m] = a.meta[(B + t) * M + m];
+      }
+      if (grad) {
+        RowReg<VEC, K> g;
+#pragma unroll
+        for (int n = 0; n < N; ++n) g.v[n] = 0.f;
+        const int R = 3 + 2 * M;
+        for (int f = 0; f < R; ++f) {
+          row_store<VEC, G, K>(g, gr + (int64_t)f * BD + t * (int64_t)D, D, lig);
+          if (lig == 0) gl[(int64_t)f * B + t] = 0.f;
+        }
+      }
+    }
+  }
+
+  if (a.loss_sum) {  // as score_kernel: lanes -> wave -> block -> one atomic per block
+    __shared__ float s_loss[TRS_BLOCK / TRS_WAVE];
+    __shared__ int s_auc[TRS_BLOCK / TRS_WAVE];
+    const float wl = trs_wave_sum(loss_acc);
+    const int wa = trs_wave_sum_i(auc_acc);
+    if (lane == 0) {
+      s_loss[threadIdx.x >> 6] = wl;
+      s_auc[threadIdx.x >> 6] = wa;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      float L = 0.f;
+      int A = 0;
+#pragma unroll
+      for (int w = 0; w < TRS_BLOCK / TRS_WAVE; ++w) {
+        L += s_loss[w];
+        A += s_auc[w];
+      }
+      if (L != 0.f) atomicAdd(a.loss_sum, L);
+      if (A != 0 && a.auc_count) atomicAdd(a.auc_count, A);
+    }
+  }
+}
+
+template <int NET>
+int launch_warp(const WarpArgs& a, hipStream_t s) {
+  RowCfg c;
+  TRS_TRY(row_cfg_for("trs_score_warp_fwd_bwd", a.T.D, c));
+  const int tpw = TRS_WAVE / c.g;
+  const int64_t waves = (a.B + tpw - 1) / tpw;
+  const dim3 gr(trs_grid(waves, TRS_BLOCK / TRS_WAVE)), bl(TRS_BLOCK);
+  return for_row_shape(c, [&](auto V, auto G, auto K) {
+    if (a.T.M > 0) hipLaunchKernelGGL((warp_kernel<NET, V(), G(), K(), true>), gr, bl, 0, s, a);
+    else hipLaunchKernelGGL((warp_kernel<NET, V(), G(), K(), false>), gr, bl, 0, s, a);
+    TRS_CHECK_LAUNCH("warp_kernel");
+    return TRS_OK;
+  });
+}
+
+// The argument checks trs_score_multi_fwd_bwd and trs_score_warp_fwd_bwd share (everything but the loss's own
+// parameters); B == 0 passes: the caller returns before it launches.
+int check_multi_args(const char* who, int net, const trs_tables* tables, const int32_t* user_dev,
+                     const int32_t* items_dev, const int32_t* meta_dev, int64_t B, int32_t M, int32_t K,
+                     const float* loss_sum_dev, const float* grad_rows_dev, const float* grad_lin_dev) {
+  TRS_TRY(trs_check_tables(who, net, tables));
+  TRS_REQUIRE(K >= 1 && K <= 64, "%s: K=%d outside 1..64", who, K);
+  TRS_REQUIRE(M == tables->M, "%s: M=%d does not match the tables' M=%d", who, M, tables->M);
+  RowCfg cfg;
+  TRS_TRY(row_cfg_for(who, tables->D, cfg));
+  TRS_REQUIRE(loss_sum_dev, "%s: loss_sum is NULL", who);
+  TRS_REQUIRE((grad_rows_dev == nullptr) == (grad_lin_dev == nullptr),
+              "%s: grad_rows and grad_lin must both be given or both NULL (forward only)", who);
+  TRS_REQUIRE(B >= 0, "%s: negative batch size", who);
+  if (B == 0) return TRS_OK;
+  TRS_REQUIRE(user_dev && items_dev, "%s: user/item ids are NULL", who);
+  TRS_REQUIRE(M == 0 || meta_dev, "%s: metadata ids are NULL but M=%d", who, M);
+  return TRS_OK;
+}
+
 }  // namespace
 
 extern "C" int trs_batch_prepare_multi(const int32_t* stream_user_dev, const int32_t* stream_item_dev,
@@ -443,21 +721,12 @@ extern "C" int trs_score_multi_fwd_bwd(int net, const trs_tables* tables, const 
                                        int32_t* auc_count_dev, float* grad_rows_dev, float* grad_lin_dev,
                                        int32_t* err_flag_dev, void* stream) {
   const char* who = "trs_score_multi_fwd_bwd";
-  TRS_TRY(trs_check_tables(who, net, tables));
-  TRS_REQUIRE(K >= 1 && K <= 64, "%s: K=%d outside 1..64", who, K);
+  TRS_TRY(check_multi_args(who, net, tables, user_dev, items_dev, meta_dev, B, M, K, loss_sum_dev, grad_rows_dev,
+                           grad_lin_dev));
   TRS_REQUIRE(loss == TRS_LOSS_HINGE || loss == TRS_LOSS_BPR || loss == TRS_LOSS_SAMPLED_SOFTMAX,
               "%s: unknown loss id %d", who, loss);
-  TRS_REQUIRE(M == tables->M, "%s: M=%d does not match the tables' M=%d", who, M, tables->M);
-  RowCfg cfg;
-  TRS_TRY(row_cfg_for(who, tables->D, cfg));
   TRS_REQUIRE(tau > 0.f && tau <= 3.0e38f, "%s: temperature must be positive and finite", who);
-  TRS_REQUIRE(loss_sum_dev, "%s: loss_sum is NULL", who);
-  TRS_REQUIRE((grad_rows_dev == nullptr) == (grad_lin_dev == nullptr),
-              "%s: grad_rows and grad_lin must both be given or both NULL (forward only)", who);
-  TRS_REQUIRE(B >= 0, "%s: negative batch size", who);
   if (B == 0) return TRS_OK;
-  TRS_REQUIRE(user_dev && items_dev, "%s: user/item ids are NULL", who);
-  TRS_REQUIRE(M == 0 || meta_dev, "%s: metadata ids are NULL but M=%d", who, M);
   MultiArgs a = {};
   a.T = *tables;
   a.user = user_dev;
@@ -478,4 +747,40 @@ extern "C" int trs_score_multi_fwd_bwd(int net, const trs_tables* tables, const 
     return sm ? launch_multi<TRS_NET_FM, true>(a, (hipStream_t)stream) : launch_multi<TRS_NET_FM, false>(a, (hipStream_t)stream);
   return sm ? launch_multi<TRS_NET_LINEAR, true>(a, (hipStream_t)stream)
             : launch_multi<TRS_NET_LINEAR, false>(a, (hipStream_t)stream);
+}
+
+extern "C" int trs_score_warp_fwd_bwd(int net, const trs_tables* tables, const int32_t* user_dev,
+                                      const int32_t* items_dev, const int32_t* meta_dev, int64_t B, int32_t M,
+                                      int32_t K, float margin, const float* rank_weight_dev, float inv_B,
+                                      float* loss_sum_dev, int32_t* auc_count_dev, int32_t* neg_out,
+                                      int32_t* neg_meta_out, int32_t* trials_out, float* grad_rows_dev,
+                                      float* grad_lin_dev, int32_t* err_flag_dev, void* stream) {
+  const char* who = "trs_score_warp_fwd_bwd";
+  TRS_TRY(check_multi_args(who, net, tables, user_dev, items_dev, meta_dev, B, M, K, loss_sum_dev, grad_rows_dev,
+                           grad_lin_dev));
+  TRS_REQUIRE(margin >= -3.0e38f && margin <= 3.0e38f, "%s: margin must be finite", who);
+  TRS_REQUIRE(rank_weight_dev, "%s: rank_weight is NULL", who);
+  TRS_REQUIRE(neg_out, "%s: neg_out is NULL", who);
+  TRS_REQUIRE(M == 0 || neg_meta_out, "%s: neg_meta_out is NULL but M=%d", who, M);
+  if (B == 0) return TRS_OK;
+  WarpArgs a = {};
+  a.T = *tables;
+  a.user = user_dev;
+  a.items = items_dev;
+  a.meta = meta_dev;
+  a.B = B;
+  a.Kn = K;
+  a.margin = margin;
+  a.inv_B = inv_B;
+  a.rank_weight = rank_weight_dev;
+  a.loss_sum = loss_sum_dev;
+  a.auc_count = auc_count_dev;
+  a.neg_out = neg_out;
+  a.neg_meta_out = neg_meta_out;
+  a.trials_out = trials_out;
+  a.grad_rows = grad_rows_dev;
+  a.grad_lin = grad_lin_dev;
+  a.err = err_flag_dev;
+  if (net == TRS_NET_FM) return launch_warp<TRS_NET_FM>(a, (hipStream_t)stream);
+  return launch_warp<TRS_NET_LINEAR>(a, (hipStream_t)stream);
 }

@@ -480,13 +480,22 @@ class SparseScorerTrainer:
                           grad_rows=gr, grad_lin=gl, loss=self.loss_id)
         if ev is not None:
             e1.record()
+        self._apply_pair_rows(ids, T, Bt, gr, gl, (e0, e1, e2) if ev is not None else None)
+
+    def _apply_pair_rows(self, ids, T, Bt, gr, gl, events=None):
+        """The row updates of one step from gradients staged in trs_score_fwd_bwd's order (R = 3 + 2M fields) for the
+        triples `ids` / `Bt`: the fused scatter for single-lr SGD, the per-table scatter / coalescing rules otherwise,
+        sparse COO gradients + optimizer.step() for the rest.  events: step()'s three timing events (bench.py)."""
+        net = self.net
         if self.kind == "sgd":
             groups = [_group_of(self.opt, p) for p in self.params]
             lrs = {g["lr"] for g in groups}
             if len(lrs) == 1:
                 ops.score_sgd_update(net.NET, T, Bt, gr, gl, lrs.pop())
-                if ev is not None:
+                if events is not None:
+                    e0, e1, e2 = events
                     e2.record()
+                    ev = self.kernel_events
                     ev.setdefault("score_kernel<fwd_bwd>", []).append((e0, e1))
                     ev.setdefault("score_sgd_update_kernel", []).append((e1, e2))
             else:
@@ -583,6 +592,32 @@ class SparseScorerTrainer:
                 fn(ps[4 + M + m], midx, gl[sl].reshape(S1 * B, 1), 1)
         if self.kind not in ("sgd", "sparse_adam", "adagrad"):
             self.opt.step()
+
+    # WARP (fit(loss='warp')): (K, margin, (K,) fp32 device table of rank weights), set by fit()
+    warp = None
+
+    def warp_step(self, ids, loss_slot):
+        """One WARP step on rows of one positive and K candidates: ids = ops.batch_prepare_multi's blocks.  One kernel
+        finds every row's first margin violator and stages the gradients of (user, positive, that candidate) into the
+        (R, B, D) views step() owns, weighted by the rank estimate; the row updates are then exactly step()'s, on the
+        triples (user, slot 0, chosen candidate).  loss_slot receives the SUM of the row losses.  No host sync."""
+        K, margin, weights = self.warp
+        B, M = ids["user"].shape[0], self.M
+        if getattr(self, "_warp_neg", None) is None:
+            self._warp_neg = torch.empty(self.cap, dtype=torch.int32, device=self.dev)
+            self._warp_neg_meta = torch.empty((self.cap, M), dtype=torch.int32, device=self.dev) if M else None
+        neg = self._warp_neg[:B]
+        neg_meta = self._warp_neg_meta.view(-1)[:B * M].view(B, M) if M else None
+        gr, gl = self._views(B)
+        T = self.net.tables()
+        ops.score_warp_fwd_bwd(self.net.NET, T, ids["user"], ids["items"], ids.get("meta"), margin, weights, loss_slot,
+                               None, neg, neg_meta, None, gr, gl, self.err, want_trials=False)
+        triple = {"user": ids["user"], "pos": ids["items"][0], "neg": neg}
+        if M:
+            triple["pos_meta"], triple["neg_meta"] = ids["meta"][0], neg_meta
+        Bt, keep = ops.make_batch(triple["user"], triple["pos"], neg, triple.get("pos_meta"), triple.get("neg_meta"),
+                                  self.err)
+        self._apply_pair_rows(triple, T, Bt, gr, gl)
 
     @staticmethod
     def _set_sparse_grad(p, idx, vals, ld):

@@ -363,7 +363,7 @@ class TorchRecSys(torch.nn.Module):
     @_host_side
     def fit(self, optimizer, epochs=10, batch_size=512, profile_epochs: int = 0, sync_tables_every: int = 1,
             sync_bn: bool = False, loss: str = 'hinge', temperature: float = 1.0, logq_correction: bool = False,
-            n_negatives: int = 1):
+            n_negatives: int = 1, margin: float = 1.0, rank_weight: str = 'log'):
         """Fits the model (reference model.py:203-288).  Per step: [shuffle slice + negative sampling] -> fused
         gather + scoring + hinge + backward -> sparse-row optimiser update; the loss stays on the device and is
         read back once per epoch (the reference syncs every step, model.py:200).
@@ -415,13 +415,30 @@ class TorchRecSys(torch.nn.Module):
         every gradient from the pre-update tables, then the per-table row updates).  Not with neg_sampling['mine'];
         K > 1 not with loss='softmax'.  evaluate() then reports the same loss on the test split with K candidates drawn by
         the evaluation sampler's rules; AUC stays pairwise on (p, c_0).  Under torch.distributed every rank draws and
-        trains on its own replica: nothing new crosses ranks."""
+        trains on its own replica: nothing new crosses ranks.
+
+        loss='warp' with n_negatives=K (1..64), margin (> 0, default 1) and rank_weight ('log' | 'harmonic'; Linear and
+        FM, rng='device' with dynamic_neg_sampling=True): WARP, the Weighted Approximate-Rank Pairwise loss of
+        WSABIE (Weston et al. 2011), LightFM's default ranking loss.  The row's candidates c_0 .. c_{K-1} are those of
+        n_negatives=K above (c_0 the negative a plain run draws; popularity / reject_seen / max_tries / `k` visits
+        compose unchanged).  With z the scorer's value (Linear the score, FM the argument of its sigmoid, as sampled
+        softmax, mining and retrieval use — on FM's sigmoid, whose values lie in (0, 1), a margin of 1 is always violated
+        and WARP would degenerate to a constant weight), candidate j violates iff h_j = (z(u,c_j) - z(u,p)) + margin > 0.
+        The row trains on the FIRST violator c_J alone: its loss is w_J * h_J, 0 when no candidate violates.  w_J is the
+        rank estimate from the J + 1 draws it took: with r = floor((n_items - 1) / (J + 1)), 'log' gives log(max(1, r))
+        (LightFM's form), 'harmonic' sum_{i=1..r} 1 / i (Weston's); no clipping.  n_items - 1 is used whatever the
+        sampler's options are: popularity or seen rejection make the estimate approximate.  Badly ranked rows take large
+        steps, rows already ranked well none.  Every optimiser and metadata scorers work; the steps run one by one (one
+        launch draws the ids, one kernel finds the violators and stages the gradients of (user, positive, c_J), then
+        today's row updates).  Not with neg_sampling['mine'], temperature or logq_correction; margin and rank_weight
+        belong to loss='warp' alone.  evaluate() then reports the WARP loss over K candidates drawn by the evaluation
+        sampler's rules; AUC stays pairwise on (p, c_0).  Under torch.distributed nothing new crosses ranks."""
         # loss: 'hinge' = the reference's only loss (helper/loss.py:5-9, model.py:282); 'bpr' = -log sigmoid(pos - neg),
         # the alternative BASELINE.json's north_star names (evaluate() then reports that loss too); 'softmax' = the
         # in-batch softmax (engine.SparseScorerTrainer.softmax_step; not a pair loss, so not in LOSS_ID)
         from ._lib import LOSS_ID, LOSS_SAMPLED_SOFTMAX
-        if loss not in LOSS_ID and loss not in ('softmax', 'sampled_softmax'):
-            raise ValueError(f"loss must be one of {sorted(list(LOSS_ID) + ['softmax', 'sampled_softmax'])}")
+        if loss not in LOSS_ID and loss not in ('softmax', 'sampled_softmax', 'warp'):
+            raise ValueError(f"loss must be one of {sorted(list(LOSS_ID) + ['softmax', 'sampled_softmax', 'warp'])}")
         if isinstance(n_negatives, bool) or not isinstance(n_negatives, (int, np.integer)) or not 1 <= n_negatives <= 64:
             raise ValueError(f"n_negatives must be an integer in 1..64, got {n_negatives!r}")
         n_negatives = int(n_negatives)
@@ -429,8 +446,22 @@ class TorchRecSys(torch.nn.Module):
         if loss == 'softmax' and n_negatives > 1:
             raise ValueError("n_negatives > 1 does not combine with loss='softmax' (its negatives are the batch's other "
                              "positives); loss='sampled_softmax' is the softmax over sampled negatives")
-        if multineg:
-            what = "loss='sampled_softmax'" if loss == 'sampled_softmax' else f"n_negatives={n_negatives}"
+        warp = loss == 'warp'
+        if warp:
+            multineg = False  # (the same candidates, its own kernel and step: engine.SparseScorerTrainer.warp_step)
+            try:
+                margin = float(margin)
+            except (TypeError, ValueError):
+                raise ValueError(f"margin must be a positive finite number, got {margin!r}") from None
+            if not (math.isfinite(margin) and margin > 0):
+                raise ValueError(f"margin must be a positive finite number, got {margin!r}")
+            if rank_weight not in ('log', 'harmonic'):
+                raise ValueError(f"rank_weight must be 'log' or 'harmonic', got {rank_weight!r}")
+        elif margin != 1.0 or rank_weight != 'log':
+            raise ValueError("margin and rank_weight apply to loss='warp' only")
+        if multineg or warp:
+            what = ("loss='warp'" if warp else
+                    "loss='sampled_softmax'" if loss == 'sampled_softmax' else f"n_negatives={n_negatives}")
             if self.net_type not in ('linear', 'fm'):
                 raise ValueError(f"{what} trains the Linear and FM scorers (net_type 'linear' or 'fm'), not "
                                  f"net_type={self.net_type!r}")
@@ -440,6 +471,9 @@ class TorchRecSys(torch.nn.Module):
             if not self.dynamic_neg_sampling:
                 raise ValueError(f"{what} needs dynamic_neg_sampling=True (there is one static negative per row)")
             if (getattr(self, 'neg_sampling', None) or {}).get('mine') is not None:
+                if warp:
+                    raise ValueError(f"{what} trains on the first violator among its candidates: it does not combine "
+                                     "with neg_sampling['mine'] (which picks by score)")
                 raise ValueError(f"{what} trains on every candidate: it does not combine with neg_sampling['mine'] "
                                  "(which trains on one of them)")
             if logq_correction:
@@ -471,10 +505,16 @@ class TorchRecSys(torch.nn.Module):
         elif multineg:  # K sampled negatives per positive: engine.SparseScorerTrainer.multineg_step
             self._multineg = (n_negatives, LOSS_ID.get(loss, LOSS_SAMPLED_SOFTMAX), tau if loss == 'sampled_softmax' else 1.0)
             runner.trainer.multineg = self._multineg
+        elif warp:  # the first margin violator among K candidates: engine.SparseScorerTrainer.warp_step
+            self._warp = (n_negatives, margin, rank_weight)
+            runner.trainer.warp = (n_negatives, margin,
+                                   ops.warp_rank_weights(self.n_items, n_negatives, rank_weight, _device()))
         else:
             runner.trainer.loss_id = LOSS_ID[loss]
         if not multineg:
             self._multineg = None
+        if not warp:
+            self._warp = None
         self.loss = loss
         for epoch in range(epochs):
             self.net = self.net.train()
@@ -561,15 +601,18 @@ class TorchRecSys(torch.nn.Module):
         softmax = getattr(self, "loss", "hinge") == "softmax" and hasattr(self.net, 'table_params')
         multineg = getattr(self, "_multineg", None) if hasattr(self.net, 'table_params') else None
         multineg = multineg if self.rng == 'device' else None
+        warp = getattr(self, "_warp", None) if hasattr(self.net, 'table_params') and self.rng == 'device' else None
         if multineg is not None:
             self._evaluate_multineg(multineg, st, sample_seed, nb, batch_size, n_test, loss_sums, auc_counts)
+        if warp is not None:
+            self._evaluate_warp(warp, st, sample_seed, nb, batch_size, n_test, loss_sums, auc_counts)
         group = 64 if hasattr(self.net, 'table_params') and not softmax else 1
         group = max(1, min(group, (1 << 22) // max(batch_size, 1)))
         if softmax:
             sm_loss = torch.zeros(nb, dtype=torch.float32, device=dev)
             sm = ops.InBatchSoftmax(min(batch_size, n_test), self.n_factors, dev)
             err = torch.zeros(1, dtype=torch.int32, device=dev)
-        for b0 in (range(0, nb, group) if multineg is None else ()):  # (the pair / in-batch softmax batches)
+        for b0 in (range(0, nb, group) if multineg is None and warp is None else ()):  # (the pair / in-batch softmax batches)
             b1 = min(b0 + group, nb)
             s, e = b0 * batch_size, min(b1 * batch_size, n_test)
             if self.rng == 'reference':
@@ -622,6 +665,25 @@ class TorchRecSys(torch.nn.Module):
             ops.score_multi_fwd_bwd(self.net.NET, self.net.tables(), ids['user'], ids['items'], ids.get('meta'),
                                     loss_id, tau, loss_sums[b:b + 1], auc_counts[b:b + 1], err_flag=err,
                                     forward_only=True)
+        check_err_flag(err, "evaluate")
+
+    def _evaluate_warp(self, warp, st, sample_seed, nb, batch_size, n_test, loss_sums, auc_counts):
+        """evaluate() after fit(loss='warp'): the WARP loss over K candidates of the evaluation sampler's rules, one test
+        batch per forward-only launch; the AUC count is pairwise on (p, c_0)."""
+        K, margin, kind = warp
+        weights = ops.warp_rank_weights(self.n_items, K, kind, loss_sums.device)
+        err = torch.zeros(1, dtype=torch.int32, device=loss_sums.device)
+        out = None
+        for b in range(nb):
+            s, e = b * batch_size, min((b + 1) * batch_size, n_test)
+            ids = ops.batch_prepare_multi(st['user'], st['pos'], 0, s, e - s, self.n_items, sample_seed, s, K,
+                                          st['item_meta'], out if e - s == batch_size else None,
+                                          sampler=self._eval_sampler())
+            if e - s == batch_size:
+                out = ids
+            ops.score_warp_fwd_bwd(self.net.NET, self.net.tables(), ids['user'], ids['items'], ids.get('meta'), margin,
+                                   weights, loss_sums[b:b + 1], auc_counts[b:b + 1], err_flag=err, forward_only=True,
+                                   want_trials=False)
         check_err_flag(err, "evaluate")
 
     # ------------------------------------------------------------------------------------------------ predict
@@ -952,6 +1014,9 @@ class FitRunner:
         # K sampled negatives per positive: a prepare launch, then the staging kernel and the per-table row updates
         multineg = getattr(self.trainer, "multineg", None)
         fast = fast and multineg is None
+        # WARP: the same prepare launch (K candidates per row), then the kernel that picks the first violator + the step's tail
+        warp = getattr(self.trainer, "warp", None)
+        fast = fast and warp is None
         if fast and m.rng == 'reference':
             fast = self.ep['user'].dtype == torch.int32
         ops.stamp("run_steps:setup")
@@ -995,9 +1060,9 @@ class FitRunner:
             else:
                 st = self.st
                 out = self.prep_out if (self.prep_out is not None and e - s == B) else None
-                if multineg is not None:
+                if multineg is not None or warp is not None:
                     ids = ops.batch_prepare_multi(st['user'], st['pos'], self.shuffle_key, s, e - s, m.n_items,
-                                                  self.sample_seed, s, multineg[0], st['item_meta'], out,
+                                                  self.sample_seed, s, (multineg or warp)[0], st['item_meta'], out,
                                                   sampler=self.sampler)
                 elif mining:  # K candidates scored under the tables as step b - 1 left them, one launch on this stream
                     ids = ops.batch_prepare_mined(st['user'], st['pos'], self.shuffle_key, s, e - s, m.n_items,
@@ -1012,6 +1077,8 @@ class FitRunner:
                 self.trainer.softmax_step(ids, self.loss_sums[b:b + 1])
             elif multineg is not None:
                 self.trainer.multineg_step(ids, self.loss_sums[b:b + 1])
+            elif warp is not None:
+                self.trainer.warp_step(ids, self.loss_sums[b:b + 1])
             else:
                 self.trainer.step(ids, self.loss_sums[b:b + 1])
             self.next_batch += 1

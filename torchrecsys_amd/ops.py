@@ -618,6 +618,79 @@ def score_multi_fwd_bwd(net, T, user, items, meta, loss, tau, loss_sum, auc_coun
     return grad_rows, grad_lin
 
 
+_warp_weights = {}  # (n_items, K, kind, device) -> (K,) fp32 table of warp_rank_weights
+
+
+def warp_rank_weight_values(n_items, K, kind="log"):
+    """The K float64 rank weights of WARP, entry N - 1 for a row whose first violator came at draw N: with
+    r_N = floor((n_items - 1) / N), 'log' gives log(max(1, r_N)) (LightFM's form), 'harmonic' sum_{i=1..r_N} 1 / i
+    (Weston et al. 2011).  n_items - 1 < N gives 0.  n_items - 1 is used whatever the sampler's options are: popularity
+    or seen rejection make the rank estimate approximate."""
+    import numpy as np
+    if kind not in ("log", "harmonic"):
+        raise ValueError(f"rank_weight must be 'log' or 'harmonic', got {kind!r}")
+    r = (int(n_items) - 1) // np.arange(1, int(K) + 1, dtype=np.int64)
+    if kind == "log":
+        return np.log(np.maximum(r, 1).astype(np.float64))
+    H = np.concatenate([[0.0], np.cumsum(1.0 / np.arange(1, max(int(r.max()), 1) + 1, dtype=np.float64))])
+    return H[np.maximum(r, 0)]
+
+
+def warp_rank_weights(n_items, K, kind="log", device=None):
+    """(K,) fp32 device table of warp_rank_weight_values (float64 on the host, rounded to fp32), cached per
+    (n_items, K, kind) and device."""
+    key = (int(n_items), int(K), kind, str(device))
+    if key not in _warp_weights:
+        w = warp_rank_weight_values(n_items, K, kind)
+        _warp_weights[key] = torch.from_numpy(w.astype("float32")).to(device)
+    return _warp_weights[key]
+
+
+def score_warp_fwd_bwd(net, T, user, items, meta, margin, rank_weight, loss_sum, auc_count=None, neg_out=None,
+                       neg_meta_out=None, trials_out=None, grad_rows=None, grad_lin=None, err_flag=None,
+                       forward_only=False, inv_B=None, want_trials=True):
+    """WARP over rows of one positive and K = items.shape[0] - 1 candidates (trs_score_warp_fwd_bwd): the first
+    candidate j with (z_j - z_p) + margin > 0 is trained on, weighted by rank_weight[j] ((K,) fp32 on the device).
+    user (B,), items (1 + K, B), meta (1 + K, B, M) or None: int32, the blocks of batch_prepare_multi.  loss_sum /
+    auc_count are accumulated in place.  Returns (neg (B,), neg_meta (B, M) or None, trials (B,) or None, grad_rows
+    (3 + 2M, B, D), grad_lin (3 + 2M, B)) — the staging order of score_fwd_bwd on (user, items[0], neg); the last two
+    are None with forward_only."""
+    _dev(user, "user ids", torch.int32)
+    _dev(items, "item id block", torch.int32)
+    _dev(meta, "metadata id block", torch.int32)
+    _dev(rank_weight, "rank_weight", torch.float32)
+    if items.dim() != 2 or items.shape[1] != user.shape[0] or items.shape[0] < 2:
+        raise ValueError("items must be the (1 + K, B) block of batch_prepare_multi")
+    B, K, D, M = user.shape[0], items.shape[0] - 1, T.D, T.M
+    if M and (meta is None or tuple(meta.shape) != (1 + K, B, M)):
+        raise ValueError(f"meta must be the (1 + K, B, M) = ({1 + K}, {B}, {M}) block of batch_prepare_multi")
+    if rank_weight is None or rank_weight.numel() != K:
+        raise ValueError(f"rank_weight must hold K = {K} floats")
+    dev = user.device
+    if neg_out is None:
+        neg_out = torch.empty(B, dtype=torch.int32, device=dev)
+    if M and neg_meta_out is None:
+        neg_meta_out = torch.empty((B, M), dtype=torch.int32, device=dev)
+    if trials_out is None and want_trials:
+        trials_out = torch.empty(B, dtype=torch.int32, device=dev)
+    if forward_only:
+        grad_rows = grad_lin = None
+    else:
+        R = 3 + 2 * M
+        if grad_rows is None:
+            grad_rows = torch.empty((R, B, D), dtype=torch.float32, device=dev)
+        if grad_lin is None:
+            grad_lin = torch.empty((R, B), dtype=torch.float32, device=dev)
+    if inv_B is None:
+        inv_B = 1.0 / B if B > 0 else 0.0
+    check(_lib.load().trs_score_warp_fwd_bwd(NET_ID[net], C.byref(T), ptr(user), ptr(items), ptr(meta) if M else None,
+                                             B, M, K, float(margin), ptr(rank_weight), float(inv_B), ptr(loss_sum),
+                                             ptr(auc_count), ptr(neg_out), ptr(neg_meta_out) if M else None,
+                                             ptr(trials_out), ptr(grad_rows), ptr(grad_lin), ptr(err_flag), _stream()),
+          "trs_score_warp_fwd_bwd")
+    return neg_out, (neg_meta_out if M else None), trials_out, grad_rows, grad_lin
+
+
 def score_all_items(net, T, user_id, n_items, device, item_meta=None, item0=0, n=None):
     n = n_items - item0 if n is None else n
     out = torch.empty(n, dtype=torch.float32, device=device)
