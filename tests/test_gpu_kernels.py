@@ -86,7 +86,7 @@ def dense_from_staging(net, p, batch, grad_rows, grad_lin):
 CASES = [("fm", 64, 0), ("fm", 8, 0), ("fm", 16, 1), ("fm", 128, 3), ("fm", 80, 0), ("fm", 10, 1), ("fm", 256, 0),
          ("fm", 512, 1), ("fm", 4, 0), ("fm", 1, 0), ("fm", 100, 2), ("fm", 33, 0),
          ("linear", 32, 0), ("linear", 8, 1), ("linear", 64, 3), ("linear", 80, 0), ("linear", 7, 2),
-         ("linear", 1024, 0)]
+         ("linear", 1024, 0), ("fm", 201, 0)]
 
 
 @pytest.mark.parametrize("net,D,M", CASES)
@@ -152,9 +152,10 @@ def test_sgd_update_three_steps(net, D, M):
         assert rel_err(t[k].cpu().numpy(), v) < TOL, k
 
 
-@pytest.mark.parametrize("D", [1, 16, 64, 80, 200])
+@pytest.mark.parametrize("D", [1, 16, 64, 80, 200, 3, 7, 12, 40])
 @pytest.mark.parametrize("kind", ["adam", "adagrad"])
 def test_coalescing_row_optimisers(D, kind):
+    """(the last four widths complete the lanes-per-row classes of csrc/rows.hip: 1, 4, 8, 16, 32, 64)"""
     ops = _ops()
     rs = np.random.RandomState(D)
     n_rows, n = 40, 150
@@ -186,6 +187,73 @@ def test_coalescing_row_optimisers(D, kind):
     assert rel_err(tW.cpu().numpy(), ref) < 5e-5
     assert np.array_equal(tW.cpu().numpy()[n_rows // 2:], W[n_rows // 2:])  # lazy: untouched rows bit-identical
     assert rel_err(s1.cpu().numpy(), m) < 5e-5
+
+
+LPR_WIDTHS = [1, 3, 7, 12, 40, 64, 200]  # one width per lanes-per-row class of csrc/rows.hip: 1, 4, 8, 16, 32, 64, 64 x 4
+
+
+@pytest.mark.parametrize("n,cap", [(150, None), (1, None), (1000, 1)])
+@pytest.mark.parametrize("D", LPR_WIDTHS)
+@pytest.mark.parametrize("kind", ["adam", "adagrad"])
+def test_row_optimisers_int32_ids_strided_values_and_ids_out_of_range(kind, D, n, cap, tune):
+    """trs_rows_scatter_add with int32 ids, values that are a column slice of a wider buffer (ld > D) and alpha = -0.5,
+    then the two apply kernels, 2 steps.  Table, accumulator and both moments are rows [1:-1] of buffers with a guard row
+    at each end; the ids -1 and n_rows (the guard rows' positions) raise err_flag, are skipped by the scatter AND by the
+    apply kernels, and leave every row they do not name bit-identical.  n = 1: a single element; n = 1000 with one
+    workgroup: every wave runs many iterations of the owner election."""
+    ops = _ops()
+    if cap is not None:
+        tune(GRID_CAP=cap)
+    rs = np.random.RandomState(D + n)
+    n_rows, GUARD = 40, np.float32(12345.0)
+
+    def guarded(init):
+        buf = torch.full((n_rows + 2, D), float(GUARD), device=DEV)
+        buf[1:-1] = torch.from_numpy(init).to(DEV)
+        return buf, buf[1:-1]
+
+    W = rs.normal(0, 1, (n_rows, D)).astype(np.float32)
+    zeros = np.zeros_like(W)
+    (bW, tW), (bacc, acc), (bs1, s1), (bs2, s2) = guarded(W.copy()), guarded(zeros), guarded(zeros), guarded(zeros)
+    idx = rs.randint(0, n_rows // 2, n).astype(np.int32)  # rows >= n_rows/2 stay untouched
+    idx[0] = 0
+    bad = n >= 3
+    if bad:
+        idx[1], idx[2] = -1, n_rows
+    good = (idx >= 0) & (idx < n_rows)
+    tidx = torch.from_numpy(idx).to(DEV)
+    stamp = torch.zeros(n_rows, dtype=torch.int32, device=DEV)
+    err = torch.zeros(1, dtype=torch.int32, device=DEV)
+    ref, m, v = W.copy(), np.zeros_like(W), np.zeros_like(W)
+    rows = np.unique(idx[good])
+    for step in (1, 2):
+        wide = rs.normal(0, 1, (n, D + 5)).astype(np.float32)
+        twide = torch.from_numpy(wide).to(DEV)
+        ops.rows_scatter_add(acc, tidx, twide[:, 2:2 + D], -0.5, err_flag=err)
+        G = np.zeros(W.shape, np.float64)
+        np.add.at(G, idx[good], -0.5 * wide[good, 2:2 + D].astype(np.float64))
+        torch.cuda.synchronize()
+        assert err.item() == (1 if bad else 0)
+        assert rel_err(acc.cpu().numpy(), G) < 1e-6
+        G = acc.cpu().numpy().copy()  # the optimiser's input: the accumulator as the device summed it
+        if kind == "adam":
+            ops.rows_apply_sparse_adam(tW, acc, s1, s2, stamp, tidx, step, 0.01, 0.9, 0.999, 1e-8, step)
+            ooptim.sparse_adam_rows(ref, G, rows, m, v, step, 0.01)
+        else:
+            ops.rows_apply_adagrad(tW, acc, s1, stamp, tidx, step, 0.05, 1e-10)
+            ooptim.adagrad_rows(ref, G, rows, m, step, 0.05)
+        torch.cuda.synchronize()
+        assert float(acc.abs().max()) == 0.0  # accumulator cleared by the owners
+    assert rel_err(tW.cpu().numpy(), ref) < 5e-5
+    assert rel_err(s1.cpu().numpy(), m) < 5e-5
+    untouched = np.ones(n_rows, bool)
+    untouched[rows] = False
+    assert np.array_equal(tW.cpu().numpy()[untouched], W[untouched])  # lazy: untouched rows bit-identical
+    for name, buf in (("table", bW), ("acc", bacc), ("s1", bs1), ("s2", bs2)):
+        ends = buf[[0, -1]].cpu().numpy()
+        assert (ends == GUARD).all(), f"{name}: a guard row was written"
+        if name != "table":
+            assert not buf[1:-1].cpu().numpy()[untouched].any(), name
 
 
 def test_out_of_range_ids_are_flagged_not_dereferenced():
@@ -859,10 +927,12 @@ def test_colsum_rowdot_outer_gather():
 
 @pytest.mark.parametrize("net,D", [("fm", 64), ("fm", 8), ("fm", 128), ("fm", 80), ("fm", 10), ("linear", 32),
                                    ("linear", 256), ("linear", 7), ("fm", 512), ("fm", 1024), ("linear", 3),
-                                   ("fm", 201)])
+                                   ("fm", 201), ("linear", 12), ("fm", 33)])
 def test_fast_sgd_step_matches_oracle_and_generic_path(net, D):
     """csrc/fast_step.hip (3-kernel exact SGD step, ids given) vs the oracle and vs the generic staged path.  The last
-    four widths are the row shapes (4,64,2), (4,64,4), (1,4,1) and (1,64,4) of csrc/score_kernels.h's table."""
+    six widths are the row shapes (4,64,2), (4,64,4), (1,4,1), (1,64,4), (4,4,1) and (1,64,1) of csrc/score_kernels.h's
+    table; with the widths before them every shape of the table is met (tests/test_gpu_row_shapes.py: every shape, ragged
+    and full, on every path)."""
     ops = _ops()
     B, lr = 777, 0.05
     p, batch, _ = make_case(net, D, 0, B, NU=90, NI=41, seed=D)
