@@ -99,7 +99,7 @@ const char* trs_last_error(void);
  *   6: batched top-k retrieval: trs_csr, trs_item_fold(_bytes), trs_retrieve_topk, trs_retrieve_workspace_bytes,
  *      trs_mask_seen, trs_rank_metrics.  (Entry points added since without touching an existing signature or struct:
  *      the in-batch softmax group, trs_batch_prepare_mined, trs_batch_prepare_multi, trs_score_multi_fwd_bwd,
- *      trs_score_warp_fwd_bwd, TRS_LOSS_WARP.) */
+ *      trs_score_warp_fwd_bwd, TRS_LOSS_WARP, trs_stage_add_l2.) */
 #define TRS_ABI_VERSION 6
 #define TRS_SYNC_WORDS 288
 int trs_abi_version(void);
@@ -271,6 +271,29 @@ int trs_score_warp_fwd_bwd(int net, const trs_tables* tables, const int32_t* use
                            const float* rank_weight_dev, float inv_B, float* loss_sum_dev, int32_t* auc_count_dev,
                            int32_t* neg_out, int32_t* neg_meta_out, int32_t* trials_out, float* grad_rows_dev,
                            float* grad_lin_dev, int32_t* err_flag_dev, void* stream);
+
+/* Per-sample L2 regularisation of the embedding rows a batch references: one pass over the field-major
+ * staging buffer of a Linear / FM step, after the staging kernel and before the first row update, so the rows it reads
+ * are the PRE-update tables'.  Ids are the blocks of trs_batch_prepare_multi, int32: user (B), items (S, B), meta
+ * (S, B, M).  Fields, F = 1 + S(1+M): grad_rows (F, B, D) and grad_lin (F, B); field 0 the user, field 1+s the item of
+ * slot s, field 1+S+m*S+s metadata column m of slot s — S = 1 is the in-batch softmax's buffer, S = 2 a pair's or the
+ * WARP triple's (trs_score_fwd_bwd's order), S = 1+K trs_score_multi_fwd_bwd's.  For every reference (f, t) with id r
+ * in the table of its group (user / item / metadata):
+ *   grad_rows[f, t, :] = grad_rows[f, t, :] + c_group * W[r, :]     (the product, then the sum: two fp32 roundings)
+ *   grad_lin[f, t]     = grad_lin[f, t]     + c_group * w[r]        (w: the 1-wide table with the same ids)
+ * c_user / c_item / c_meta already contain the 1/B of the batch mean.  A row referenced n times in the batch receives
+ * the term n times, once per staged reference; every staged row has one writer (no float atomics).  One launch covers
+ * every reference of every group whose coefficient is not 0.  A group whose coefficient is exactly 0 is skipped
+ * entirely: its fields are neither read nor written and its table is not gathered.  Linear has no 1-wide metadata
+ * tables: those grad_lin fields are not touched.  Elements of the buffers beyond the F fields are not touched.
+ * An id outside its table is not used as an address: its reference gets nothing added and bit 0 of *err_flag_dev (may
+ * be NULL) is set.  B == 0, or every coefficient 0: TRS_OK, nothing launched.
+ * TRS_E_ARG, nothing launched: tables NULL or a NULL member; net not TRS_NET_LINEAR / TRS_NET_FM; S outside 1..65;
+ * M != tables->M; a D the scorer kernels do not take; a coefficient negative or not finite; grad_rows or grad_lin NULL;
+ * NULL ids with B > 0; meta_dev NULL with M > 0 and c_meta > 0. */
+int trs_stage_add_l2(int net, const trs_tables* tables, const int32_t* user_dev, const int32_t* items_dev,
+                     const int32_t* meta_dev, int64_t B, int32_t S, int32_t M, float c_user, float c_item, float c_meta,
+                     float* grad_rows_dev, float* grad_lin_dev, int32_t* err_flag_dev, void* stream);
 
 /* ------------------------------------------------------------------ scorers: forward only (a2, a3, a6) */
 /* Fused positive+negative scoring pass; the user row is gathered once for both passes.

@@ -135,6 +135,7 @@ PROTOTYPES = {
                                           _vp, _vp, _vp]),
     "trs_score_warp_fwd_bwd": (C.c_int, [C.c_int, _T, _vp, _vp, _vp, _i64, _i32, _i32, _f, _vp, _f, _vp, _vp, _vp, _vp,
                                          _vp, _vp, _vp, _vp, _vp]),
+    "trs_stage_add_l2": (C.c_int, [C.c_int, _T, _vp, _vp, _vp, _i64, _i32, _i32, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "trs_score_forward": (C.c_int, [C.c_int, _T, _Bp, _vp, _vp, _vp]),
     "trs_score_fwd_bwd": (C.c_int, [C.c_int, _T, _Bp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "trs_score_backward": (C.c_int, [C.c_int, _T, _Bp, _vp, _vp, _vp, _vp, _vp]),

@@ -460,7 +460,8 @@ class SparseScorerTrainer:
         the SUM of the batch's hinge terms (caller divides by B)."""
         B = ids["user"].shape[0]
         net = self.net
-        if self.fast_kind == "sgd" and self.M == 0 and auc_slot is None and ids["user"].dtype == torch.int32:
+        if (self.fast_kind == "sgd" and self.M == 0 and auc_slot is None and ids["user"].dtype == torch.int32
+                and self.l2 is None):  # (the one-launch step stages nothing a penalty could be added to)
             te, evs, ns = self._make_events(1) if self.kernel_events is not None else (None, None, 0)
             ops.train_steps_sgd(net.NET, net.tables(), None, None, 0, 0, 0, B, 1, self.fast_lr, ids["user"],
                                 ids["pos"], ids["neg"], self.gz, self.du, loss_slot, self.err, self.scratch,
@@ -478,9 +479,34 @@ class SparseScorerTrainer:
             e0.record()
         ops.score_fwd_bwd(net.NET, T, Bt, B, self.D, self.M, self.dev, loss_slot, auc_slot, want_scores=False,
                           grad_rows=gr, grad_lin=gl, loss=self.loss_id)
+        self._add_l2_pair(ids, gr, gl)
         if ev is not None:
             e1.record()
         self._apply_pair_rows(ids, T, Bt, gr, gl, (e0, e1, e2) if ev is not None else None)
+
+    # per-sample L2 regularisation (fit(l2=...)): None | (lambda_user, lambda_item, lambda_metadata), set by fit()
+    l2 = None
+
+    def _add_l2(self, user, items, meta, gr, gl):
+        """fit(l2=...): adds lambda_group / B times the pre-update row of every staged reference to its staged gradient
+        (ops.stage_add_l2, one launch) — between a step's staging kernel and its first row update, so the penalised
+        gradient goes through the optimiser's rule like any other.  items (S, B), meta (S, B, M): int32 blocks in the
+        staging buffer's slot order."""
+        if self.l2 is None:
+            return
+        inv_B = 1.0 / user.shape[0]
+        ops.stage_add_l2(self.net.NET, self.net.tables(), user, items, meta, [lam * inv_B for lam in self.l2], gr, gl,
+                         self.err)
+
+    def _add_l2_pair(self, ids, gr, gl):
+        """_add_l2 for triples (user, pos, neg) staged in trs_score_fwd_bwd's order: S = 2, one stack per id block (the
+        reference-RNG path carries int64 ids)."""
+        if self.l2 is None:
+            return
+        i32 = torch.int32
+        items = torch.stack([ids["pos"], ids["neg"]]).to(i32)
+        meta = torch.stack([ids["pos_meta"], ids["neg_meta"]]).to(i32) if self.M else None
+        self._add_l2(ids["user"].to(i32), items, meta, gr, gl)
 
     def _apply_pair_rows(self, ids, T, Bt, gr, gl, events=None):
         """The row updates of one step from gradients staged in trs_score_fwd_bwd's order (R = 3 + 2M fields) for the
@@ -529,6 +555,10 @@ class SparseScorerTrainer:
         T = net.tables()
         Bt, keep = ops.make_batch(ids["user"], ids["pos"], None, ids.get("pos_meta"), None, self.err)
         self._sm(net.NET, T, Bt, tau, logq, loss_slot, gr, gl, chunk_rows=self.SOFTMAX_CHUNK_ROWS)
+        if self.l2 is not None:  # S = 1: the positives and their metadata, viewed as one-slot blocks
+            i32 = torch.int32
+            self._add_l2(ids["user"].to(i32), ids["pos"].to(i32).view(1, B),
+                         ids["pos_meta"].to(i32).view(1, B, M) if M else None, gr, gl)
         if self.kind == "sgd":
             fn = lambda p, idx, vals, ld: ops.rows_scatter_add(p.data, idx, vals, -_group_of(self.opt, p)["lr"], ld=ld)
         elif self.kind in ("sparse_adam", "adagrad"):
@@ -570,6 +600,7 @@ class SparseScorerTrainer:
         net = self.net
         ops.score_multi_fwd_bwd(net.NET, net.tables(), ids["user"], ids["items"], ids.get("meta"), loss_id, tau,
                                 loss_slot, None, gr, gl, self.err)
+        self._add_l2(ids["user"], ids["items"], ids.get("meta"), gr, gl)
         if self.kind == "sgd":
             fn = lambda p, idx, vals, ld: ops.rows_scatter_add(p.data, idx, vals, -_group_of(self.opt, p)["lr"], ld=ld)
         elif self.kind in ("sparse_adam", "adagrad"):
@@ -581,7 +612,8 @@ class SparseScorerTrainer:
         item_idx = ids["items"].view(-1)  # slot-major, as the staged fields 1 .. 1 + K
         fn(ps[0], ids["user"], gr[0], D)
         fn(ps[1], item_idx, gr[1:1 + S1].reshape(S1 * B, D), D)
-        if loss_id != ops._lib.LOSS_SAMPLED_SOFTMAX:  # (under the softmax that block is exactly 0: nothing to apply)
+        # (under the softmax that block is exactly 0: nothing to apply — unless the user group's penalty was added to it)
+        if loss_id != ops._lib.LOSS_SAMPLED_SOFTMAX or (self.l2 is not None and self.l2[0] > 0):
             fn(ps[2], ids["user"], gl[0].reshape(B, 1), 1)
         fn(ps[3], item_idx, gl[1:1 + S1].reshape(S1 * B, 1), 1)
         for m in range(M):
@@ -617,6 +649,7 @@ class SparseScorerTrainer:
             triple["pos_meta"], triple["neg_meta"] = ids["meta"][0], neg_meta
         Bt, keep = ops.make_batch(triple["user"], triple["pos"], neg, triple.get("pos_meta"), triple.get("neg_meta"),
                                   self.err)
+        self._add_l2_pair(triple, gr, gl)  # (user, positive, chosen candidate) of every row, violator or not
         self._apply_pair_rows(triple, T, Bt, gr, gl)
 
     @staticmethod

@@ -13,6 +13,7 @@ Same constructor keywords, same methods, same printed strings, same state_dict k
 import functools
 import math
 import os
+from collections.abc import Mapping
 from typing import List
 
 import numpy as np
@@ -84,6 +85,34 @@ def _check_mining_options(ns, net_type):
 
     K = integer("candidates", 8, 1, 64)
     integer("top", 1, 1, K)
+
+
+def _check_l2(l2, net_type):
+    """fit(l2=...): None when every coefficient is 0, else (lambda_user, lambda_item, lambda_metadata)."""
+    groups = ('user', 'item', 'metadata')
+
+    def number(v, what):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{what} must be a non-negative finite number, got {v!r}")
+        v = float(v)
+        if not (math.isfinite(v) and v >= 0):
+            raise ValueError(f"{what} must be a non-negative finite number, got {v!r}")
+        return v
+
+    if isinstance(l2, Mapping):
+        for key in l2:
+            if key not in groups:
+                raise ValueError(f"l2 has the unknown key {key!r}: its keys are among {groups}")
+        lam = tuple(number(l2.get(g, 0.0), f"l2[{g!r}]") for g in groups)
+    else:
+        lam = (number(l2, "l2"),) * 3
+    if not any(lam):
+        return None
+    if net_type not in ('linear', 'fm'):
+        raise ValueError("l2 regularises the embedding rows of the Linear and FM scorers (net_type 'linear' or 'fm'): "
+                         f"with net_type={net_type!r} the dense layers take the optimiser's own weight_decay, and its "
+                         "embedding rows are not covered")
+    return lam
 
 
 class TorchRecSys(torch.nn.Module):
@@ -363,7 +392,7 @@ class TorchRecSys(torch.nn.Module):
     @_host_side
     def fit(self, optimizer, epochs=10, batch_size=512, profile_epochs: int = 0, sync_tables_every: int = 1,
             sync_bn: bool = False, loss: str = 'hinge', temperature: float = 1.0, logq_correction: bool = False,
-            n_negatives: int = 1, margin: float = 1.0, rank_weight: str = 'log'):
+            n_negatives: int = 1, margin: float = 1.0, rank_weight: str = 'log', l2=0.0):
         """Fits the model (reference model.py:203-288).  Per step: [shuffle slice + negative sampling] -> fused
         gather + scoring + hinge + backward -> sparse-row optimiser update; the loss stays on the device and is
         read back once per epoch (the reference syncs every step, model.py:200).
@@ -432,7 +461,26 @@ class TorchRecSys(torch.nn.Module):
         launch draws the ids, one kernel finds the violators and stages the gradients of (user, positive, c_J), then
         today's row updates).  Not with neg_sampling['mine'], temperature or logq_correction; margin and rank_weight
         belong to loss='warp' alone.  evaluate() then reports the WARP loss over K candidates drawn by the evaluation
-        sampler's rules; AUC stays pairwise on (p, c_0).  Under torch.distributed nothing new crosses ranks."""
+        sampler's rules; AUC stays pairwise on (p, c_0).  Under torch.distributed nothing new crosses ranks.
+
+        l2=lambda (Linear and FM): per-sample L2 regularisation of the embedding rows a batch touches —
+        LightFM's user_alpha / item_alpha, the lambda of the BPR paper.  A non-negative finite number, or a mapping with
+        keys among 'user', 'item', 'metadata' (missing keys mean 0); a 1-wide table (bias / linear term) takes its
+        group's coefficient.  Per batch of B rows the step minimises
+          (1/B) sum_b [ loss_b + 1/2 sum_{references r of row b} lambda_group(r) (|W_r|^2 + w_r^2) ]
+        where the references of row b are the rows its gradients are staged for: its user, its item slots (the pair, the
+        positive alone under loss='softmax', the positive and all K candidates under n_negatives=K, (positive, chosen
+        candidate) under loss='warp' — c_0 for a row without a violator: the penalty belongs to the reference, not to
+        the violation) and the metadata rows of those slots.  So every staged reference's gradient gains lambda_group / B
+        times its PRE-update row (as loss.backward() before optimizer.step() reads it); a row referenced c times in the
+        batch receives the term c times; 1/B is that of the actual batch, the partial last one included; a row no id of
+        the batch references is left bit-identical.  The penalised gradient goes through the optimiser's rule unchanged
+        (torch's coupled weight_decay semantics, restricted to touched rows).  Combines with every loss, n_negatives,
+        neg_sampling option (mining included), rng and optimiser.  With any coefficient non-zero the steps run one by
+        one on the staged per-step loop (as n_negatives > 1 does), with one more launch per step; all coefficients zero
+        is today's run on today's paths, bit for bit.  The printed training loss stays the data loss without the
+        penalty and evaluate() is unchanged, so runs with and without l2 compare.  Under torch.distributed nothing new
+        crosses ranks.  net_type='mlp': ValueError for any non-zero coefficient."""
         # loss: 'hinge' = the reference's only loss (helper/loss.py:5-9, model.py:282); 'bpr' = -log sigmoid(pos - neg),
         # the alternative BASELINE.json's north_star names (evaluate() then reports that loss too); 'softmax' = the
         # in-batch softmax (engine.SparseScorerTrainer.softmax_step; not a pair loss, so not in LOSS_ID)
@@ -442,6 +490,7 @@ class TorchRecSys(torch.nn.Module):
         if isinstance(n_negatives, bool) or not isinstance(n_negatives, (int, np.integer)) or not 1 <= n_negatives <= 64:
             raise ValueError(f"n_negatives must be an integer in 1..64, got {n_negatives!r}")
         n_negatives = int(n_negatives)
+        l2 = _check_l2(l2, self.net_type)
         multineg = loss == 'sampled_softmax' or n_negatives > 1
         if loss == 'softmax' and n_negatives > 1:
             raise ValueError("n_negatives > 1 does not combine with loss='softmax' (its negatives are the batch's other "
@@ -515,6 +564,8 @@ class TorchRecSys(torch.nn.Module):
             self._multineg = None
         if not warp:
             self._warp = None
+        if l2 is not None:  # engine.SparseScorerTrainer._add_l2: one launch between a step's staging and its row updates
+            runner.trainer.l2 = l2
         self.loss = loss
         for epoch in range(epochs):
             self.net = self.net.train()
@@ -1017,6 +1068,8 @@ class FitRunner:
         # WARP: the same prepare launch (K candidates per row), then the kernel that picks the first violator + the step's tail
         warp = getattr(self.trainer, "warp", None)
         fast = fast and warp is None
+        # per-sample L2 (fit(l2=...)): the penalty is added to the staged gradients, which only the per-step loop has
+        fast = fast and getattr(self.trainer, "l2", None) is None
         if fast and m.rng == 'reference':
             fast = self.ep['user'].dtype == torch.int32
         ops.stamp("run_steps:setup")

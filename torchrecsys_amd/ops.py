@@ -691,6 +691,35 @@ def score_warp_fwd_bwd(net, T, user, items, meta, margin, rank_weight, loss_sum,
     return neg_out, (neg_meta_out if M else None), trials_out, grad_rows, grad_lin
 
 
+def stage_add_l2(net, T, user, items, meta, coefs, grad_rows, grad_lin, err_flag=None):
+    """Adds the per-sample L2 term to a step's staged gradients, in place (trs_stage_add_l2, one launch): for every
+    staged reference, grad_rows[f, t] += c * W[id] and grad_lin[f, t] += c * w[id] from the tables as they are now.
+    user (B,), items (S, B), meta (S, B, M) or None: int32, the blocks of batch_prepare_multi.  coefs = (c_user, c_item,
+    c_meta), each already holding the 1/B of the batch mean; a group at 0 is skipped.  grad_rows (F, B, D) and grad_lin
+    (F, B), F = 1 + S * (1 + M), field-major: the user, the S item slots, then the S slots of every metadata column."""
+    _dev(user, "user ids", torch.int32)
+    _dev(items, "item id block", torch.int32)
+    _dev(meta, "metadata id block", torch.int32)
+    _dev(grad_rows, "grad_rows", torch.float32)
+    _dev(grad_lin, "grad_lin", torch.float32)
+    if items.dim() != 2 or items.shape[1] != user.shape[0] or items.shape[0] < 1:
+        raise ValueError("items must be an (S, B) block of item ids, slot-major")
+    B, S, D, M = user.shape[0], items.shape[0], T.D, T.M
+    c_user, c_item, c_meta = (float(c) for c in coefs)
+    if M and c_meta > 0 and (meta is None or tuple(meta.shape) != (S, B, M)):
+        raise ValueError(f"meta must be the (S, B, M) = ({S}, {B}, {M}) block of metadata ids")
+    F = 1 + S * (1 + M)
+    if grad_rows is None or tuple(grad_rows.shape) != (F, B, D):
+        raise ValueError(f"grad_rows must be the (F, B, D) = ({F}, {B}, {D}) staging buffer")
+    if grad_lin is None or tuple(grad_lin.shape) != (F, B):
+        raise ValueError(f"grad_lin must be the (F, B) = ({F}, {B}) staging buffer")
+    if B == 0:  # (empty buffers have no storage to point at)
+        return
+    check(_lib.load().trs_stage_add_l2(NET_ID[net], C.byref(T), ptr(user), ptr(items), ptr(meta) if M else None, B, S,
+                                       M, c_user, c_item, c_meta, ptr(grad_rows), ptr(grad_lin), ptr(err_flag),
+                                       _stream()), "trs_stage_add_l2")
+
+
 def score_all_items(net, T, user_id, n_items, device, item_meta=None, item0=0, n=None):
     n = n_items - item0 if n is None else n
     out = torch.empty(n, dtype=torch.float32, device=device)
