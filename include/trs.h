@@ -99,7 +99,7 @@ const char* trs_last_error(void);
  *   6: batched top-k retrieval: trs_csr, trs_item_fold(_bytes), trs_retrieve_topk, trs_retrieve_workspace_bytes,
  *      trs_mask_seen, trs_rank_metrics.  (Entry points added since without touching an existing signature or struct:
  *      the in-batch softmax group, trs_batch_prepare_mined, trs_batch_prepare_multi, trs_score_multi_fwd_bwd,
- *      trs_score_warp_fwd_bwd, TRS_LOSS_WARP, trs_stage_add_l2.) */
+ *      trs_score_warp_fwd_bwd, TRS_LOSS_WARP, trs_stage_add_l2, trs_neighbour_fold, trs_neighbours_topk.) */
 #define TRS_ABI_VERSION 6
 #define TRS_SYNC_WORDS 288
 int trs_abi_version(void);
@@ -630,6 +630,31 @@ int trs_mask_seen(float* scores_dev, int64_t n_rows, int64_t n_items, const int6
  * idcg = sum_{r<min(k,|T_u|)} 1/log2(r+2), n_rel = |T_u|), sums in ascending r. */
 int trs_rank_metrics(const int64_t* ids_dev, int64_t n_q, int32_t k, const int64_t* users_dev, const trs_csr* rel,
                      double* metrics_out_dev, void* stream);
+
+/* ------------------------------------------------------------------- nearest neighbours (similar_items / _users) */
+/* Neighbour search over the rows of one table (model.py similar_items / similar_users): the similarity
+ * of rows q and j is <x_q, x_j> (dot) or <x^_q, x^_j> with x^ = x * (1 / |x|) (cosine: normalise first, then the fp32
+ * inner product; a zero row has x^ = 0).  Added without touching an existing signature or struct.
+ *
+ * trs_neighbour_fold: rows (n_rows, D) fp32 with row stride ld >= D floats (the S block of a trs_item_fold buffer with
+ * ld = its padded width, or a user table with ld = D) -> fold_dev in trs_item_fold's layout, trs_item_fold_bytes(n_rows,
+ * D) bytes: X^ (n_rows rounded up to 128 rows, D zero-padded to 16/32/64/128/256 columns; padding rows and columns are
+ * zero), then as many zeros as rows where trs_item_fold keeps c.  cosine = 0 copies and pads; cosine = 1 multiplies each
+ * row by its inverse norm: per lane l of one wave the squares of columns 4l .. 4l+3 summed in ascending column order
+ * (fp32, product and sum rounded separately, from 0), the 64 lane sums added by the xor butterfly of strides 32, 16, 8,
+ * 4, 2, 1, then 1.0f / sqrtf(sum), or 0 when the sum is 0.  fold_dev must not overlap rows_dev. */
+int trs_neighbour_fold(const float* rows_dev, int64_t n_rows, int32_t D, int64_t ld, int32_t cosine, void* fold_dev,
+                       int64_t fold_bytes, void* stream);
+/* Top-k neighbours of the rows queries[q] (dense row ids, int64) among the n_rows rows of a trs_neighbour_fold buffer,
+ * 1 <= k <= min(TRS_RETRIEVE_KMAX, n_rows): the fused kernel of trs_retrieve_topk with the buffer as both operands, all
+ * constants zero and each query's own row excluded (another row with identical values is not).  Outputs ids (n_q, k)
+ * int64 and the raw inner products (n_q, k) fp32, by (similarity descending, row id ascending); positions beyond the
+ * n_rows - 1 candidates hold id -1 and score -inf, and so does the whole row of a query outside [0, n_rows), which is
+ * never used as an address (trs_retrieve_topk treats a user outside its table the same way).  workspace: at least
+ * trs_retrieve_workspace_bytes(n_q, k) bytes. */
+int trs_neighbours_topk(const void* fold_dev, int64_t fold_bytes, int64_t n_rows, int32_t D,
+                        const int64_t* queries_dev, int64_t n_q, int32_t k, int64_t* ids_out_dev,
+                        float* scores_out_dev, void* workspace_dev, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------- in-batch softmax (fit) */
 /* Training loss of fit(loss='softmax') for the Linear / FM scorers (Yi et al., RecSys 2019).  Batch

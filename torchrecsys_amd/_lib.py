@@ -173,6 +173,8 @@ PROTOTYPES = {
     "trs_retrieve_workspace_bytes": (C.c_int64, [_i64, _i32]),
     "trs_retrieve_topk": (C.c_int, [C.c_int, _T, _vp, _i64, _vp, _i64, _i32, C.POINTER(TrsCsr), C.POINTER(TrsCsr), _vp,
                                     _vp, _vp, _vp, _i64, _vp]),
+    "trs_neighbour_fold": (C.c_int, [_vp, _i64, _i32, _i64, _i32, _vp, _i64, _vp]),
+    "trs_neighbours_topk": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
     "trs_mask_seen": (C.c_int, [_vp, _i64, _i64, _vp, C.POINTER(TrsCsr), _vp]),
     "trs_rank_metrics": (C.c_int, [_vp, _i64, _i32, _vp, C.POINTER(TrsCsr), _vp, _vp]),
     "trs_softmax_workspace_bytes": (C.c_int64, [_i64, _i32]),

@@ -12,6 +12,10 @@
 //                       Each workgroup writes its users' sorted top-k keys of its split to the workspace.
 // retrieve_merge_kernel joins the splits (bitonic in LDS), writes ids / scores and, given a relevance CSR, metrics.
 // mask_seen_kernel      generic path (MLP, k > KMAX): seen entries of score rows -> -inf.
+// neighbour_fold_kernel rows of a table (an item fold's S block, the user table) -> a buffer in the item fold's layout:
+//                       the rows, optionally scaled to unit length, zero-padded, then a block of zero constants.
+//                       trs_neighbours_topk runs retrieve_topk_kernel<NQ, true> over it: the query rows are rows of
+//                       the buffer itself and each query's own row is the one excluded id (similar_items / _users).
 // rank_metrics_kernel   generic path: metrics of given top-k ids.
 //
 // The MFMA is an exact fp32 FMA chain (gemm.hip:1-3); the dimension order of the dot product differs from the scoring
@@ -92,6 +96,47 @@ __global__ __launch_bounds__(TRS_BLOCK) void item_fold_kernel(int net, const trs
   }
 }
 
+// One wave per row, one pass: lane l holds columns 4l .. 4l+3 (Dp <= 256: one float4 per lane) between the load, the
+// norm and the store.  Inverse norm, restated in tests/neighbours_ref.py: per lane the squares summed in ascending d
+// (from 0.f, products and sums rounded separately), trs_wave_sum over the 64 lanes, 1.0f / sqrtf; 0 for a zero row.
+__global__ __launch_bounds__(TRS_BLOCK) void neighbour_fold_kernel(const float* __restrict__ rows, int64_t n_rows, int D,
+                                                                  int64_t ld, int cosine, int Dp, int64_t n_pad,
+                                                                  float* __restrict__ X, float* __restrict__ c) {
+  const int lane = threadIdx.x & 63;
+  const int d0 = 4 * lane;
+  const bool vec = (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(rows) & 15) == 0;  // rows start on 16 bytes
+  const int64_t nwave = ((int64_t)gridDim.x * TRS_BLOCK) >> 6;
+  for (int64_t i = ((int64_t)blockIdx.x * TRS_BLOCK + threadIdx.x) >> 6; i < n_pad; i += nwave) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (i < n_rows && d0 < D) {
+      const float* r = rows + i * ld + d0;
+      if (vec && d0 + 4 <= D) {
+        v = *reinterpret_cast<const float4*>(r);
+      } else {
+        v.x = r[0];
+        if (d0 + 1 < D) v.y = r[1];
+        if (d0 + 2 < D) v.z = r[2];
+        if (d0 + 3 < D) v.w = r[3];
+      }
+    }
+    if (cosine) {
+      float sq = 0.f;
+      sq += v.x * v.x;
+      sq += v.y * v.y;
+      sq += v.z * v.z;
+      sq += v.w * v.w;
+      sq = trs_wave_sum(sq);
+      const float inv = sq > 0.f ? 1.0f / sqrtf(sq) : 0.f;
+      v.x *= inv;
+      v.y *= inv;
+      v.z *= inv;
+      v.w *= inv;
+    }
+    if (d0 < Dp) *reinterpret_cast<float4*>(X + i * Dp + d0) = v;
+    if (lane == 0) c[i] = 0.f;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ fused top-k
 struct RetrieveArgs {
   const float* S;
@@ -148,7 +193,9 @@ __device__ void rt_compact(uint64_t* cand, uint64_t* th, int* cnt, int* flagged,
   __syncthreads();
 }
 
-template <int NQ>  // Dp = 8 * NQ
+// SELF: the "seen" row of query user u is the single id u itself (neighbour search: users and items are the same
+// rows); a.seen is not read.  The <NQ, false> instances are the kernels of recommend() / evaluate_ranking().
+template <int NQ, bool SELF>  // Dp = 8 * NQ
 __global__ __launch_bounds__(TRS_BLOCK, 2) void retrieve_topk_kernel(const RetrieveArgs a) {
   constexpr int Dp = 8 * NQ;
   __shared__ uint64_t cand[RT_UT * RT_CAP];
@@ -171,7 +218,13 @@ __global__ __launch_bounds__(TRS_BLOCK, 2) void retrieve_topk_kernel(const Retri
     cnt[tid] = 0;
     int64_t lo = 0, hi = 0;
     const int64_t q = q0 + tid;
-    if (q < a.n_q && a.seen.off) {
+    if (SELF) {
+      const int64_t u = q < a.n_q ? a.users[q] : -1;
+      if ((uint64_t)u < (uint64_t)a.n_users) {  // the walk below skips it in a split that starts behind it
+        lo = u;
+        hi = u + 1;
+      }
+    } else if (q < a.n_q && a.seen.off) {
       const int64_t u = a.users[q];
       if ((uint64_t)u < (uint64_t)a.seen.n_rows) {
         lo = a.seen.off[u];
@@ -220,14 +273,14 @@ __global__ __launch_bounds__(TRS_BLOCK, 2) void retrieve_topk_kernel(const Retri
     __syncthreads();  // the previous tile's appends are done
     rt_compact(cand, th, cnt, flagged, &nflag, a.k, RT_CAP - RT_TN);
     const int64_t base = t * RT_TN;
-    if (tid < RT_UT && a.seen.off) {
+    if (tid < RT_UT && (SELF || a.seen.off)) {
       uint32_t* wb = seenb + tid * RT_WAVES;
 #pragma unroll
       for (int j = 0; j < RT_WAVES; ++j) wb[j] = 0;
       int64_t p = seen_p[tid];
       const int64_t e = seen_e[tid];
       while (p < e) {
-        const int64_t it = a.seen.items[p];
+        const int64_t it = SELF ? p : (int64_t)a.seen.items[p];
         if (it >= base + RT_TN) break;
         if (it >= base) wb[(it - base) >> 5] |= 1u << ((it - base) & 31);
         ++p;
@@ -399,9 +452,51 @@ static int check_csr(const trs_csr* c, const char* who, const char* what) {
   return TRS_OK;
 }
 
-template <int NQ>
+template <int NQ, bool SELF>
 static void launch_retrieve(const RetrieveArgs& a, dim3 grid, hipStream_t s) {
-  hipLaunchKernelGGL(retrieve_topk_kernel<NQ>, grid, dim3(TRS_BLOCK), 0, s, a);
+  hipLaunchKernelGGL((retrieve_topk_kernel<NQ, SELF>), grid, dim3(TRS_BLOCK), 0, s, a);
+}
+
+// The fused kernel over the query tiles x item splits of `a` (a.part, a.tiles_per_split filled here), then the merge.
+template <bool SELF>
+static int run_retrieve(const char* who, RetrieveArgs& a, int Dp, int64_t splits, MergeArgs& m, hipStream_t s) {
+  a.tiles_per_split = (a.n_tiles + splits - 1) / splits;
+  const int64_t used = (a.n_tiles + a.tiles_per_split - 1) / a.tiles_per_split;  // splits that own at least one tile
+  TRS_REQUIRE(rt_user_tiles(a.n_q) < ((int64_t)1 << 31), "%s: too many query users in one call", who);
+  const dim3 grid((unsigned)rt_user_tiles(a.n_q), (unsigned)used);
+  switch (Dp) {
+    case 16: launch_retrieve<2, SELF>(a, grid, s); break;
+    case 32: launch_retrieve<4, SELF>(a, grid, s); break;
+    case 64: launch_retrieve<8, SELF>(a, grid, s); break;
+    case 128: launch_retrieve<16, SELF>(a, grid, s); break;
+    default: launch_retrieve<32, SELF>(a, grid, s); break;
+  }
+  TRS_CHECK_LAUNCH("retrieve_topk_kernel");
+  m.part = a.part;
+  m.n_q = a.n_q;
+  m.splits = used;
+  m.k = a.k;
+  const int64_t mg = a.n_q < 65536 ? a.n_q : 65536;
+  hipLaunchKernelGGL(retrieve_merge_kernel, dim3((unsigned)mg), dim3(TRS_BLOCK), 0, s, m);
+  TRS_CHECK_LAUNCH("retrieve_merge_kernel");
+  return TRS_OK;
+}
+
+// What trs_retrieve_topk and trs_neighbours_topk check alike: k, the query count, the folded buffer, the workspace.
+static int rt_check_topk(const char* who, int64_t n_items, int D, int k, int64_t n_q, const void* fold_dev,
+                         int64_t fold_bytes, const void* workspace_dev, int64_t workspace_bytes) {
+  TRS_REQUIRE(k >= 1 && k <= TRS_RETRIEVE_KMAX, "%s: k=%d outside 1..%d (larger k: score rows + trs_topk)", who, k,
+              TRS_RETRIEVE_KMAX);
+  TRS_REQUIRE(k <= n_items, "%s: k=%d > n_items=%lld", who, k, (long long)n_items);
+  TRS_REQUIRE(n_q >= 0, "%s: negative n_q", who);
+  const int64_t fneed = trs_item_fold_bytes(n_items, D);
+  TRS_REQUIRE(fneed > 0, "%s: D=%d outside 1..%d", who, D, TRS_RETRIEVE_DMAX);
+  TRS_REQUIRE(fold_dev && fold_bytes >= fneed, "%s: fold buffer too small (%lld < %lld)", who, (long long)fold_bytes,
+              (long long)fneed);
+  TRS_REQUIRE(workspace_bytes >= trs_retrieve_workspace_bytes(n_q, k) && (workspace_dev || n_q == 0),
+              "%s: workspace too small (%lld < %lld)", who, (long long)workspace_bytes,
+              (long long)trs_retrieve_workspace_bytes(n_q, k));
+  return TRS_OK;
 }
 
 }  // namespace
@@ -443,17 +538,7 @@ extern "C" int trs_retrieve_topk(int net, const trs_tables* T, const void* fold_
   TRS_REQUIRE(T != nullptr, "%s: tables is NULL", who);
   TRS_REQUIRE(net == TRS_NET_LINEAR || net == TRS_NET_FM, "%s: net must be TRS_NET_LINEAR or TRS_NET_FM", who);
   TRS_REQUIRE(T->user && T->user_lin && T->n_users > 0 && T->n_items > 0, "%s: user table is NULL/empty", who);
-  TRS_REQUIRE(k >= 1 && k <= TRS_RETRIEVE_KMAX, "%s: k=%d outside 1..%d (larger k: score rows + trs_topk)", who, k,
-              TRS_RETRIEVE_KMAX);
-  TRS_REQUIRE(k <= T->n_items, "%s: k=%d > n_items=%lld", who, k, (long long)T->n_items);
-  TRS_REQUIRE(n_q >= 0, "%s: negative n_q", who);
-  const int64_t fneed = trs_item_fold_bytes(T->n_items, T->D);
-  TRS_REQUIRE(fneed > 0, "%s: D=%d outside 1..%d", who, T->D, TRS_RETRIEVE_DMAX);
-  TRS_REQUIRE(fold_dev && fold_bytes >= fneed, "%s: fold buffer too small (%lld < %lld)", who, (long long)fold_bytes,
-              (long long)fneed);
-  TRS_REQUIRE(workspace_bytes >= trs_retrieve_workspace_bytes(n_q, k) && (workspace_dev || n_q == 0),
-              "%s: workspace too small (%lld < %lld)", who, (long long)workspace_bytes,
-              (long long)trs_retrieve_workspace_bytes(n_q, k));
+  TRS_TRY(rt_check_topk(who, T->n_items, T->D, k, n_q, fold_dev, fold_bytes, workspace_dev, workspace_bytes));
   if (seen) {
     const int rc = check_csr(seen, who, "seen");
     if (rc) return rc;
@@ -477,40 +562,70 @@ extern "C" int trs_retrieve_topk(int net, const trs_tables* T, const void* fold_
   a.n_users = T->n_users;
   a.n_items = T->n_items;
   a.n_tiles = n_tiles;
-  a.tiles_per_split = (n_tiles + splits - 1) / splits;
   a.D = T->D;
   a.k = k;
   a.users = users_dev;
   a.n_q = n_q;
   if (seen) a.seen = *seen;
   a.part = (uint64_t*)workspace_dev;
-  const int64_t used = (n_tiles + a.tiles_per_split - 1) / a.tiles_per_split;  // splits that own at least one tile
-  TRS_REQUIRE(rt_user_tiles(n_q) < ((int64_t)1 << 31), "%s: too many query users in one call", who);
-  const dim3 grid((unsigned)rt_user_tiles(n_q), (unsigned)used);
-  hipStream_t s = (hipStream_t)stream;
-  switch (Dp) {
-    case 16: launch_retrieve<2>(a, grid, s); break;
-    case 32: launch_retrieve<4>(a, grid, s); break;
-    case 64: launch_retrieve<8>(a, grid, s); break;
-    case 128: launch_retrieve<16>(a, grid, s); break;
-    default: launch_retrieve<32>(a, grid, s); break;
-  }
-  TRS_CHECK_LAUNCH("retrieve_topk_kernel");
   MergeArgs m = {};
-  m.part = a.part;
-  m.n_q = n_q;
-  m.splits = used;
-  m.k = k;
   m.fm = net == TRS_NET_FM;
   m.users = users_dev;
   if (rel) m.rel = *rel;
   m.ids = ids_out_dev;
   m.scores = scores_out_dev;
   m.metrics = metrics_out_dev;
-  const int64_t mg = n_q < 65536 ? n_q : 65536;
-  hipLaunchKernelGGL(retrieve_merge_kernel, dim3((unsigned)mg), dim3(TRS_BLOCK), 0, s, m);
-  TRS_CHECK_LAUNCH("retrieve_merge_kernel");
+  return run_retrieve<false>(who, a, Dp, splits, m, (hipStream_t)stream);
+}
+
+extern "C" int trs_neighbour_fold(const float* rows_dev, int64_t n_rows, int32_t D, int64_t ld, int32_t cosine,
+                                  void* fold_dev, int64_t fold_bytes, void* stream) {
+  const char* who = "trs_neighbour_fold";
+  TRS_REQUIRE(rows_dev != nullptr, "%s: rows is NULL", who);
+  TRS_REQUIRE(n_rows > 0, "%s: n_rows=%lld < 1", who, (long long)n_rows);
+  const int64_t need = trs_item_fold_bytes(n_rows, D);
+  TRS_REQUIRE(need > 0, "%s: D=%d outside 1..%d", who, D, TRS_RETRIEVE_DMAX);
+  TRS_REQUIRE(ld >= D, "%s: ld=%lld < D=%d", who, (long long)ld, D);
+  TRS_REQUIRE(cosine == 0 || cosine == 1, "%s: cosine must be 0 or 1", who);
+  TRS_REQUIRE(fold_dev && fold_bytes >= need, "%s: fold buffer too small (%lld < %lld)", who, (long long)fold_bytes,
+              (long long)need);
+  const int Dp = rt_dp(D);
+  const int64_t n_pad = rt_items_pad(n_rows);
+  float* X = (float*)fold_dev;
+  hipLaunchKernelGGL(neighbour_fold_kernel, dim3(trs_grid(n_pad, TRS_BLOCK / 64)), dim3(TRS_BLOCK), 0,
+                     (hipStream_t)stream, rows_dev, n_rows, (int)D, ld, (int)cosine, Dp, n_pad, X, X + n_pad * Dp);
+  TRS_CHECK_LAUNCH("neighbour_fold_kernel");
   return TRS_OK;
+}
+
+extern "C" int trs_neighbours_topk(const void* fold_dev, int64_t fold_bytes, int64_t n_rows, int32_t D,
+                                   const int64_t* queries_dev, int64_t n_q, int32_t k, int64_t* ids_out_dev,
+                                   float* scores_out_dev, void* workspace_dev, int64_t workspace_bytes, void* stream) {
+  const char* who = "trs_neighbours_topk";
+  TRS_REQUIRE(n_rows > 0, "%s: n_rows=%lld < 1", who, (long long)n_rows);
+  TRS_TRY(rt_check_topk(who, n_rows, D, k, n_q, fold_dev, fold_bytes, workspace_dev, workspace_bytes));
+  if (n_q == 0) return TRS_OK;
+  TRS_REQUIRE(queries_dev && ids_out_dev && scores_out_dev, "%s: queries/ids_out/scores_out is NULL", who);
+  const int Dp = rt_dp(D);
+  const int64_t n_pad = rt_items_pad(n_rows);
+  RetrieveArgs a = {};
+  a.S = (const float*)fold_dev;  // the catalogue and the query rows are the same padded matrix: the row length is Dp
+  a.c = a.S + n_pad * Dp;        // the zero block: every item constant ...
+  a.user = a.S;
+  a.user_lin = a.c;              // ... and every query constant (n_rows <= n_pad entries)
+  a.n_users = n_rows;
+  a.n_items = n_rows;
+  a.n_tiles = n_pad / RT_TN;
+  a.D = Dp;
+  a.k = k;
+  a.users = queries_dev;
+  a.n_q = n_q;
+  a.part = (uint64_t*)workspace_dev;
+  MergeArgs m = {};  // fm = 0: raw inner products out
+  m.users = queries_dev;
+  m.ids = ids_out_dev;
+  m.scores = scores_out_dev;
+  return run_retrieve<true>(who, a, Dp, rt_splits(n_q, n_rows, k), m, (hipStream_t)stream);
 }
 
 extern "C" int trs_mask_seen(float* scores_dev, int64_t n_rows, int64_t n_items, const int64_t* users_dev,

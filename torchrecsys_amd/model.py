@@ -887,6 +887,112 @@ class TorchRecSys(torch.nn.Module):
             ids[keep] = idx.cpu().to(torch.int64)[ids[keep]]
         return (ids, scores.cpu()) if return_scores else ids
 
+    # ------------------------------------------------------------------------------------------------ neighbours
+    def _dense_rows(self, ids, index, n_rows, what):
+        """Table rows of a list of caller ids of one side (`what`: 'user' | 'item'); IndexError on an unknown id."""
+        ids = torch.as_tensor(ids, dtype=torch.int64).reshape(-1)
+        if index is None:
+            bad = (ids < 0) | (ids >= n_rows)
+            if bool(bad.any()):
+                raise IndexError(f"{what} id {int(ids[bad][0])} outside [0, {n_rows})")
+            return ids
+        index = index.cpu().to(torch.int64)
+        pos = torch.searchsorted(index, ids)
+        ok = pos < index.numel()
+        ok[ok.clone()] = index[pos[ok]] == ids[ok]
+        if not bool(ok.all()):
+            raise IndexError(f"{what} id {int(ids[~ok][0])} does not occur in the ingested interactions")
+        return pos
+
+    def _similar(self, what, query_ids, top_k, metric, return_scores):
+        """similar_items / similar_users: argument checks (before any device work), id mapping, the search, ids back."""
+        if metric not in ('cosine', 'dot'):
+            raise ValueError(f"metric must be 'cosine' or 'dot', got {metric!r}")
+        if self.net_type not in ('linear', 'fm'):
+            raise ValueError(f"similar_{what}s needs net_type 'linear' or 'fm': with net_type={self.net_type!r} the "
+                             "metadata embeddings are concatenated, not summed, so an item has no folded row")
+        if self.n_factors > ops._lib.RETRIEVE_DMAX:
+            raise ValueError(f"similar_{what}s takes n_factors <= {ops._lib.RETRIEVE_DMAX} (TRS_RETRIEVE_DMAX), got "
+                             f"{self.n_factors}")
+        self.net = self.net.eval()
+        n_rows = self.n_items if what == 'item' else self.n_users
+        index = getattr(self.data_processor, f"{what}_index", None)
+        qlist = query_ids.tolist() if hasattr(query_ids, "tolist") else list(query_ids)
+        k = min(int(top_k), n_rows)
+        if k <= 0 or not qlist:
+            e = torch.empty((len(qlist), max(k, 0)), dtype=torch.int64)
+            return (e, torch.empty(e.shape, dtype=torch.float32)) if return_scores else e
+        queries = self._dense_rows(qlist, index, n_rows, what).to(_device())
+        ids, scores = self._neighbours_dense(what, queries, k, metric == 'cosine')
+        ids = ids.cpu()
+        if index is not None:
+            keep = ids >= 0
+            ids[keep] = index.cpu().to(torch.int64)[ids[keep]]
+        return (ids, scores.cpu()) if return_scores else ids
+
+    def _neighbours_dense(self, what, queries, k, cosine):
+        """Top-k neighbours of dense rows (int64 GPU tensor) of the item or the user side: (ids (n, k) dense int64 with
+        -1 padding, similarities (n, k) fp32 with -inf padding).  k <= KMAX: the fused kernel over the normalised
+        buffer; larger k: rows of a Linear scorer over it, the query's own column -> -inf, trs_topk."""
+        dev = queries.device
+        D = self.n_factors
+        n = queries.numel()
+        if what == 'user':
+            n_rows, rows = self.n_users, self.net.user.weight.data
+        elif self.net.n_meta_tables() == 0:  # S_i is the item row itself
+            n_rows, rows = self.n_items, self.net.item.weight.data
+        else:
+            n_rows = self.n_items
+            fold = ops.item_fold(self.net.NET, self.net.tables(), n_rows, D, dev, self._item_meta_dev())
+            n_pad = (n_rows + 127) // 128 * 128
+            Dp = fold.numel() // (4 * n_pad) - 1
+            rows = fold.view(torch.float32)[:n_pad * Dp].view(n_pad, Dp)
+        nf = ops.neighbour_fold(rows, n_rows, D, cosine)
+        if k <= ops._lib.RETRIEVE_KMAX:
+            outs = [ops.neighbours_topk(nf, n_rows, D, queries[s:s + self.RECOMMEND_CHUNK], k)
+                    for s in range(0, n, self.RECOMMEND_CHUNK)]
+            return torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])
+        X, zero = ops.fold_views(nf, n_rows, D)
+        ids = torch.empty((n, k), dtype=torch.int64, device=dev)
+        scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+        pad = (torch.arange(k, device=dev) >= n_rows - 1)[None, :]
+        for s in range(0, n, self.GENERIC_CHUNK):
+            qs = queries[s:s + self.GENERIC_CHUNK]
+            g = qs.numel()
+            Tz, keep = ops.make_tables(X[qs].contiguous(), X, zero[:g].view(-1, 1), zero.view(-1, 1))
+            sims = torch.stack([ops.score_all_items("linear", Tz, r, n_rows, dev) for r in range(g)])
+            sims[torch.arange(g, device=dev), qs] = float('-inf')
+            top = torch.stack([ops.topk(sims[r], k) for r in range(g)])
+            sc = torch.gather(sims, 1, top)
+            ids[s:s + g] = torch.where(pad, torch.full_like(top, -1), top)
+            scores[s:s + g] = torch.where(pad, torch.full_like(sc, float('-inf')), sc)
+        return ids, scores
+
+    @_host_side
+    def similar_items(self, item_ids, top_k: int = 10, metric: str = 'cosine', return_scores: bool = False):
+        """The top_k items most similar to each of several items: an (n, k) int64 CPU tensor of original item ids,
+        k = min(top_k, n_items); with return_scores also the (n, k) fp32 similarities.
+        An item is represented by S_i = item_i + sum_m meta_m(i), the row the scorers multiply with a user's (two items
+        with the same metadata and close id rows are close); bias and linear terms take no part.  metric='dot':
+        <S_q, S_j>; metric='cosine': the rows are scaled to unit length first (fp32), then the same inner product; a zero
+        row is similar to nothing (0 everywhere).  The query's own id is never returned; another item with identical
+        values is.  Order: similarity descending, ties by ascending item row as in predict(); the positions beyond the
+        n_items - 1 other items hold id -1 and similarity -inf.  An unknown id raises IndexError.
+        Linear and FM only (ValueError for the MLP, whose metadata embeddings are concatenated, and for n_factors >
+        TRS_RETRIEVE_DMAX).  k <= TRS_RETRIEVE_KMAX runs the fused matrix-core kernel of recommend() on a normalised
+        copy of the folded item matrix, built per call; larger k scores rows one query at a time.  Under
+        torch.distributed every rank answers from its own replica."""
+        return self._similar('item', item_ids, top_k, metric, return_scores)
+
+    @_host_side
+    def similar_users(self, user_ids, top_k: int = 10, metric: str = 'cosine', return_scores: bool = False):
+        """similar_items() for users: a user is its row of the user table (user_bias / linear_user take no part); the
+        result holds original user ids, k = min(top_k, n_users).
+        Every call builds a padded (for cosine: unit-length) copy of the user table — n_users rounded up to 128 rows x
+        n_factors rounded up to 16/32/64/128/256 columns x 4 bytes, plus 4 bytes per row — which lives for the call:
+        5 GB for 10 M users at 128 factors."""
+        return self._similar('user', user_ids, top_k, metric, return_scores)
+
     def _relevance_csr(self, exclude_seen):
         """CSR of the test split's distinct (user, item) pairs over dense users; with exclude_seen without the pairs
         that are also in the train split (this rank's train rows: under dp_partition 'user' all rows of its users)."""

@@ -790,6 +790,36 @@ def retrieve_topk(net, T, fold, users, k, seen=None, rel=None):
     return ids, scores, met
 
 
+def neighbour_fold(rows, n_rows, D, cosine):
+    """Rows of a table as a padded, optionally unit-length buffer in trs_item_fold's layout (trs_neighbour_fold), one
+    uint8 buffer.  rows: an (n, ld) fp32 GPU matrix whose first n_rows rows and D columns are the table."""
+    lib = _lib.load()
+    _dev(rows, "neighbour rows", torch.float32)
+    if rows.dim() != 2 or rows.shape[0] < n_rows or rows.shape[1] < D:
+        raise ValueError(f"rows must be an (n >= {n_rows}, ld >= {D}) matrix, got {tuple(rows.shape)}")
+    nb = lib.trs_item_fold_bytes(int(n_rows), int(D))
+    buf = torch.empty(max(nb, 8), dtype=torch.uint8, device=rows.device)
+    check(lib.trs_neighbour_fold(ptr(rows), int(n_rows), int(D), rows.shape[1], int(bool(cosine)), ptr(buf), nb,
+                                 _stream()), "trs_neighbour_fold")
+    return buf
+
+
+def neighbours_topk(fold, n_rows, D, queries, k):
+    """Fused top-k neighbours of dense rows `queries` (int64 GPU tensor) in a neighbour_fold buffer, self excluded:
+    (ids (n, k) int64 with -1 padding, similarities (n, k) fp32 with -inf padding)."""
+    lib = _lib.load()
+    _dev(queries, "query rows", torch.int64)
+    n = queries.numel()
+    dev = queries.device
+    ids = torch.empty((n, k), dtype=torch.int64, device=dev)
+    scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+    ws_bytes = lib.trs_retrieve_workspace_bytes(n, k)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    check(lib.trs_neighbours_topk(ptr(fold), fold.numel(), int(n_rows), int(D), ptr(queries), n, int(k), ptr(ids),
+                                  ptr(scores), ptr(ws), ws_bytes, _stream()), "trs_neighbours_topk")
+    return ids, scores
+
+
 def mask_seen(scores, users, seen):
     """Seen entries of score rows (n, n_items) fp32 -> -inf (trs_mask_seen), in place."""
     _dev(scores, "score rows", torch.float32)
