@@ -102,6 +102,7 @@ const char* trs_last_error(void);
  *      trs_score_warp_fwd_bwd, TRS_LOSS_WARP, trs_stage_add_l2, trs_neighbour_fold, trs_neighbours_topk.) */
 #define TRS_ABI_VERSION 6
 #define TRS_SYNC_WORDS 288
+#define TRS_SYNC_REBASE 0x40000000u /* arrivals after which trs_train_steps_sgd zeroes sync_dev and its host count */
 int trs_abi_version(void);
 /* Tuning / A-B knobs of the launch paths (kernel selection, launch shapes): GRID_CAP, PASS_GRID_CAP, K1_ITERS,
  * PASS_ITERS, PRESORT_GRID_CAP, PASS_NT, K1_NT, K1_WGS_PER_CU, GEMM32_NO_GLDS, GEMM16_TN_WIDE, GEMM16_TILE, GEMM16_NO_GLDS, BN_FINAL_TWO_SWEEPS (meanings:
@@ -457,7 +458,11 @@ typedef struct trs_train_args {
                                 launch — K1's workgroups count themselves in on sync_dev[0] once their row reads are
                                 done, wait for the whole grid, and add the flagged references' contributions
                                 themselves (no second launch).  err bit 2: the grid did not become resident within
-                                0.2 s (that step's results are not exact). */
+                                0.2 s (that step's results are not exact).  Before a step that finds the count at
+                                TRS_SYNC_REBASE (2^30) or above, the entry point zeroes the TRS_SYNC_WORDS words on
+                                the stream and the count with them: launches that count in early never write the
+                                flag lines, and a line 2^31 arrivals old would read as "reached" (all launches on
+                                one sync_dev therefore go to ONE stream). */
   const int32_t* n_flagged_dev; /* NULL, or (n_steps) int32 from trs_epoch_flags_ordered (the id and flag arrays above
                                 then are the ones it ordered): batch st's first n_flagged_dev[st] triples are the ones
                                 that carry a flagged reference.  The one-launch step then counts a workgroup in as soon

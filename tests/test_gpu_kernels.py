@@ -933,6 +933,12 @@ def test_fast_sgd_step_matches_oracle_and_generic_path(net, D):
     six widths are the row shapes (4,64,2), (4,64,4), (1,4,1), (1,64,4), (4,4,1) and (1,64,1) of csrc/score_kernels.h's
     table; with the widths before them every shape of the table is met (tests/test_gpu_row_shapes.py: every shape, ragged
     and full, on every path)."""
+    check_fast_sgd_step(net, D)
+
+
+def check_fast_sgd_step(net, D, first_stamp=1, prepare_scratch=None):
+    """first_stamp / prepare_scratch(scratch, net, NU, NI, B, D): the step stamps and the state of the duplicate-detection
+    scratch a long run arrives with (tests/test_gpu_long_run.py)."""
     ops = _ops()
     B, lr = 777, 0.05
     p, batch, _ = make_case(net, D, 0, B, NU=90, NI=41, seed=D)
@@ -942,9 +948,11 @@ def test_fast_sgd_step_matches_oracle_and_generic_path(net, D):
     ref = {k: v.copy() for k, v in p.items()}
     losses = torch.zeros(3, device=DEV)
     scratch = ops.train_scratch(90, 41, B, D, DEV) if D != 8 else None  # D == 8 exercises the all-atomic variant
+    if prepare_scratch is not None:
+        prepare_scratch(scratch, net, 90, 41, B, D)
     for step in range(3):
         ops.train_steps_sgd(net, T, None, None, 0, 0, 0, B, 1, lr, ids["user_id"], ids["pos_item_id"],
-                            ids["neg_item_id"], gz, du, losses[step:step + 1], err, scratch, 1 + step)
+                            ids["neg_item_id"], gz, du, losses[step:step + 1], err, scratch, first_stamp + step)
         _, _, loss, grads = onets.train_forward_backward(net, ref, batch)
         ooptim.sgd_step(ref, grads, lr)
         assert abs(losses[step].item() / B - float(loss)) <= TOL * max(abs(float(loss)), 1e-3)
@@ -1058,6 +1066,10 @@ def test_flag_mode_matches_oracle(net, D, skew, n_users, one_launch, tune):
     ordered: the presort also puts every batch's triples with a flagged reference first (trs_epoch_flags_ordered: the
     same multiset of triples, the same flags per triple, their count reported) and the one-launch step counts its
     workgroups in after those triples (trs_train_args.n_flagged_dev) instead of after its last one."""
+    check_flag_mode(net, D, skew, n_users, one_launch, tune)
+
+
+def check_flag_mode(net, D, skew, n_users, one_launch, tune, first_stamp=1, prepare_scratch=None):
     ops = _ops()
     rs = np.random.RandomState(D + skew)
     NU, NI, B, nb, lr = n_users, 57 if n_users == 300 else 5000, 512, 3, 0.05
@@ -1118,11 +1130,14 @@ def test_flag_mode_matches_oracle(net, D, skew, n_users, one_launch, tune):
     import ctypes
     sync = (torch.zeros(288, dtype=torch.int32, device=DEV), ctypes.c_uint32(0)) if one_launch else None
     scratch, ustage = ops.train_scratch(NU, NI, B, D, DEV), torch.empty((B, D), device=DEV)
+    if prepare_scratch is not None:
+        prepare_scratch(scratch, net, NU, NI, B, D)
     # (two C calls, 2 + 1 steps: the arrival counter carries over from call to call)
-    ops.train_steps_sgd(net, T, None, None, 0, 0, 0, B, 2, lr, *ids, gz, du, losses, err, scratch, 1, None,
+    ops.train_steps_sgd(net, T, None, None, 0, 0, 0, B, 2, lr, *ids, gz, du, losses, err, scratch, first_stamp, None,
                         user_dup=udup, item_dup=idup, ustage=ustage, sync=sync, n_flagged=ef.n_flagged_from(0))
     ids2, udup2, idup2 = ef.step_args(2)
-    ops.train_steps_sgd(net, T, None, None, 0, 0, 0, B, 1, lr, *ids2, gz, du, losses[2:], err, scratch, 3, None,
+    ops.train_steps_sgd(net, T, None, None, 0, 0, 0, B, 1, lr, *ids2, gz, du, losses[2:], err, scratch,
+                        first_stamp + 2, None,
                         user_dup=udup2, item_dup=idup2, ustage=ustage, sync=sync, n_flagged=ef.n_flagged_from(2))
     torch.cuda.synchronize()
     if one_launch:  # every launch counted all its workgroups in, and the library knows how many it scheduled
@@ -1254,6 +1269,10 @@ def test_presorted_item_update_matches_oracle(net, D, skew, inline_user):
     sorted runs only walk rows with several references.  "userflags": no user sort — user duplicates as flags of the
     LDS-bitmap kernel, the flagged users' gradients added with float atomics in the sorted-run launch (the dense regime's
     plain-SGD step)."""
+    check_presorted_item_update(net, D, skew, inline_user)
+
+
+def check_presorted_item_update(net, D, skew, inline_user, first_stamp=1, prepare_scratch=None):
     ops = _ops()
     rs = np.random.RandomState(D + skew)
     NU, NI, B, nb, lr = 300, 57, 512, 3, 0.05
@@ -1284,14 +1303,17 @@ def test_presorted_item_update_matches_oracle(net, D, skew, inline_user):
         cnt = np.bincount(np.concatenate([i[b * B:(b + 1) * B], j[b * B:(b + 1) * B]]), minlength=NI)
         want = np.stack([cnt[i[b * B:(b + 1) * B]] > 1, cnt[j[b * B:(b + 1) * B]] > 1], axis=1).astype(np.uint8)
         assert np.array_equal(idup[b * B:(b + 1) * B].cpu().numpy(), want)
+    scratch = ops.train_scratch(NU, NI, B, D, DEV)
+    if prepare_scratch is not None:
+        prepare_scratch(scratch, net, NU, NI, B, D)
     if inline_user:
         ops.train_steps_sgd(net, T, None, None, 0, 0, 0, B, nb, lr, *ids, gz, du, losses, err,
-                            ops.train_scratch(NU, NI, B, D, DEV), 1, None, sk, sv, ps.key_bytes, udup,
+                            scratch, first_stamp, None, sk, sv, ps.key_bytes, udup,
                             torch.empty((B, D), device=DEV), usorted,
                             item_dup=idup if inline_user == "items" else None)
     else:
         ops.train_steps_sgd(net, T, None, None, 0, 0, 0, B, nb, lr, *ids, gz, du, losses, err,
-                            ops.train_scratch(NU, NI, B, D, DEV), 1, None, sk, sv, ps.key_bytes)
+                            scratch, first_stamp, None, sk, sv, ps.key_bytes)
     torch.cuda.synchronize()
     ref = {k: v.copy() for k, v in p.items()}
     for b in range(nb):
@@ -1310,6 +1332,11 @@ def test_presorted_adaptive_rules_match_the_oracle(net, D, skew, kind):
     """SparseAdam / Adagrad on the presorted two-launch step (users referenced once updated by K1, duplicated users
     and item rows by their sorted runs, cut runs through the gradient accumulator + cut_rows_apply_kernel): 4 batches
     in one C call == oracle steps on the coalesced gradients of the rows present in each batch."""
+    check_presorted_adaptive_rules(net, D, skew, kind)
+
+
+def check_presorted_adaptive_rules(net, D, skew, kind, first_stamp=1, prepare_scratch=None):
+    """Returns the number of cut runs the last step listed."""
     from torchrecsys_amd import _lib
     from oracle.nets import touched_rows
     ops = _ops()
@@ -1343,10 +1370,14 @@ def test_presorted_adaptive_rules_match_the_oracle(net, D, skew, kind):
         o.user_s2, o.item_s2, o.user_lin_s2, o.item_lin_s2 = (ops.ptr(s2[k]) for k in names)
     o.gacc, o.gacc_lin, o.cut_rows, o.cut_count = ops.ptr(gacc), ops.ptr(gacc_lin), ops.ptr(cut_rows), ops.ptr(cut_count)
     o.cut_capacity = cut_rows.numel()
+    scratch = ops.train_scratch(NU, NI, B, D, DEV)
+    if prepare_scratch is not None:
+        prepare_scratch(scratch, net, NU, NI, B, D)
     ops.train_steps_sgd(net, T, None, None, 0, 0, 0, B, nb, lr, *ids, gz, du, losses, err,
-                        ops.train_scratch(NU, NI, B, D, DEV), 1, None, sk, sv, ps.key_bytes, udup,
+                        scratch, first_stamp, None, sk, sv, ps.key_bytes, udup,
                         torch.empty((B, D), device=DEV), usorted, o)
     torch.cuda.synchronize()
+    cuts_listed = int(cut_count.max().item())  # (the last step's list; the other parity's counter is reset by it)
     ref = {k: v.copy() for k, v in p.items()}
     r1 = {k: np.zeros_like(v) for k, v in p.items()}
     r2 = {k: np.zeros_like(v) for k, v in p.items()}
@@ -1377,6 +1408,7 @@ def test_presorted_adaptive_rules_match_the_oracle(net, D, skew, kind):
         assert rel_err(t[k].cpu().numpy(), ref[k]) < 0.05, k
     assert float(gacc.abs().max()) == 0.0 and float(gacc_lin.abs().max()) == 0.0  # accumulator left clean
     assert err.item() == 0
+    return cuts_listed
 
 
 @pytest.mark.parametrize("net,D,M,skew", [("fm", 64, 1, False), ("fm", 16, 3, True), ("linear", 32, 1, True),
@@ -1389,6 +1421,10 @@ def test_presorted_step_with_metadata_matches_oracle(net, D, M, skew, meta_sorte
     "hot": 90 % of the items carry category 0 of the first column, batch 2048, a ten times larger step — that row's run
     is ~3 700 references long and is cut into ~58 pieces of 64; FM's pieces subtract sum(c)*w with the w they loaded,
     which other pieces may already have touched (second order in the step size): held to the same 1e-5."""
+    check_presorted_step_with_metadata(net, D, M, skew, meta_sorted, B)
+
+
+def check_presorted_step_with_metadata(net, D, M, skew, meta_sorted, B, first_stamp=1, prepare_scratch=None):
     from torchrecsys_amd import _lib
     ops = _ops()
     rs = np.random.RandomState(D + M + skew)
@@ -1432,8 +1468,11 @@ def test_presorted_step_with_metadata_matches_oracle(net, D, M, skew, meta_sorte
             pm, nm = ps.meta_id_args(0)
             ms.pos_meta_ids, ms.neg_meta_ids = ops.ptr(pm), ops.ptr(nm)
     losses = torch.zeros(nb, device=DEV)
+    scratch = ops.train_scratch(NU, NI, B, D, DEV)
+    if prepare_scratch is not None:
+        prepare_scratch(scratch, net, NU, NI, B, D)
     ops.train_steps_sgd(net, T, None, None, 0, 0, 0, B, nb, lr, *ids, gz, du, losses, err,
-                        ops.train_scratch(NU, NI, B, D, DEV), 1, None, sk, sv, ps.key_bytes, udup,
+                        scratch, first_stamp, None, sk, sv, ps.key_bytes, udup,
                         torch.empty((B, D), device=DEV), usorted, None, ms)
     torch.cuda.synchronize()
     ref = {k: v.copy() for k, v in p.items()}

@@ -66,7 +66,7 @@ struct FastArgs {
   const uint8_t* idup_pos;
   float* ustage;            // (B,D) pre-update user rows, read by the sorted item update
   OptArgs o;                // update rule of the presorted mode (kind OPT_SGD: lr above)
-  // INL 3 (flag mode, one launch per step): sync[0] = ONE monotonic arrival counter (never reset, wraps mod 2^32); a
+  // INL 3 (flag mode, one launch per step): sync[0] = ONE monotonic arrival counter (zeroed by the host every 2^30 arrivals); a
   // launch counts its workgroups in and waits until the counter has reached sync_target = arrivals of all earlier
   // launches + its own grid (wrap-safe signed compare); sync[32 * (1 + g)], g < 8: flag lines that carry the last
   // completed target (TRS_SYNC_WORDS uint32 in all)
@@ -1692,6 +1692,16 @@ extern "C" int trs_train_steps_sgd(const trs_train_args* args, void* stream) {
       a.idup_pos = args->item_dup_flags_dev + (int64_t)st * 2 * batch;
       a.ustage = ustage_buf_dev;
       a.sync = args->sync_count_host ? args->sync_dev : nullptr;
+      // Rebase: launches that count in early never write the flag lines, so after 2^31 arrivals of them a launch that
+      // polls its line would read a stale value as "ahead" and not wait.  Long before that, zero counter and lines
+      // behind every earlier launch of the stream: all values stay within TRS_SYNC_REBASE + one grid of each other.
+      if (a.sync && *args->sync_count_host >= TRS_SYNC_REBASE) {
+        if (hipMemsetAsync(args->sync_dev, 0, TRS_SYNC_WORDS * sizeof(uint32_t), s) != hipSuccess) {
+          trs_set_error("trs_train_steps_sgd: clearing the arrival counter failed");
+          return TRS_E_LAUNCH;
+        }
+        *args->sync_count_host = 0;
+      }
       a.sync_base = a.sync ? *args->sync_count_host : 0u;
       a.nflag = args->n_flagged_dev ? args->n_flagged_dev + st : nullptr;
     }
