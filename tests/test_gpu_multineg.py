@@ -307,7 +307,7 @@ def test_out_of_range_id_sets_the_flag_and_is_not_used_as_an_address(net_type, M
 
 
 # ------------------------------------------------------------------------------------------------ 6. optimisers
-@pytest.mark.parametrize("kind", ["sgd", "sparse_adam", "adagrad", "sgd_momentum"])
+@pytest.mark.parametrize("kind", ["sgd", "sgd_two_lr", "sparse_adam", "adagrad", "sgd_momentum"])
 @pytest.mark.parametrize("net_type,M", [("fm", 2), ("linear", 2), ("fm", 0)])
 def test_one_multineg_step_per_optimiser_class(net_type, M, kind):
     """engine.SparseScorerTrainer.multineg_step: the oracle's gradient pushed through oracle.optim's rules; 1e-5 on the
@@ -327,6 +327,9 @@ def test_one_multineg_step_per_optimiser_class(net_type, M, kind):
     W = params_of(net)
     if kind == "sgd":
         opt = torch.optim.SGD(net.parameters(), lr=0.5)
+    elif kind == "sgd_two_lr":  # the user embedding table at 0.5, every other table at 0.25
+        ps = net.table_params()
+        opt = torch.optim.SGD([{"params": [ps[0]], "lr": 0.5}, {"params": ps[1:], "lr": 0.25}], lr=0.5)
     elif kind == "sgd_momentum":  # a dense-state torch optimiser: sparse COO gradients + optimizer.step()
         opt = torch.optim.SGD(net.parameters(), lr=0.5, momentum=0.9)
     elif kind == "sparse_adam":
@@ -334,7 +337,7 @@ def test_one_multineg_step_per_optimiser_class(net_type, M, kind):
     else:
         opt = torch.optim.Adagrad(net.parameters(), lr=0.05)
     tr = SparseScorerTrainer(net, opt, cap)  # B < capacity: prefix views of the staging buffers
-    assert tr.kind == ("generic" if kind == "sgd_momentum" else kind)
+    assert tr.kind == {"sgd_momentum": "generic", "sgd_two_lr": "sgd"}.get(kind, kind)
     tr.multineg = (K, loss_id(SM), tau)
     user, items = forced_rows(np.random.RandomState(8), NU, NI, B, K)
     loss = torch.zeros(1, device=DEV)
@@ -349,8 +352,8 @@ def test_one_multineg_step_per_optimiser_class(net_type, M, kind):
 
     def rule(w0, g):
         w = w0.copy()
-        if kind in ("sgd", "sgd_momentum"):  # (the momentum buffer of a first step is the gradient)
-            w -= np.float32(0.5) * g
+        if kind in ("sgd", "sgd_two_lr", "sgd_momentum"):  # (the momentum buffer of a first step is the gradient)
+            w -= np.float32(0.5 if (kind != "sgd_two_lr" or k == "user.weight") else 0.25) * g
         elif kind == "sparse_adam":
             ooptim.sparse_adam_rows(w, g, rows[k], np.zeros_like(w), np.zeros_like(w), 1, 0.01)
         else:

@@ -171,8 +171,12 @@ def test_row_chunks_agree_and_repeat_bit_identically(net_type, M, B):
 
 # ------------------------------------------------------------------------------------------------ 3. optimisers
 @pytest.mark.parametrize("net_type,M", [("fm", 2), ("linear", 2), ("fm", 0)])
-@pytest.mark.parametrize("kind", ["sparse_adam", "adagrad"])
+@pytest.mark.parametrize("kind", ["sparse_adam", "adagrad", "sgd_two_lr", "sgd_momentum"])
 def test_three_steps_of_coalescing_optimisers(net_type, M, kind):
+    """Every optimiser class beside plain SGD (despite the name: it grew from the coalescing kinds), the oracle's
+    gradient through oracle.optim's rules, 1e-5 on the tables: three steps of the coalescing rules (and their state),
+    one step of SGD with two learning rates (the per-table scatter) and of SGD with momentum (a dense-state torch
+    optimiser: sparse COO gradients + optimizer.step())."""
     NU, NI, D, B, tau = 300, 200, 16, 256, 0.5
     net = build_net(net_type, M, NU, NI, D, 5)
     ps = net.table_params()
@@ -180,12 +184,19 @@ def test_three_steps_of_coalescing_optimisers(net_type, M, kind):
     if kind == "sparse_adam":
         opt = torch.optim.SparseAdam(list(net.parameters()), lr=0.01)
         st = [[np.zeros_like(w), np.zeros_like(w)] for w in W]
-    else:
+    elif kind == "adagrad":
         opt = torch.optim.Adagrad(net.parameters(), lr=0.05)
         st = [[np.zeros_like(w)] for w in W]
+    elif kind == "sgd_two_lr":  # the user embedding table at 0.5, every other table at 0.25
+        opt = torch.optim.SGD([{"params": [ps[0]], "lr": 0.5}, {"params": ps[1:], "lr": 0.25}], lr=0.5)
+    else:
+        opt = torch.optim.SGD(net.parameters(), lr=0.5, momentum=0.9)
+        momentum = {}
     logq = random_logq(NI, 1)
     tr = trainer(net, opt, B, tau, logq)
-    for step in range(1, 4):
+    assert tr.kind == {"sgd_momentum": "generic", "sgd_two_lr": "sgd"}.get(kind, kind)
+    n_steps = 3 if kind in ("sparse_adam", "adagrad") else 1
+    for step in range(1, n_steps + 1):
         u, p, pm = make_batch(B, NU, NI, M, 100 + step)
         loss = torch.zeros(1, device=DEV)
         tr.softmax_step(device_ids(u, p, pm, torch.int32), loss)
@@ -196,10 +207,16 @@ def test_three_steps_of_coalescing_optimisers(net_type, M, kind):
             g = grads[k].astype(np.float32)
             if kind == "sparse_adam":
                 ooptim.sparse_adam_rows(W[k], g, rows, st[k][0], st[k][1], step, 0.01)
-            else:
+            elif kind == "adagrad":
                 ooptim.adagrad_rows(W[k], g, rows, st[k][0], step, 0.05)
+            elif kind == "sgd_two_lr":
+                ooptim.sgd_step({k: W[k]}, {k: g}, 0.5 if k == 0 else 0.25)
+            else:
+                ooptim.sgd_momentum_step({k: W[k]}, {k: g}, momentum, 0.5, 0.9)
     for k, q in enumerate(ps):
         assert rel_err(q.detach().cpu().numpy(), W[k]) <= 1e-5, k
+        if n_steps == 1:
+            continue
         s = opt.state[q]
         names = ("exp_avg", "exp_avg_sq") if kind == "sparse_adam" else ("sum",)
         for j, name in enumerate(names):

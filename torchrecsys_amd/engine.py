@@ -9,6 +9,10 @@ Optimiser dispatch:
   anything else                                 -> the staged rows are handed to the optimiser as the sparse COO
                                                    gradients autograd would have produced, then optimizer.step().
 Moments live in optimizer.state[p] under torch's own key names, so optimizer.state_dict() stays truthful.
+
+Every per-step loss (step, warp_step, softmax_step, multineg_step) stages its gradients with its own kernel into one
+field-major layout (staged_layout) and ends in one tail, SparseScorerTrainer._apply_staged, which hands every table its
+block through the rule above; single-lr SGD on pairs (step, warp_step) keeps its one-launch fused scatter in front of it.
 """
 import os
 
@@ -66,24 +70,48 @@ class RowState:
         return self.step_id
 
 
+def optimizer_state(kind, optimizer, p, g):
+    """optimizer.state[p] of a coalescing rule, created on first use under torch's own key names like torch does (g:
+    the parameter's group).  torch.optim.Adam counts its steps in a tensor, SparseAdam in an int; torch.optim.Adagrad
+    creates its state in __init__, a foreign object's is made here."""
+    st = optimizer.state[p]
+    if kind == "sparse_adam" and "exp_avg" not in st:
+        st["step"] = torch.tensor(0.0) if type(optimizer) is torch.optim.Adam else 0
+        st["exp_avg"] = torch.zeros_like(p.data)
+        st["exp_avg_sq"] = torch.zeros_like(p.data)
+    if kind == "adagrad" and "sum" not in st:
+        st["step"] = torch.tensor(0.0)
+        st["sum"] = torch.full_like(p.data, g.get("initial_accumulator_value", 0.0))
+    return st
+
+
+def staged_layout(S, M, has_meta_lin):
+    """The one layout of every step's staging buffers (ops.stage_add_l2 documents the same): F =
+    1 + S (1 + M) fields, the user, the S item slots, then the S slots of every metadata column.  Returns one (index into
+    table_params(), id source 'user' | 'item' | column m, field slice, wide) per table in update order; wide tables take
+    their block of grad_rows, 1-wide ones that of grad_lin (has_meta_lin: FM's 1-wide metadata tables)."""
+    items = slice(1, 1 + S)
+    out = [(0, "user", slice(0, 1), True), (1, "item", items, True), (2, "user", slice(0, 1), False),
+           (3, "item", items, False)]
+    for m in range(M):
+        fields = slice(1 + S + m * S, 1 + S + (m + 1) * S)
+        out.append((4 + m, m, fields, True))
+        if has_meta_lin:
+            out.append((4 + M + m, m, fields, False))
+    return out
+
+
 def apply_rows(kind, optimizer, p, rs, idx, vals, ld=None):
     """One coalescing-optimiser update of table `p` from uncoalesced (idx, vals) entries."""
     g = _group_of(optimizer, p)
-    st = optimizer.state[p]
+    st = optimizer_state(kind, optimizer, p, g)
     ops.rows_scatter_add(rs.acc, idx, vals, 1.0, ld=ld)
     if kind == "sparse_adam":
-        if len(st) == 0:
-            st["step"] = torch.tensor(0.0) if type(optimizer) is torch.optim.Adam else 0
-            st["exp_avg"] = torch.zeros_like(p.data)
-            st["exp_avg_sq"] = torch.zeros_like(p.data)
         st["step"] += 1
         b1, b2 = g["betas"]
         ops.rows_apply_sparse_adam(p.data, rs.acc, st["exp_avg"], st["exp_avg_sq"], rs.stamp, idx, rs.next_id(),
                                    g["lr"], b1, b2, g["eps"], int(st["step"]))
     elif kind == "adagrad":
-        if "sum" not in st:  # torch.optim.Adagrad creates its state in __init__; be safe for foreign objects
-            st["step"] = torch.tensor(0.0)
-            st["sum"] = torch.full_like(p.data, g.get("initial_accumulator_value", 0.0))
         st["step"] += 1
         step = float(st["step"])
         clr = g["lr"] / (1 + (step - 1) * g["lr_decay"])
@@ -399,17 +427,7 @@ class SparseScorerTrainer:
         own key names (created on first use like torch does) and the step counters are advanced here."""
         from . import _lib
         g = _group_of(self.opt, self.params[0])
-        sts = []
-        for p in self.params:
-            st = self.opt.state[p]
-            if self.kind == "sparse_adam" and "exp_avg" not in st:
-                st["step"] = torch.tensor(0.0) if type(self.opt) is torch.optim.Adam else 0
-                st["exp_avg"] = torch.zeros_like(p.data)
-                st["exp_avg_sq"] = torch.zeros_like(p.data)
-            if self.kind == "adagrad" and "sum" not in st:
-                st["step"] = torch.tensor(0.0)
-                st["sum"] = torch.full_like(p.data, g.get("initial_accumulator_value", 0.0))
-            sts.append(st)
+        sts = [optimizer_state(self.kind, self.opt, p, g) for p in self.params]  # (one rule for all tables: one g)
         step0 = int(sts[0]["step"])
         assert all(int(st["step"]) == step0 for st in sts), "embedding tables were stepped a different number of times"
         o = _lib.TrsOpt()
@@ -509,30 +527,44 @@ class SparseScorerTrainer:
         self._add_l2(ids["user"].to(i32), items, meta, gr, gl)
 
     def _apply_pair_rows(self, ids, T, Bt, gr, gl, events=None):
-        """The row updates of one step from gradients staged in trs_score_fwd_bwd's order (R = 3 + 2M fields) for the
-        triples `ids` / `Bt`: the fused scatter for single-lr SGD, the per-table scatter / coalescing rules otherwise,
-        sparse COO gradients + optimizer.step() for the rest.  events: step()'s three timing events (bench.py)."""
-        net = self.net
+        """The row updates of one step from gradients staged in trs_score_fwd_bwd's order (S = 2 item slots) for the
+        triples `ids` / `Bt`: the fused scatter (one launch) for single-lr SGD, the staged tail otherwise.  events:
+        step()'s three timing events (bench.py)."""
+        lrs = {_group_of(self.opt, p)["lr"] for p in self.params} if self.kind == "sgd" else ()
+        if len(lrs) == 1:
+            ops.score_sgd_update(self.net.NET, T, Bt, gr, gl, lrs.pop())
+            if events is not None:
+                e0, e1, e2 = events
+                e2.record()
+                ev = self.kernel_events
+                ev.setdefault("score_kernel<fwd_bwd>", []).append((e0, e1))
+                ev.setdefault("score_sgd_update_kernel", []).append((e1, e2))
+            return
+        self._apply_staged(ids["user"], torch.cat([ids["pos"], ids["neg"]]),
+                           lambda m: torch.cat([ids["pos_meta"][:, m], ids["neg_meta"][:, m]]), 2, gr, gl)
+
+    def _apply_staged(self, user, item_idx, meta_idx, S, gr, gl, skip_user_lin=False):
+        """The tail of every step: each embedding table takes its block of the staged gradients (staged_layout) through
+        the optimiser's rule (module docstring).  user (B,), item_idx (S * B,) and meta_idx(m) -> (S * B,) are the flat
+        ids, slot-major as the fields; a column's ids are built once for its two tables.  skip_user_lin: the user's
+        1-wide block is known to be exactly zero."""
         if self.kind == "sgd":
-            groups = [_group_of(self.opt, p) for p in self.params]
-            lrs = {g["lr"] for g in groups}
-            if len(lrs) == 1:
-                ops.score_sgd_update(net.NET, T, Bt, gr, gl, lrs.pop())
-                if events is not None:
-                    e0, e1, e2 = events
-                    e2.record()
-                    ev = self.kernel_events
-                    ev.setdefault("score_kernel<fwd_bwd>", []).append((e0, e1))
-                    ev.setdefault("score_sgd_update_kernel", []).append((e1, e2))
-            else:
-                self._per_table(ids, gr, gl, lambda p, idx, vals, ld: ops.rows_scatter_add(
-                    p.data, idx, vals, -_group_of(self.opt, p)["lr"], ld=ld))
+            fn = lambda p, idx, vals, ld: ops.rows_scatter_add(p.data, idx, vals, -_group_of(self.opt, p)["lr"], ld=ld)
         elif self.kind in ("sparse_adam", "adagrad"):
-            self._per_table(ids, gr, gl, lambda p, idx, vals, ld: apply_rows(
-                self.kind, self.opt, p, self.row_state[id(p)], idx, vals, ld))
+            fn = lambda p, idx, vals, ld: apply_rows(self.kind, self.opt, p, self.row_state[id(p)], idx, vals, ld)
         else:
             self.opt.zero_grad()
-            self._per_table(ids, gr, gl, self._set_sparse_grad)
+            fn = self._set_sparse_grad
+        B, ids = user.shape[0], {"user": user, "item": item_idx}
+        for table, source, fields, wide in staged_layout(S, self.M, net_has_meta_lin(self.net)):
+            if skip_user_lin and table == 2:
+                continue
+            if source not in ids:
+                ids[source] = meta_idx(source)
+            ld = self.D if wide else 1
+            n = fields.stop - fields.start
+            fn(self.params[table], ids[source], (gr if wide else gl)[fields].reshape(n * B, ld), ld)
+        if self.kind not in ("sgd", "sparse_adam", "adagrad"):
             self.opt.step()
 
     # in-batch softmax (fit(loss='softmax')): (temperature, (n_items,) fp32 log q or None), set by fit()
@@ -542,7 +574,7 @@ class SparseScorerTrainer:
     def softmax_step(self, ids, loss_slot):
         """One step of the in-batch softmax loss on the batch's (user, positive, metadata) rows: every other positive of
         the batch is a negative (ids["neg"] is ignored).  loss_slot receives the SUM of the row losses (caller divides
-        by B).  The gradient rows go through the same per-table paths as step()'s."""
+        by B).  S = 1 item slot; the staged rows go through the one tail (_apply_staged)."""
         tau, logq = self.softmax
         B, D, M = ids["user"].shape[0], self.D, self.M
         net = self.net
@@ -559,25 +591,7 @@ class SparseScorerTrainer:
             i32 = torch.int32
             self._add_l2(ids["user"].to(i32), ids["pos"].to(i32).view(1, B),
                          ids["pos_meta"].to(i32).view(1, B, M) if M else None, gr, gl)
-        if self.kind == "sgd":
-            fn = lambda p, idx, vals, ld: ops.rows_scatter_add(p.data, idx, vals, -_group_of(self.opt, p)["lr"], ld=ld)
-        elif self.kind in ("sparse_adam", "adagrad"):
-            fn = lambda p, idx, vals, ld: apply_rows(self.kind, self.opt, p, self.row_state[id(p)], idx, vals, ld)
-        else:
-            self.opt.zero_grad()
-            fn = self._set_sparse_grad
-        ps = self.params
-        fn(ps[0], ids["user"], gr[0], D)
-        fn(ps[1], ids["pos"], gr[1], D)
-        fn(ps[2], ids["user"], gl[0].reshape(B, 1), 1)
-        fn(ps[3], ids["pos"], gl[1].reshape(B, 1), 1)
-        for m in range(M):
-            midx = ids["pos_meta"][:, m].contiguous()
-            fn(ps[4 + m], midx, gr[2 + m], D)
-            if net_has_meta_lin(net):
-                fn(ps[4 + M + m], midx, gl[2 + m].reshape(B, 1), 1)
-        if self.kind not in ("sgd", "sparse_adam", "adagrad"):
-            self.opt.step()
+        self._apply_staged(ids["user"], ids["pos"], lambda m: ids["pos_meta"][:, m].contiguous(), 1, gr, gl)
 
     # K sampled negatives per positive (fit(n_negatives=K) / fit(loss='sampled_softmax')): (K, loss id of
     # trs_score_multi_fwd_bwd, temperature), set by fit()
@@ -586,11 +600,10 @@ class SparseScorerTrainer:
     def multineg_step(self, ids, loss_slot):
         """One step on rows of one positive and K sampled negatives: ids = ops.batch_prepare_multi's blocks (user (B,),
         items (1 + K, B), meta (1 + K, B, M)).  loss_slot receives the SUM of the row losses (caller divides by B).  One
-        kernel stages every gradient from the pre-update tables; the rows then go through the same per-table paths as
-        step()'s, each table's entries being one contiguous block of the staging buffer.  No host sync."""
+        kernel stages every gradient from the pre-update tables (S = 1 + K item slots); the rows then go through the
+        one tail (_apply_staged), each table's entries being one contiguous block of the staging buffer.  No host sync."""
         K, loss_id, tau = self.multineg
         B, D, M = ids["user"].shape[0], self.D, self.M
-        S1 = 1 + K
         F = ops.multineg_fields(K, M)
         if getattr(self, "_mn_rows", None) is None or self._mn_rows.numel() < F * self.cap * D:
             self._mn_rows = torch.empty(F * self.cap * D, dtype=torch.float32, device=self.dev)
@@ -601,29 +614,11 @@ class SparseScorerTrainer:
         ops.score_multi_fwd_bwd(net.NET, net.tables(), ids["user"], ids["items"], ids.get("meta"), loss_id, tau,
                                 loss_slot, None, gr, gl, self.err)
         self._add_l2(ids["user"], ids["items"], ids.get("meta"), gr, gl)
-        if self.kind == "sgd":
-            fn = lambda p, idx, vals, ld: ops.rows_scatter_add(p.data, idx, vals, -_group_of(self.opt, p)["lr"], ld=ld)
-        elif self.kind in ("sparse_adam", "adagrad"):
-            fn = lambda p, idx, vals, ld: apply_rows(self.kind, self.opt, p, self.row_state[id(p)], idx, vals, ld)
-        else:
-            self.opt.zero_grad()
-            fn = self._set_sparse_grad
-        ps = self.params
-        item_idx = ids["items"].view(-1)  # slot-major, as the staged fields 1 .. 1 + K
-        fn(ps[0], ids["user"], gr[0], D)
-        fn(ps[1], item_idx, gr[1:1 + S1].reshape(S1 * B, D), D)
-        # (under the softmax that block is exactly 0: nothing to apply — unless the user group's penalty was added to it)
-        if loss_id != ops._lib.LOSS_SAMPLED_SOFTMAX or (self.l2 is not None and self.l2[0] > 0):
-            fn(ps[2], ids["user"], gl[0].reshape(B, 1), 1)
-        fn(ps[3], item_idx, gl[1:1 + S1].reshape(S1 * B, 1), 1)
-        for m in range(M):
-            midx = ids["meta"][:, :, m].contiguous().view(-1)  # one copy per column: the ids are (slot, row, column)
-            sl = slice(1 + S1 + m * S1, 1 + S1 + (m + 1) * S1)
-            fn(ps[4 + m], midx, gr[sl].reshape(S1 * B, D), D)
-            if net_has_meta_lin(net):
-                fn(ps[4 + M + m], midx, gl[sl].reshape(S1 * B, 1), 1)
-        if self.kind not in ("sgd", "sparse_adam", "adagrad"):
-            self.opt.step()
+        # under the softmax the user's 1-wide block is exactly 0: nothing to apply — unless the user group's penalty was
+        # added to it.  The ids are (slot, row, column): item ids flat as they lie, one copy per metadata column
+        zero_user_lin = loss_id == ops._lib.LOSS_SAMPLED_SOFTMAX and not (self.l2 is not None and self.l2[0] > 0)
+        self._apply_staged(ids["user"], ids["items"].view(-1), lambda m: ids["meta"][:, :, m].contiguous().view(-1),
+                           1 + K, gr, gl, skip_user_lin=zero_user_lin)
 
     # WARP (fit(loss='warp')): (K, margin, (K,) fp32 device table of rank weights), set by fit()
     warp = None
@@ -657,21 +652,23 @@ class SparseScorerTrainer:
         g = torch.sparse_coo_tensor(idx.reshape(1, -1).long(), vals, size=p.shape)
         p.grad = g if p.grad is None else p.grad + g
 
-    def _per_table(self, ids, gr, gl, fn):
-        """Call fn(param, idx (n,), vals (n, width), ld) once per embedding table with that table's COO entries."""
-        B, D, M = ids["user"].shape[0], self.D, self.M
-        ps = self.params
-        item_idx = torch.cat([ids["pos"], ids["neg"]])
-        fn(ps[0], ids["user"], gr[0], D)
-        fn(ps[1], item_idx, gr[1:3].reshape(2 * B, D), D)
-        fn(ps[2], ids["user"], gl[0].reshape(B, 1), 1)
-        fn(ps[3], item_idx, gl[1:3].reshape(2 * B, 1), 1)
-        for m in range(M):
-            midx = torch.cat([ids["pos_meta"][:, m], ids["neg_meta"][:, m]]).contiguous()
-            sl = slice(3 + 2 * m, 5 + 2 * m)
-            fn(ps[4 + m], midx, gr[sl].reshape(2 * B, D), D)
-            if net_has_meta_lin(self.net):
-                fn(ps[4 + M + m], midx, gl[sl].reshape(2 * B, 1), 1)
+    def per_step_only(self):
+        """Does this configuration need FitRunner's per-step loop?  The in-batch softmax, K sampled negatives and WARP
+        have their own staging kernels, and the L2 penalty is added to staged gradients, which neither the C step loop
+        nor the presorted path has.  (Mining is the sampler's property: FitRunner asks it.)"""
+        return (self.softmax is not None or self.multineg is not None or self.warp is not None
+                or self.l2 is not None)
+
+    def n_candidates(self):
+        """K when the step takes ops.batch_prepare_multi's blocks of K candidates per row, else None."""
+        multi = self.multineg or self.warp
+        return multi[0] if multi else None
+
+    def loss_step(self, ids, loss_slot):
+        """One step of the loss fit() configured."""
+        step = (self.softmax_step if self.softmax is not None else self.multineg_step if self.multineg is not None
+                else self.warp_step if self.warp is not None else self.step)
+        step(ids, loss_slot)
 
     def check_errors(self):
         from .collaborative._scorer import check_err_flag

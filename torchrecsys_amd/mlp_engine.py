@@ -411,6 +411,12 @@ class MLPTrainer:
         self.keep_ctx = False  # tests: keep the last step's forward context (y_l, batch statistics) in self.last_ctx
         self.last_ctx = None
 
+    def per_step_only(self):
+        return False  # (FitRunner.run_steps: nothing here needs the staged per-step loop)
+
+    def loss_step(self, ids, loss_slot):
+        self.step(ids, loss_slot)
+
     def step(self, ids, loss_slot, auc_slot=None, score_grad=None):
         """One training step.  score_grad (optional, (2B,) fp32: d loss / d score of the positive rows, then of the
         negative rows) replaces the gradient of the built-in pairwise loss — a caller's own loss, and what the full-size

@@ -10,6 +10,7 @@ Same constructor keywords, same methods, same printed strings, same state_dict k
         benchmark runs in
   seed : seed of the device-side generators (rng='device')
 """
+import collections
 import functools
 import math
 import os
@@ -115,7 +116,14 @@ def _check_l2(l2, net_type):
     return lam
 
 
+# What fit() trains on, as its validation chose it: kind 'pair' (hinge / bpr on one negative) | 'softmax' (in-batch) |
+# 'multineg' (K sampled negatives) | 'warp'; loss_id the pair loss (_lib.LOSS_ID) of 'pair' and of 'multineg' (there
+# also _lib.LOSS_SAMPLED_SOFTMAX); logq the (n_items,) device table or None; rank_weight 'log' | 'harmonic'
+Objective = collections.namedtuple("Objective", "kind loss_id K temperature logq margin rank_weight")
+
+
 class TorchRecSys(torch.nn.Module):
+    _objective = Objective('pair', 0, 1, 1.0, None, 1.0, 'log')  # never fitted: evaluate() reports the hinge loss
 
     @_host_side
     def __init__(self,
@@ -548,22 +556,20 @@ class TorchRecSys(torch.nn.Module):
         if self.net_type == 'mlp':
             self.net.compute.sync_bn = bool(sync_bn)
         runner = self.make_runner(optimizer, batch_size)
-        if loss == 'softmax':
-            self._softmax = (tau, self._logq(runner.data) if logq_correction else None)
-            runner.trainer.softmax = self._softmax
-        elif multineg:  # K sampled negatives per positive: engine.SparseScorerTrainer.multineg_step
-            self._multineg = (n_negatives, LOSS_ID.get(loss, LOSS_SAMPLED_SOFTMAX), tau if loss == 'sampled_softmax' else 1.0)
-            runner.trainer.multineg = self._multineg
-        elif warp:  # the first margin violator among K candidates: engine.SparseScorerTrainer.warp_step
-            self._warp = (n_negatives, margin, rank_weight)
-            runner.trainer.warp = (n_negatives, margin,
-                                   ops.warp_rank_weights(self.n_items, n_negatives, rank_weight, _device()))
+        obj = self._objective = Objective(
+            kind='softmax' if loss == 'softmax' else 'multineg' if multineg else 'warp' if warp else 'pair',
+            loss_id=LOSS_ID.get(loss, LOSS_SAMPLED_SOFTMAX if multineg else 0), K=n_negatives,
+            temperature=tau if loss in ('softmax', 'sampled_softmax') else 1.0,
+            logq=self._logq(runner.data) if loss == 'softmax' and logq_correction else None,
+            margin=margin, rank_weight=rank_weight)
+        if obj.kind == 'softmax':  # engine.SparseScorerTrainer.softmax_step
+            runner.trainer.softmax = (obj.temperature, obj.logq)
+        elif obj.kind == 'multineg':  # K sampled negatives per positive: engine.SparseScorerTrainer.multineg_step
+            runner.trainer.multineg = (obj.K, obj.loss_id, obj.temperature)
+        elif obj.kind == 'warp':  # the first margin violator among K candidates: engine.SparseScorerTrainer.warp_step
+            runner.trainer.warp = (obj.K, obj.margin, ops.warp_rank_weights(self.n_items, obj.K, obj.rank_weight, _device()))
         else:
-            runner.trainer.loss_id = LOSS_ID[loss]
-        if not multineg:
-            self._multineg = None
-        if not warp:
-            self._warp = None
+            runner.trainer.loss_id = obj.loss_id
         if l2 is not None:  # engine.SparseScorerTrainer._add_l2: one launch between a step's staging and its row updates
             runner.trainer.l2 = l2
         self.loss = loss
@@ -649,21 +655,26 @@ class TorchRecSys(torch.nn.Module):
         # Linear / FM score triples independently of their batch: several batches per launch (ids, scores, per-batch
         # reductions, one id-range check per group); the MLP's activations are per batch
         # fit(loss='softmax'): every test batch is its own softmax, one batch at a time
-        softmax = getattr(self, "loss", "hinge") == "softmax" and hasattr(self.net, 'table_params')
-        multineg = getattr(self, "_multineg", None) if hasattr(self.net, 'table_params') else None
-        multineg = multineg if self.rng == 'device' else None
-        warp = getattr(self, "_warp", None) if hasattr(self.net, 'table_params') and self.rng == 'device' else None
-        if multineg is not None:
-            self._evaluate_multineg(multineg, st, sample_seed, nb, batch_size, n_test, loss_sums, auc_counts)
-        if warp is not None:
-            self._evaluate_warp(warp, st, sample_seed, nb, batch_size, n_test, loss_sums, auc_counts)
+        obj = self._objective
+        softmax = obj.kind == 'softmax'
+        if obj.kind == 'multineg':  # the same loss over K candidates of the evaluation sampler's rules
+            self._evaluate_candidates(obj.K, st, sample_seed, nb, batch_size, n_test, lambda ids, b, err: (
+                ops.score_multi_fwd_bwd(self.net.NET, self.net.tables(), ids['user'], ids['items'], ids.get('meta'),
+                                        obj.loss_id, obj.temperature, loss_sums[b:b + 1], auc_counts[b:b + 1],
+                                        err_flag=err, forward_only=True)))
+        elif obj.kind == 'warp':
+            weights = ops.warp_rank_weights(self.n_items, obj.K, obj.rank_weight, dev)
+            self._evaluate_candidates(obj.K, st, sample_seed, nb, batch_size, n_test, lambda ids, b, err: (
+                ops.score_warp_fwd_bwd(self.net.NET, self.net.tables(), ids['user'], ids['items'], ids.get('meta'),
+                                       obj.margin, weights, loss_sums[b:b + 1], auc_counts[b:b + 1], err_flag=err,
+                                       forward_only=True, want_trials=False)))
         group = 64 if hasattr(self.net, 'table_params') and not softmax else 1
         group = max(1, min(group, (1 << 22) // max(batch_size, 1)))
         if softmax:
             sm_loss = torch.zeros(nb, dtype=torch.float32, device=dev)
             sm = ops.InBatchSoftmax(min(batch_size, n_test), self.n_factors, dev)
             err = torch.zeros(1, dtype=torch.int32, device=dev)
-        for b0 in (range(0, nb, group) if multineg is None and warp is None else ()):  # (the pair / in-batch softmax batches)
+        for b0 in (range(0, nb, group) if obj.kind in ('pair', 'softmax') else ()):
             b1 = min(b0 + group, nb)
             s, e = b0 * batch_size, min(b1 * batch_size, n_test)
             if self.rng == 'reference':
@@ -672,12 +683,10 @@ class TorchRecSys(torch.nn.Module):
                 ids = ops.batch_prepare(st['user'], st['pos'], st['neg'], 0, s, e - s, self.n_items, sample_seed, s,
                                         st['item_meta'], sampler=self._eval_sampler())
             pos, neg = self.net.score_ids(ids)
-            from ._lib import LOSS_ID
-            ops.hinge_auc_batches(pos, neg, batch_size, loss_sums[b0:b1], auc_counts[b0:b1],
-                                  loss=LOSS_ID.get(getattr(self, "loss", "hinge"), 0))
+            ops.hinge_auc_batches(pos, neg, batch_size, loss_sums[b0:b1], auc_counts[b0:b1], loss=obj.loss_id)
             if softmax:
                 Bt, keep = ops.make_batch(ids['user'], ids['pos'], None, ids.get('pos_meta'), None, err)
-                sm(self.net.NET, self.net.tables(), Bt, self._softmax[0], self._softmax[1], sm_loss[b0:b0 + 1])
+                sm(self.net.NET, self.net.tables(), Bt, obj.temperature, obj.logq, sm_loss[b0:b0 + 1])
         if softmax:
             check_err_flag(err, "evaluate")
             loss_sums = sm_loss
@@ -700,11 +709,11 @@ class TorchRecSys(torch.nn.Module):
             self.eval_results[metric] = value
             print(f'|--- Testing {metric}: {value:.4f}')
 
-    def _evaluate_multineg(self, multineg, st, sample_seed, nb, batch_size, n_test, loss_sums, auc_counts):
-        """evaluate() after fit(n_negatives=K) / fit(loss='sampled_softmax'): the same loss over K candidates of the
-        evaluation sampler's rules, one test batch per forward-only launch; the AUC count is pairwise on (p, c_0)."""
-        K, loss_id, tau = multineg
-        err = torch.zeros(1, dtype=torch.int32, device=loss_sums.device)
+    def _evaluate_candidates(self, K, st, sample_seed, nb, batch_size, n_test, score):
+        """evaluate() after a fit on K candidates per row (n_negatives=K, loss='sampled_softmax', loss='warp'): one test
+        batch of ops.batch_prepare_multi's blocks per forward-only launch score(ids, batch number, error flag), which
+        adds the batch's loss sum and its AUC count, pairwise on (p, c_0)."""
+        err = torch.zeros(1, dtype=torch.int32, device=st['user'].device)
         out = None
         for b in range(nb):
             s, e = b * batch_size, min((b + 1) * batch_size, n_test)
@@ -713,28 +722,7 @@ class TorchRecSys(torch.nn.Module):
                                           sampler=self._eval_sampler())
             if e - s == batch_size:
                 out = ids
-            ops.score_multi_fwd_bwd(self.net.NET, self.net.tables(), ids['user'], ids['items'], ids.get('meta'),
-                                    loss_id, tau, loss_sums[b:b + 1], auc_counts[b:b + 1], err_flag=err,
-                                    forward_only=True)
-        check_err_flag(err, "evaluate")
-
-    def _evaluate_warp(self, warp, st, sample_seed, nb, batch_size, n_test, loss_sums, auc_counts):
-        """evaluate() after fit(loss='warp'): the WARP loss over K candidates of the evaluation sampler's rules, one test
-        batch per forward-only launch; the AUC count is pairwise on (p, c_0)."""
-        K, margin, kind = warp
-        weights = ops.warp_rank_weights(self.n_items, K, kind, loss_sums.device)
-        err = torch.zeros(1, dtype=torch.int32, device=loss_sums.device)
-        out = None
-        for b in range(nb):
-            s, e = b * batch_size, min((b + 1) * batch_size, n_test)
-            ids = ops.batch_prepare_multi(st['user'], st['pos'], 0, s, e - s, self.n_items, sample_seed, s, K,
-                                          st['item_meta'], out if e - s == batch_size else None,
-                                          sampler=self._eval_sampler())
-            if e - s == batch_size:
-                out = ids
-            ops.score_warp_fwd_bwd(self.net.NET, self.net.tables(), ids['user'], ids['items'], ids.get('meta'), margin,
-                                   weights, loss_sums[b:b + 1], auc_counts[b:b + 1], err_flag=err, forward_only=True,
-                                   want_trials=False)
+            score(ids, b, err)
         check_err_flag(err, "evaluate")
 
     # ------------------------------------------------------------------------------------------------ predict
@@ -1162,20 +1150,14 @@ class FitRunner:
         if os.environ.get("TRS_META_FAST", "1") == "0" and has_meta:
             kind = None  # tuning / fall-back knob: metadata scorers on the generic staged path
         fast = (kind == "sgd" and not has_meta) or (kind is not None and self.trainer.wants_presort(B))
-        softmax = getattr(self.trainer, "softmax", None) is not None
-        fast = fast and not softmax  # the in-batch softmax runs on the generic loop below
+        # losses and regularisers that stage their gradients step by step (engine.SparseScorerTrainer.per_step_only):
+        # the per-step loop below, on K candidates per row where the loss trains on them
+        per_step = self.trainer.per_step_only()
+        n_cand = self.trainer.n_candidates() if per_step else None
         # score-aware mining: the negative of step t depends on the tables after step t - 1, so neither the slice-ahead
         # presort nor the C step loop applies — the per-step loop below, one mining launch in front of every step
         mining = getattr(self.sampler, "mine", None) is not None
-        fast = fast and not mining
-        # K sampled negatives per positive: a prepare launch, then the staging kernel and the per-table row updates
-        multineg = getattr(self.trainer, "multineg", None)
-        fast = fast and multineg is None
-        # WARP: the same prepare launch (K candidates per row), then the kernel that picks the first violator + the step's tail
-        warp = getattr(self.trainer, "warp", None)
-        fast = fast and warp is None
-        # per-sample L2 (fit(l2=...)): the penalty is added to the staged gradients, which only the per-step loop has
-        fast = fast and getattr(self.trainer, "l2", None) is None
+        fast = fast and not per_step and not mining
         if fast and m.rng == 'reference':
             fast = self.ep['user'].dtype == torch.int32
         ops.stamp("run_steps:setup")
@@ -1219,9 +1201,9 @@ class FitRunner:
             else:
                 st = self.st
                 out = self.prep_out if (self.prep_out is not None and e - s == B) else None
-                if multineg is not None or warp is not None:
+                if n_cand is not None:
                     ids = ops.batch_prepare_multi(st['user'], st['pos'], self.shuffle_key, s, e - s, m.n_items,
-                                                  self.sample_seed, s, (multineg or warp)[0], st['item_meta'], out,
+                                                  self.sample_seed, s, n_cand, st['item_meta'], out,
                                                   sampler=self.sampler)
                 elif mining:  # K candidates scored under the tables as step b - 1 left them, one launch on this stream
                     ids = ops.batch_prepare_mined(st['user'], st['pos'], self.shuffle_key, s, e - s, m.n_items,
@@ -1232,14 +1214,7 @@ class FitRunner:
                                             self.sample_seed, s, st['item_meta'], out, sampler=self.sampler)
                 if e - s == B:
                     self.prep_out = ids
-            if softmax:
-                self.trainer.softmax_step(ids, self.loss_sums[b:b + 1])
-            elif multineg is not None:
-                self.trainer.multineg_step(ids, self.loss_sums[b:b + 1])
-            elif warp is not None:
-                self.trainer.warp_step(ids, self.loss_sums[b:b + 1])
-            else:
-                self.trainer.step(ids, self.loss_sums[b:b + 1])
+            self.trainer.loss_step(ids, self.loss_sums[b:b + 1])
             self.next_batch += 1
             done += 1
         return done

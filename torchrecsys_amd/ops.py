@@ -510,16 +510,21 @@ def sample_neg(pos, n_items, seed, offset):
     return neg
 
 
+def _pair_out(B, M, dev):  # the int32 blocks batch_prepare / batch_prepare_mined fill
+    out = {k: torch.empty(B, dtype=torch.int32, device=dev) for k in ("user", "pos", "neg")}
+    if M:
+        out["pos_meta"] = torch.empty((B, M), dtype=torch.int32, device=dev)
+        out["neg_meta"] = torch.empty((B, M), dtype=torch.int32, device=dev)
+    return out
+
+
 def batch_prepare(stream_user, stream_item, neg_static, shuffle_key, t0, B, n_items, seed, offset, item_meta=None,
                   out=None, sampler=None):
     """Returns dict of int32 GPU tensors user/pos/neg[/pos_meta/neg_meta] for epoch positions [t0, t0+B)."""
     dev = stream_user.device
     M = 0 if item_meta is None else item_meta.shape[1]
     if out is None:
-        out = {k: torch.empty(B, dtype=torch.int32, device=dev) for k in ("user", "pos", "neg")}
-        if M:
-            out["pos_meta"] = torch.empty((B, M), dtype=torch.int32, device=dev)
-            out["neg_meta"] = torch.empty((B, M), dtype=torch.int32, device=dev)
+        out = _pair_out(B, M, dev)
     check(_lib.load().trs_batch_prepare(ptr(stream_user), ptr(stream_item), ptr(neg_static), stream_user.numel(),
                                         int(shuffle_key), int(t0), int(B), int(n_items), int(seed), int(offset),
                                         ptr(item_meta), M, ptr(out["user"]), ptr(out["pos"]), ptr(out["neg"]),
@@ -541,10 +546,7 @@ def batch_prepare_mined(stream_user, stream_item, shuffle_key, t0, B, n_items, s
         raise ValueError(f"hard-negative mining scores candidates with the Linear / FM kernels, not net={net!r}")
     M = 0 if item_meta is None else item_meta.shape[1]
     if out is None:
-        out = {k: torch.empty(B, dtype=torch.int32, device=dev) for k in ("user", "pos", "neg")}
-        if M:
-            out["pos_meta"] = torch.empty((B, M), dtype=torch.int32, device=dev)
-            out["neg_meta"] = torch.empty((B, M), dtype=torch.int32, device=dev)
+        out = _pair_out(B, M, dev)
     if return_chosen and "chosen" not in out:
         out["chosen"] = torch.empty(B, dtype=torch.int32, device=dev)
     check(_lib.load().trs_batch_prepare_mined(ptr(stream_user), ptr(stream_item), None, stream_user.numel(),
@@ -581,6 +583,22 @@ def batch_prepare_multi(stream_user, stream_item, shuffle_key, t0, B, n_items, s
     return out
 
 
+def _check_blocks(user, items, meta, M, multi, also=()):
+    """Checks the int32 id blocks user (B,), items (S, B), meta (S, B, M where M > 0) of a step; multi: they are
+    batch_prepare_multi's, S = 1 + K >= 2.  also: (tensor, name, dtype) checked with them.  Returns (B, S)."""
+    for t, name, dtype in (user, "user ids", torch.int32), (items, "item id block", torch.int32), \
+            (meta, "metadata id block", torch.int32), *also:
+        _dev(t, name, dtype)
+    if items.dim() != 2 or items.shape[1] != user.shape[0] or items.shape[0] < 1 + multi:
+        raise ValueError("items must be the (1 + K, B) block of batch_prepare_multi" if multi else
+                         "items must be an (S, B) block of item ids, slot-major")
+    B, S = user.shape[0], items.shape[0]
+    if M and (meta is None or tuple(meta.shape) != (S, B, M)):
+        raise ValueError(f"meta must be the (1 + K, B, M) = ({S}, {B}, {M}) block of batch_prepare_multi" if multi else
+                         f"meta must be the (S, B, M) = ({S}, {B}, {M}) block of metadata ids")
+    return B, S
+
+
 def multineg_fields(K, M):
     """Staged gradient fields of score_multi_fwd_bwd: 1 user + (1 + K) item slots + M * (1 + K) metadata slots."""
     return 1 + (1 + K) * (1 + M)
@@ -593,14 +611,8 @@ def score_multi_fwd_bwd(net, T, user, items, meta, loss, tau, loss_sum, auc_coun
     _lib.LOSS_ID (mean of K pairs) or _lib.LOSS_SAMPLED_SOFTMAX (with temperature tau).  loss_sum / auc_count are
     accumulated in place.  Returns (grad_rows (F, B, D), grad_lin (F, B)), F = multineg_fields(K, M), field-major: the
     user, the 1 + K item slots, then the 1 + K slots of every metadata column; (None, None) with forward_only."""
-    _dev(user, "user ids", torch.int32)
-    _dev(items, "item id block", torch.int32)
-    _dev(meta, "metadata id block", torch.int32)
-    if items.dim() != 2 or items.shape[1] != user.shape[0] or items.shape[0] < 2:
-        raise ValueError("items must be the (1 + K, B) block of batch_prepare_multi")
-    B, K, D, M = user.shape[0], items.shape[0] - 1, T.D, T.M
-    if M and (meta is None or tuple(meta.shape) != (1 + K, B, M)):
-        raise ValueError(f"meta must be the (1 + K, B, M) = ({1 + K}, {B}, {M}) block of batch_prepare_multi")
+    B, S = _check_blocks(user, items, meta, T.M, True)
+    K, D, M = S - 1, T.D, T.M
     if forward_only:
         grad_rows = grad_lin = None
     else:
@@ -655,15 +667,8 @@ def score_warp_fwd_bwd(net, T, user, items, meta, margin, rank_weight, loss_sum,
     auc_count are accumulated in place.  Returns (neg (B,), neg_meta (B, M) or None, trials (B,) or None, grad_rows
     (3 + 2M, B, D), grad_lin (3 + 2M, B)) — the staging order of score_fwd_bwd on (user, items[0], neg); the last two
     are None with forward_only."""
-    _dev(user, "user ids", torch.int32)
-    _dev(items, "item id block", torch.int32)
-    _dev(meta, "metadata id block", torch.int32)
-    _dev(rank_weight, "rank_weight", torch.float32)
-    if items.dim() != 2 or items.shape[1] != user.shape[0] or items.shape[0] < 2:
-        raise ValueError("items must be the (1 + K, B) block of batch_prepare_multi")
-    B, K, D, M = user.shape[0], items.shape[0] - 1, T.D, T.M
-    if M and (meta is None or tuple(meta.shape) != (1 + K, B, M)):
-        raise ValueError(f"meta must be the (1 + K, B, M) = ({1 + K}, {B}, {M}) block of batch_prepare_multi")
+    B, S = _check_blocks(user, items, meta, T.M, True, [(rank_weight, "rank_weight", torch.float32)])
+    K, D, M = S - 1, T.D, T.M
     if rank_weight is None or rank_weight.numel() != K:
         raise ValueError(f"rank_weight must hold K = {K} floats")
     dev = user.device
@@ -697,17 +702,10 @@ def stage_add_l2(net, T, user, items, meta, coefs, grad_rows, grad_lin, err_flag
     user (B,), items (S, B), meta (S, B, M) or None: int32, the blocks of batch_prepare_multi.  coefs = (c_user, c_item,
     c_meta), each already holding the 1/B of the batch mean; a group at 0 is skipped.  grad_rows (F, B, D) and grad_lin
     (F, B), F = 1 + S * (1 + M), field-major: the user, the S item slots, then the S slots of every metadata column."""
-    _dev(user, "user ids", torch.int32)
-    _dev(items, "item id block", torch.int32)
-    _dev(meta, "metadata id block", torch.int32)
-    _dev(grad_rows, "grad_rows", torch.float32)
-    _dev(grad_lin, "grad_lin", torch.float32)
-    if items.dim() != 2 or items.shape[1] != user.shape[0] or items.shape[0] < 1:
-        raise ValueError("items must be an (S, B) block of item ids, slot-major")
-    B, S, D, M = user.shape[0], items.shape[0], T.D, T.M
     c_user, c_item, c_meta = (float(c) for c in coefs)
-    if M and c_meta > 0 and (meta is None or tuple(meta.shape) != (S, B, M)):
-        raise ValueError(f"meta must be the (S, B, M) = ({S}, {B}, {M}) block of metadata ids")
+    D, M = T.D, T.M
+    B, S = _check_blocks(user, items, meta, M if c_meta > 0 else 0, False,  # (meta is read only with its coefficient)
+                         [(grad_rows, "grad_rows", torch.float32), (grad_lin, "grad_lin", torch.float32)])
     F = 1 + S * (1 + M)
     if grad_rows is None or tuple(grad_rows.shape) != (F, B, D):
         raise ValueError(f"grad_rows must be the (F, B, D) = ({F}, {B}, {D}) staging buffer")
