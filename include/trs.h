@@ -99,13 +99,14 @@ const char* trs_last_error(void);
  *   6: batched top-k retrieval: trs_csr, trs_item_fold(_bytes), trs_retrieve_topk, trs_retrieve_workspace_bytes,
  *      trs_mask_seen, trs_rank_metrics.  (Entry points added since without touching an existing signature or struct:
  *      the in-batch softmax group, trs_batch_prepare_mined, trs_batch_prepare_multi, trs_score_multi_fwd_bwd,
- *      trs_score_warp_fwd_bwd, TRS_LOSS_WARP, trs_stage_add_l2, trs_neighbour_fold, trs_neighbours_topk.) */
+ *      trs_score_warp_fwd_bwd, TRS_LOSS_WARP, trs_stage_add_l2, trs_neighbour_fold, trs_neighbours_topk,
+ *      trs_fold_in_users.) */
 #define TRS_ABI_VERSION 6
 #define TRS_SYNC_WORDS 288
 #define TRS_SYNC_REBASE 0x40000000u /* arrivals after which trs_train_steps_sgd zeroes sync_dev and its host count */
 int trs_abi_version(void);
 /* Tuning / A-B knobs of the launch paths (kernel selection, launch shapes): GRID_CAP, PASS_GRID_CAP, K1_ITERS,
- * PASS_ITERS, PRESORT_GRID_CAP, PASS_NT, K1_NT, K1_WGS_PER_CU, GEMM32_NO_GLDS, GEMM16_TN_WIDE, GEMM16_TILE, GEMM16_NO_GLDS, BN_FINAL_TWO_SWEEPS (meanings:
+ * PASS_ITERS, PRESORT_GRID_CAP, PASS_NT, K1_NT, K1_WGS_PER_CU, GEMM32_NO_GLDS, GEMM16_TN_WIDE, GEMM16_TILE, GEMM16_NO_GLDS, BN_FINAL_TWO_SWEEPS, FOLDIN_DEPTH (meanings:
  * csrc/trs_common.h TrsTuning).  The library reads TRS_<name> from the environment ONCE, at its first use; this entry
  * point changes a knob afterwards (tests, tools): unset != 0 restores the default.  The defaults are the measured best. */
 int trs_tuning_set(const char* name, int64_t value, int32_t unset);
@@ -660,6 +661,41 @@ int trs_neighbour_fold(const float* rows_dev, int64_t n_rows, int32_t D, int64_t
 int trs_neighbours_topk(const void* fold_dev, int64_t fold_bytes, int64_t n_rows, int32_t D,
                         const int64_t* queries_dev, int64_t n_q, int32_t k, int64_t* ids_out_dev,
                         float* scores_out_dev, void* workspace_dev, int64_t workspace_bytes, void* stream);
+
+/* --------------------------------------------------------- fold-in of unseen users (fold_in_users) */
+/* One new user row per item history, the item side frozen: E epochs of per-visit SGD on z(u,i) = (<u, S_i> + b) + c_i,
+ * S and c those of a trs_item_fold buffer of (n_items, D) (layout unchanged, read only).  One launch for all users.
+ * Added without touching an existing signature or struct.
+ * hist: CSR of the n_new = hist->n_rows new users, off int64 (n_new + 1), items int32; every row holds sorted, distinct
+ * dense item rows; n_h = off[h+1] - off[h].  State per user h: u in R^D = 0, b = 0, fp32.
+ * For epoch e = 0 .. E-1, visit j = 0 .. n_h-1, in this order, sequentially:
+ *   order      r = j when shuffle == 0, else r = trs_feistel_perm(j, n_h, key_e, trs_feistel_half_bits(n_h)), key_e =
+ *              ((y << 32) | x) | 1 of trs_philox4x32_10(counter = e, key = (seed + 0xD1B54A32D192ED03) mod 2^64);
+ *              p = items[off[h] + r].
+ *   negative   n = trs_sample_neg_opt(seed, ctr = ((uint64)e << 32) | r, u = h, pos = p, n_items, sampler): max_tries
+ *              candidates, one rejected while the history holds it (the seen CSR is the history CSR itself) when
+ *              reject_seen; the last candidate is kept whatever it is, as in training.  Without reject_seen every
+ *              max_tries gives the plain draw trs_sample_one_neg (max_tries = 0 calls it).  No popularity option.
+ *   purity     the schedule depends on (seed, e, r, n_h) and the history only, not on h or on what else is in the call:
+ *              a history folds in to the same row alone or among 10 000 others.
+ *   scores     z_p = (sum_d u_d * S_{p,d} + b) + c_p, z_n likewise; s = z (Linear), s = sigmoid(z) (FM).  The order of
+ *              the sum over d is the kernel's (per lane four ascending columns, then trs_group_sum).
+ *   loss       (value, dneg) = trs_pair_loss(loss, s_p, s_n), loss = TRS_LOSS_HINGE (active at h >= 0) | TRS_LOSS_BPR.
+ *   gradients  g_p = -dneg * w_p, g_n = dneg * w_n; w = 1 (Linear), w = s (1 - s) (FM).
+ *   update     u_d <- u_d - lr * ((g_p * S_{p,d} + g_n * S_{n,d}) + l2 * u_d);  b <- b - lr * ((g_p + g_n) + l2 * b)
+ *              (Linear: g_p + g_n = 0, so with l2 = 0 the bias stays exactly 0); every product and sum rounded to fp32.
+ *   loss_out   loss_out[e][h] = (sum of the epoch's values in visit order) / n_h; 0 for an empty history.
+ * An item id outside [0, n_items) is never used as an address: that visit is skipped (no update, nothing added to the
+ * loss sum) and bit 0 of *err_flag_dev (may be NULL) is set.
+ * Outputs: user_out (n_new, D), user_lin_out (n_new), loss_out (epochs, n_new) or NULL; each written once.
+ * TRS_E_ARG, nothing launched: net not TRS_NET_LINEAR / TRS_NET_FM; D outside 1..TRS_RETRIEVE_DMAX; n_items < 2 (or
+ * >= 2^31); fold_dev NULL or fold_bytes < trs_item_fold_bytes(n_items, D); loss not hinge / BPR; epochs outside
+ * 1..1024; lr not finite or <= 0; l2 not finite or < 0; max_tries outside 0..64; reject_seen with max_tries == 0; hist
+ * NULL; with n_new > 0 a NULL array of hist or a NULL user_out / user_lin_out.  n_new == 0: TRS_OK, nothing launched. */
+int trs_fold_in_users(int net, const void* fold_dev, int64_t fold_bytes, int64_t n_items, int32_t D,
+                      const trs_csr* hist, int32_t loss, int32_t epochs, float lr, float l2, uint64_t seed,
+                      int32_t shuffle, int32_t reject_seen, int32_t max_tries, float* user_out_dev,
+                      float* user_lin_out_dev, float* loss_out_dev, int32_t* err_flag_dev, void* stream);
 
 /* ------------------------------------------------------------------------------- in-batch softmax (fit) */
 /* Training loss of fit(loss='softmax') for the Linear / FM scorers (Yi et al., RecSys 2019).  Batch

@@ -56,6 +56,7 @@ struct TrsTuning {
   int gemm16_tile;        // TRS_GEMM16_TILE     128 | 256 | 512: force the bf16-resident tile (0)
   int gemm16_no_glds;     // TRS_GEMM16_NO_GLDS  1: bf16 NT GEMMs on the register-staged 256 x 256 kernel
   int bn_final_two_sweeps;  // TRS_BN_FINAL_TWO_SWEEPS  1: the two-sweep finalise kernels
+  int foldin_depth;       // TRS_FOLDIN_DEPTH    visits whose rows trs_fold_in_users keeps requested: 1 | 2 | 4 | 8 (4)
 };
 TrsTuning& trs_tuning();
 

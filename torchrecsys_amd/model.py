@@ -875,6 +875,140 @@ class TorchRecSys(torch.nn.Module):
             ids[keep] = idx.cpu().to(torch.int64)[ids[keep]]
         return (ids, scores.cpu()) if return_scores else ids
 
+    # ------------------------------------------------------------------------------------------------ fold-in
+    def _check_fold_in(self, what, epochs, lr, loss, l2, seed, max_tries, reject_seen):
+        """Argument checks of fold_in_users / recommend_for_histories (before any device work)."""
+        if self.net_type not in ('linear', 'fm'):
+            raise ValueError(f"{what} needs net_type 'linear' or 'fm': with net_type={self.net_type!r} (mlp) a user is "
+                             "not an inner-product row against a folded item matrix")
+        if self.n_factors > ops._lib.RETRIEVE_DMAX:
+            raise ValueError(f"{what} takes n_factors <= {ops._lib.RETRIEVE_DMAX} (TRS_RETRIEVE_DMAX), got "
+                             f"{self.n_factors}")
+
+        def integer(v, name, lo, hi):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+                raise ValueError(f"{name} must be an integer in {lo}..{hi}, got {v!r}")
+
+        def number(v, name, positive):
+            ok = isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and math.isfinite(v)
+            if not ok or (v <= 0 if positive else v < 0):
+                raise ValueError(f"{name} must be a finite number {'> 0' if positive else '>= 0'}, got {v!r}")
+        integer(epochs, "epochs", 1, 1024)
+        number(lr, "lr", True)
+        number(l2, "l2", False)
+        if loss not in ('hinge', 'bpr'):
+            raise ValueError(f"loss must be 'hinge' or 'bpr', got {loss!r}")
+        integer(seed, "seed", -(1 << 63), (1 << 64) - 1)
+        integer(max_tries, "max_tries", 0, 64)
+        if reject_seen and int(max_tries) < 1:
+            raise ValueError("reject_seen needs max_tries >= 1")
+
+    def _history_csr(self, histories):
+        """Host side of fold-in: original item ids -> dense rows (IndexError on an unknown id), every history sorted and
+        de-duplicated, the users ordered by history length, longest first (the lane groups of a wave then have similar
+        trip counts and the long tails start first).  Returns (offsets int64 (n+1,), items int32, rank) as numpy arrays:
+        row rank[r] of the CSR is the caller's history r."""
+        hs = [np.asarray(h.tolist() if hasattr(h, "tolist") else list(h), dtype=np.int64).reshape(-1) for h in histories]
+        n = len(hs)
+        lens = np.array([h.size for h in hs], dtype=np.int64)
+        flat = np.concatenate(hs) if n and lens.sum() else np.zeros(0, dtype=np.int64)
+        dense = self._dense_rows(flat, getattr(self.data_processor, "item_index", None), self.n_items, 'item').numpy()
+        key = np.unique(np.repeat(np.arange(n, dtype=np.int64), lens) * int(self.n_items) + dense)
+        rows, items = key // int(self.n_items), key % int(self.n_items)
+        counts = np.bincount(rows, minlength=n).astype(np.int64)
+        order = np.argsort(-counts, kind='stable')
+        rank = np.empty(n, dtype=np.int64)
+        rank[order] = np.arange(n, dtype=np.int64)
+        off_orig = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        off = np.concatenate([[0], np.cumsum(counts[order])]).astype(np.int64)
+        out = np.empty(items.size, dtype=np.int32)
+        out[off[rank[rows]] + (np.arange(items.size, dtype=np.int64) - off_orig[rows])] = items
+        return off, out, rank
+
+    def _fold_in_dense(self, off, items, opts, want_loss):
+        """Fold-in of a dense history CSR (numpy) on the device: (fold, (off, items) on the GPU, U, b, loss | None)."""
+        dev = _device()
+        self.net = self.net.eval()
+        fold = ops.item_fold(self.net.NET, self.net.tables(), self.n_items, self.n_factors, dev, self._item_meta_dev())
+        hist = (torch.from_numpy(off).to(dev), torch.from_numpy(items).to(dev))
+        U, b, ls = ops.fold_in_users(self.net.NET, fold, self.n_items, self.n_factors, hist, opts['loss'],
+                                     opts['epochs'], opts['lr'], opts['l2'], opts['seed'], opts['shuffle'],
+                                     opts['reject_seen'], opts['max_tries'], want_loss=want_loss)
+        return fold, hist, U, b, ls
+
+    @_host_side
+    def fold_in_users(self, histories, epochs: int = 8, lr: float = 0.05, loss: str = 'hinge', l2: float = 0.0,
+                      seed: int = 0, shuffle: bool = True, reject_seen: bool = True, max_tries: int = 8,
+                      return_loss: bool = False):
+        """Rows for users the model has never seen, fitted to their item histories with the item side frozen: CPU
+        tensors U (n, n_factors) fp32 and b (n,) fp32 — what the user table and user_bias / linear_user would hold —
+        and with return_loss the (epochs, n) fp32 mean pair loss of every epoch.
+        histories: a sequence of sequences / 1-D arrays of original item ids (an unknown id raises IndexError); each is
+        sorted and de-duplicated first.  Per user, `epochs` passes of per-visit SGD over the history (shuffled per epoch
+        when `shuffle`), one sampled negative per visit (one the history holds is redrawn, at most max_tries candidates,
+        when reject_seen), loss 'hinge' or 'bpr' on the scorer's outputs, step lr, L2 coefficient l2 on u and b; the
+        exact rule is in include/trs.h ("fold-in").  The result for a history does not depend on the other histories of
+        the call.  An empty history gives u = 0, b = 0.  One kernel launch for all users.
+        Linear and FM only (ValueError for the MLP and for n_factors > TRS_RETRIEVE_DMAX).  The model's parameters are
+        never written.  Under torch.distributed every rank answers from its own replica."""
+        self._check_fold_in("fold_in_users", epochs, lr, loss, l2, seed, max_tries, reject_seen)
+        opts = dict(epochs=int(epochs), lr=float(lr), loss=loss, l2=float(l2), seed=int(seed), shuffle=bool(shuffle),
+                    reject_seen=bool(reject_seen), max_tries=int(max_tries))
+        off, items, rank = self._history_csr(histories)
+        n = rank.size
+        if n == 0:
+            U, b = torch.empty((0, self.n_factors), dtype=torch.float32), torch.empty((0,), dtype=torch.float32)
+            return (U, b, torch.empty((opts['epochs'], 0), dtype=torch.float32)) if return_loss else (U, b)
+        _, _, U, b, ls = self._fold_in_dense(off, items, opts, return_loss)
+        r = torch.from_numpy(rank)
+        U, b = U.cpu()[r], b.cpu()[r]
+        return (U, b, ls.cpu()[:, r]) if return_loss else (U, b)
+
+    @_host_side
+    def recommend_for_histories(self, histories, top_k: int = 10, exclude_seen: bool = True,
+                                return_scores: bool = False, **fold_in_options):
+        """recommend() for users the model has never seen: fold_in_users(histories, **fold_in_options), then the fused
+        top-k of recommend() over the model's folded items with the folded-in rows as the user side.  Output as
+        recommend(): an (n, k) int64 CPU tensor of original item ids, k = min(top_k, n_items), with return_scores also
+        the (n, k) fp32 scores (FM: sigmoid(z), ranked by z); exclude_seen drops each history's own items; positions
+        beyond the candidates hold id -1 / score -inf; ties by ascending item row.
+        Only the fused kernel is offered: top_k > TRS_RETRIEVE_KMAX raises ValueError (the generic path of recommend()
+        for larger k is out of scope here), as do the MLP and n_factors > TRS_RETRIEVE_DMAX."""
+        unknown = set(fold_in_options) - {'epochs', 'lr', 'loss', 'l2', 'seed', 'shuffle', 'reject_seen', 'max_tries'}
+        if unknown:
+            raise ValueError(f"unknown fold-in options {sorted(unknown)}")
+        opts = dict(epochs=8, lr=0.05, loss='hinge', l2=0.0, seed=0, shuffle=True, reject_seen=True, max_tries=8)
+        opts.update(fold_in_options)
+        self._check_fold_in("recommend_for_histories", opts['epochs'], opts['lr'], opts['loss'], opts['l2'],
+                            opts['seed'], opts['max_tries'], opts['reject_seen'])
+        if int(top_k) > ops._lib.RETRIEVE_KMAX:
+            raise ValueError(f"recommend_for_histories takes top_k <= {ops._lib.RETRIEVE_KMAX} (TRS_RETRIEVE_KMAX), got "
+                             f"{top_k}")
+        opts = dict(epochs=int(opts['epochs']), lr=float(opts['lr']), loss=opts['loss'], l2=float(opts['l2']),
+                    seed=int(opts['seed']), shuffle=bool(opts['shuffle']), reject_seen=bool(opts['reject_seen']),
+                    max_tries=int(opts['max_tries']))
+        off, items, rank = self._history_csr(histories)
+        n = rank.size
+        k = min(int(top_k), self.n_items)
+        if k <= 0 or n == 0:
+            e = torch.empty((n, max(k, 0)), dtype=torch.int64)
+            return (e, torch.empty(e.shape, dtype=torch.float32)) if return_scores else e
+        fold, hist, U, b, _ = self._fold_in_dense(off, items, opts, False)
+        # a temporary table set whose user side is the folded-in rows: the fused kernel reads nothing else of it
+        T, keep = ops.make_tables(U, self.net.item.weight.data, b.view(-1, 1), self.net.table_params()[3].data)
+        users = torch.arange(n, dtype=torch.int64, device=U.device)
+        seen = hist if exclude_seen and hist[1].numel() else None  # every history empty: nothing to exclude
+        outs = [ops.retrieve_topk(self.net.NET, T, fold, users[s:s + self.RECOMMEND_CHUNK], k, seen)
+                for s in range(0, n, self.RECOMMEND_CHUNK)]
+        r = torch.from_numpy(rank)
+        ids = torch.cat([o[0] for o in outs]).cpu()[r]
+        scores = torch.cat([o[1] for o in outs]).cpu()[r]
+        idx = getattr(self.data_processor, "item_index", None)
+        if idx is not None:
+            good = ids >= 0
+            ids[good] = idx.cpu().to(torch.int64)[ids[good]]
+        return (ids, scores) if return_scores else ids
+
     # ------------------------------------------------------------------------------------------------ neighbours
     def _dense_rows(self, ids, index, n_rows, what):
         """Table rows of a list of caller ids of one side (`what`: 'user' | 'item'); IndexError on an unknown id."""

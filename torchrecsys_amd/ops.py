@@ -818,6 +818,31 @@ def neighbours_topk(fold, n_rows, D, queries, k):
     return ids, scores
 
 
+def fold_in_users(net, fold, n_items, D, hist, loss, epochs, lr, l2, seed, shuffle, reject_seen, max_tries,
+                  want_loss=False, err_flag=None):
+    """New user rows fitted to item histories against a frozen item fold (trs_fold_in_users; the update rule is in
+    include/trs.h "fold-in").  fold: an item_fold buffer of (n_items, D); hist: (offsets int64 (n+1,), items int32) GPU
+    CSR of sorted, distinct dense item rows.  Returns GPU tensors (U (n, D) fp32, b (n,) fp32, loss (epochs, n) fp32 or
+    None).  err_flag: optional int32 GPU tensor whose bit 0 is set by an item id outside the catalogue."""
+    lib = _lib.load()
+    off, items = hist
+    _dev(fold, "item fold", torch.uint8)
+    dev = fold.device
+    n = off.numel() - 1
+    if items.numel() == 0:  # every history empty: the kernel reads no item, but the CSR may not carry a NULL array
+        items = torch.zeros(1, dtype=torch.int32, device=dev)
+    cs = csr(off, items)
+    U = torch.empty((n, int(D)), dtype=torch.float32, device=dev)
+    b = torch.empty((n,), dtype=torch.float32, device=dev)
+    ls = torch.empty((int(epochs), n), dtype=torch.float32, device=dev) if want_loss else None
+    check(lib.trs_fold_in_users(NET_ID[net], ptr(fold), fold.numel(), int(n_items), int(D), C.byref(cs),
+                                _lib.LOSS_ID[loss], int(epochs), float(lr), float(l2),
+                                int(seed) & 0xFFFFFFFFFFFFFFFF, int(bool(shuffle)), int(bool(reject_seen)),
+                                int(max_tries), ptr(U), ptr(b), ptr(ls), ptr(_dev(err_flag, "err_flag", torch.int32)),
+                                _stream()), "trs_fold_in_users")
+    return U, b, ls
+
+
 def mask_seen(scores, users, seen):
     """Seen entries of score rows (n, n_items) fp32 -> -inf (trs_mask_seen), in place."""
     _dev(scores, "score rows", torch.float32)
