@@ -100,13 +100,13 @@ const char* trs_last_error(void);
  *      trs_mask_seen, trs_rank_metrics.  (Entry points added since without touching an existing signature or struct:
  *      the in-batch softmax group, trs_batch_prepare_mined, trs_batch_prepare_multi, trs_score_multi_fwd_bwd,
  *      trs_score_warp_fwd_bwd, TRS_LOSS_WARP, trs_stage_add_l2, trs_neighbour_fold, trs_neighbours_topk,
- *      trs_fold_in_users.) */
+ *      trs_fold_in_users, trs_item_ranks, trs_item_ranks_workspace_bytes.) */
 #define TRS_ABI_VERSION 6
 #define TRS_SYNC_WORDS 288
 #define TRS_SYNC_REBASE 0x40000000u /* arrivals after which trs_train_steps_sgd zeroes sync_dev and its host count */
 int trs_abi_version(void);
 /* Tuning / A-B knobs of the launch paths (kernel selection, launch shapes): GRID_CAP, PASS_GRID_CAP, K1_ITERS,
- * PASS_ITERS, PRESORT_GRID_CAP, PASS_NT, K1_NT, K1_WGS_PER_CU, GEMM32_NO_GLDS, GEMM16_TN_WIDE, GEMM16_TILE, GEMM16_NO_GLDS, BN_FINAL_TWO_SWEEPS, FOLDIN_DEPTH (meanings:
+ * PASS_ITERS, PRESORT_GRID_CAP, PASS_NT, K1_NT, K1_WGS_PER_CU, GEMM32_NO_GLDS, GEMM16_TN_WIDE, GEMM16_TILE, GEMM16_NO_GLDS, BN_FINAL_TWO_SWEEPS, FOLDIN_DEPTH, RANKS_STAGES (meanings:
  * csrc/trs_common.h TrsTuning).  The library reads TRS_<name> from the environment ONCE, at its first use; this entry
  * point changes a knob afterwards (tests, tools): unset != 0 restores the default.  The defaults are the measured best. */
 int trs_tuning_set(const char* name, int64_t value, int32_t unset);
@@ -696,6 +696,40 @@ int trs_fold_in_users(int net, const void* fold_dev, int64_t fold_bytes, int64_t
                       const trs_csr* hist, int32_t loss, int32_t epochs, float lr, float l2, uint64_t seed,
                       int32_t shuffle, int32_t reject_seen, int32_t max_tries, float* user_out_dev,
                       float* user_lin_out_dev, float* loss_out_dev, int32_t* err_flag_dev, void* stream);
+
+/* ------------------------------------------------- exact ranks (rank_items / evaluate_ranks) */
+/* Where given items land in a user's full ranking.  Added without touching an existing signature or struct.
+ *   v(u, i)    the fp32 value trs_retrieve_topk ranks by: the Linear score / the FM logit z = (acc + ucon_u) + c_i, acc the
+ *              fp32 FMA chain over the padded factors in that kernel's order (bit-identical: the target values are
+ *              computed by the same MFMA sequence over gathered rows).
+ *   key(u, i)  value descending, ties by ascending item id (the key of trs_topk / trs_retrieve_topk).
+ *   C_u        all n_items items; with `seen`, without the items of seen row u.
+ *   rank(u, t) = #{ i in C_u, i != t : key(u, i) > key(u, t) }, 0-based, int64.  t may itself be a seen item: its rank
+ *              is then its position among C_u + {t}.  A user's other targets compete like any other item.  For t in C_u
+ *              and k <= TRS_RETRIEVE_KMAX: trs_retrieve_topk(u, k, seen) returns t at position r  <=>  rank(u, t) == r.
+ * users (n_q) int64 dense query users; targets: CSR with n_rows == n_q, row q = the targets of query q (dense item ids,
+ * sorted, distinct; a user may be queried more than once).  seen (optional): indexed by dense user id, as in
+ * trs_retrieve_topk.  Outputs, one entry per target in CSR order (targets->off[n_q] entries): ranks_out int64;
+ * values_out (optional) fp32 v(u, t) in the scorer's output units as trs_retrieve_topk writes its scores (Linear: v,
+ * FM: sigmoid(v)).  A user outside the table gets rank -1 (value -inf) for all of its targets and is never used as an
+ * address; so does a target outside [0, n_items) (callers validate ids before the call).
+ * workspace: trs_item_ranks_workspace_bytes(n_q, targets->off[n_q]) bytes = 8 * (n_q + 1) + 8 per target.  The target
+ * count lives on the device: the call reads targets->off[n_q] back (8 bytes, one stream synchronisation) after the
+ * checks that need no device, then launches two kernels: the target keys, and the counting pass — the tile loop of
+ * trs_retrieve_topk over rows of (query, target) with `count += key > target key` as its epilogue, the item splits'
+ * partial counts added to ranks_out by 64-bit integer atomics (deterministic).  Knob RANKS_STAGES (timing only): 1 runs
+ * the key launch alone, 2 the counting launch alone on the keys a call before left in the same workspace (ranks_out is
+ * then added to, not reset), 3 (default) both.
+ * TRS_E_ARG, nothing launched: tables NULL or without a user table; net not TRS_NET_LINEAR / TRS_NET_FM; n_q < 0; D
+ * outside 1..TRS_RETRIEVE_DMAX; fold_dev NULL or fold_bytes < trs_item_fold_bytes; targets NULL, with a NULL array or
+ * with n_rows != n_q; a seen CSR with a NULL array; with n_q > 0 a NULL users / ranks_out or a workspace that is NULL or
+ * below trs_item_ranks_workspace_bytes(n_q, 0); after the read-back a workspace below the full size.  n_q == 0 or no
+ * target: TRS_OK, nothing launched. */
+int64_t trs_item_ranks_workspace_bytes(int64_t n_q, int64_t n_targets);
+int trs_item_ranks(int net, const trs_tables* tables, const void* fold_dev, int64_t fold_bytes,
+                   const int64_t* users_dev, int64_t n_q, const trs_csr* targets, const trs_csr* seen,
+                   int64_t* ranks_out_dev, float* values_out_dev, void* workspace_dev, int64_t workspace_bytes,
+                   void* stream);
 
 /* ------------------------------------------------------------------------------- in-batch softmax (fit) */
 /* Training loss of fit(loss='softmax') for the Linear / FM scorers (Yi et al., RecSys 2019).  Batch

@@ -40,6 +40,7 @@ const Knob KNOBS[] = {
     {"GEMM16_NO_GLDS", nullptr, &TrsTuning::gemm16_no_glds, 0},
     {"BN_FINAL_TWO_SWEEPS", nullptr, &TrsTuning::bn_final_two_sweeps, 0},
     {"FOLDIN_DEPTH", nullptr, &TrsTuning::foldin_depth, 4},
+    {"RANKS_STAGES", nullptr, &TrsTuning::ranks_stages, 3},
 };
 TrsTuning g_tuning;
 std::once_flag g_tuning_once;

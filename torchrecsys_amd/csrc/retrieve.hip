@@ -17,6 +17,10 @@
 //                       trs_neighbours_topk runs retrieve_topk_kernel<NQ, true> over it: the query rows are rows of
 //                       the buffer itself and each query's own row is the one excluded id (similar_items / _users).
 // rank_metrics_kernel   generic path: metrics of given top-k ids.
+// rank_values_kernel    exact ranks (rank_items / evaluate_ranks): key(u, t) of every (query, target) pair by the tile
+//                       loop's MFMA sequence over gathered rows (bit-identical values).
+// rank_count_kernel     retrieve_topk_kernel's tile loop over rows of (query, target) with `count += key > target key`
+//                       as its epilogue; the item splits add their counts to the ranks by 64-bit integer atomics.
 //
 // The MFMA is an exact fp32 FMA chain (gemm.hip:1-3); the dimension order of the dot product differs from the scoring
 // kernels', so on arbitrary weights the scores agree with predict() to rounding, and exactly where all products and
@@ -447,6 +451,245 @@ __global__ __launch_bounds__(TRS_BLOCK) void mask_seen_kernel(float* scores, int
   }
 }
 
+// ------------------------------------------------------------------------------------------------ exact ranks
+// rank(u, t) = #{ i in C_u, i != t : key(u, i) > key(u, t) } (include/trs.h "exact ranks").  A query row of the counting
+// kernel is (query q, up to RK_G of its targets); the rows of query q start at rstart[q] (RK_G == 1: the targets'
+// offsets themselves, row j = target j).  RK_G = 4 was built and does not fit: 64 counters per lane spill to scratch at
+// every D under __launch_bounds__(256, 2) (profiles/EXPERIMENTS.md).
+constexpr int RK_G = 1;
+constexpr uint64_t RK_NONE = ~(uint64_t)0;  // key of a padding slot or an invalid pair: no key is above it
+
+struct RankArgs {
+  const float* S;
+  const float* c;
+  const float* user;
+  const float* user_lin;
+  int64_t n_users, n_items, n_tiles, tiles_per_split;
+  int D, Dp, fm;
+  const int64_t* users;
+  int64_t n_q, n_t;
+  trs_csr targets;  // row q: the targets of query q
+  trs_csr seen;     // off == NULL: no masking
+  const int64_t* rstart;  // (n_q + 1) first row of each query
+  uint64_t* tkey;   // (n_t) key(u, t) of every pair
+  int64_t* ranks;   // (n_t)
+  float* values;    // (n_t) or NULL
+};
+
+// first q in [0, n) with a[q + 1] > x: the row of a CSR-like offset array that holds position x
+__device__ __forceinline__ int64_t rk_row_of(const int64_t* a, int64_t n, int64_t x) {
+  int64_t l = 0, r = n;
+  while (l < r) {
+    const int64_t m = (l + r) >> 1;
+    if (a[m + 1] <= x) l = m + 1; else r = m;
+  }
+  return l;
+}
+
+// key(u, t) of 32 pairs per wave by the MFMA sequence of retrieve_topk_kernel: row `col` of the A block is the pair's
+// user, column `col` of the B block the pair's target, and the diagonal of the 32 x 32 product holds <U_u, S_t> in the
+// very order the tile loop accumulates it — the value is bit-identical to the one the counting kernel compares with.
+// Also sets ranks[j] to 0 (-1 for a user outside the table or a target outside the catalogue).
+__global__ __launch_bounds__(TRS_BLOCK) void rank_values_kernel(const RankArgs a) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, col = lane & 31, h = lane >> 5;
+  const int64_t j = ((int64_t)blockIdx.x * RT_WAVES + w) * 32 + col;
+  bool ok = false;
+  int64_t u = 0, t = 0;
+  if (j < a.n_t) {
+    const int64_t q = rk_row_of(a.targets.off, a.n_q, j);
+    if (q < a.n_q) {
+      const int64_t uu = a.users[q], tt = a.targets.items[j];
+      ok = (uint64_t)uu < (uint64_t)a.n_users && (uint64_t)tt < (uint64_t)a.n_items;
+      if (ok) {
+        u = uu;
+        t = tt;
+      }
+    }
+  }
+  const float* urow = a.user + u * (int64_t)a.D;
+  const float* sb = a.S + t * (int64_t)a.Dp + 4 * h;
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  for (int qq = 0; qq < a.Dp / 8; ++qq) {  // uniform trip count: every lane takes part in every MFMA
+    float av[4];
+#pragma unroll
+    for (int cc = 0; cc < 4; ++cc) {
+      const int d = 8 * qq + 4 * h + cc;
+      av[cc] = (ok && d < a.D) ? urow[d] : 0.f;
+    }
+    const float4 b = *reinterpret_cast<const float4*>(sb + 8 * qq);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0], b.x, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1], b.y, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[2], b.z, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[3], b.w, acc, 0, 0, 0);
+  }
+  // accumulator row (r & 3) + 8 * (r >> 2) + 4 * h == col sits in the half h = (col >> 2) & 1 at r = (col & 3) + 4 * (col >> 3)
+  if (j < a.n_t && h == ((col >> 2) & 1)) {
+    const int rr = (col & 3) + 4 * (col >> 3);
+    float dot = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      if (r == rr) dot = acc[r];
+    const float v = (dot + a.user_lin[u]) + a.c[t];
+    a.tkey[j] = ok ? trs_topk_key(v, (uint32_t)t) : RK_NONE;
+    a.ranks[j] = ok ? 0 : -1;
+    if (a.values) a.values[j] = ok ? (a.fm ? trs::sigmoidf_(v) : v) : -INFINITY;
+  }
+}
+
+// One workgroup = 32 query rows x one split of the item tiles: grid, A operand, B operand, seen-bit walk and the
+// in_range handling of retrieve_topk_kernel; the epilogue counts the keys above each of the row's target keys
+// (read from LDS: the lanes of a half wave share a row, so the read is a broadcast) in int32 registers.  No candidate
+// buffer and no LDS atomic in the tile loop.  After the last tile the counters are summed over the 32 columns and the
+// 4 waves, and each split adds its part to ranks[] with one 64-bit integer atomic per (row, target).
+template <int NQ, int G>  // Dp = 8 * NQ
+__global__ __launch_bounds__(TRS_BLOCK, 2) void rank_count_kernel(const RankArgs a) {
+  constexpr int Dp = 8 * NQ;
+  __shared__ uint64_t tk[RT_UT * G];
+  __shared__ int64_t row_u[RT_UT];  // the row's dense user; -1: no such row, or a user outside the table
+  __shared__ int64_t row_s[RT_UT];  // its first target's position in targets.items / ranks
+  __shared__ int row_n[RT_UT];      // its targets (0 .. G)
+  __shared__ float row_c[RT_UT];    // its user constant
+  __shared__ uint32_t seenb[RT_UT * RT_WAVES];
+  __shared__ int64_t seen_p[RT_UT], seen_e[RT_UT];
+  __shared__ int part[RT_WAVES][RT_UT * G];
+
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, col = lane & 31, h = lane >> 5;
+  const int64_t n_rows = a.rstart[a.n_q];
+  const int64_t r0 = (int64_t)blockIdx.x * RT_UT;
+  if (r0 >= n_rows) return;  // (G == 1: never; a grid sized by a bound on the rows would end here)
+  const int64_t t0 = (int64_t)blockIdx.y * a.tiles_per_split;
+  const int64_t t1 = t0 + a.tiles_per_split < a.n_tiles ? t0 + a.tiles_per_split : a.n_tiles;
+
+  for (int i = tid; i < RT_UT * RT_WAVES; i += TRS_BLOCK) seenb[i] = 0;
+  if (tid < RT_UT) {
+    const int64_t row = r0 + tid;
+    int64_t u = -1, s0 = 0, lo = 0, hi = 0;
+    int n = 0;
+    if (row < n_rows) {
+      const int64_t q = rk_row_of(a.rstart, a.n_q, row);
+      if (q < a.n_q) {
+        const int64_t uu = a.users[q];
+        if ((uint64_t)uu < (uint64_t)a.n_users) {
+          u = uu;
+          s0 = a.targets.off[q] + (row - a.rstart[q]) * G;
+          const int64_t left = a.targets.off[q + 1] - s0;
+          n = left < G ? (left > 0 ? (int)left : 0) : G;
+          if (s0 < 0 || s0 + n > a.n_t) n = 0;  // (offsets that do not ascend: nothing is read or written)
+        }
+      }
+    }
+    for (int g = 0; g < G; ++g) tk[tid * G + g] = g < n ? a.tkey[s0 + g] : RK_NONE;
+    if (u >= 0 && a.seen.off && (uint64_t)u < (uint64_t)a.seen.n_rows) {
+      lo = a.seen.off[u];
+      hi = a.seen.off[u + 1];
+      int64_t l = lo, r = hi;  // first seen item >= the split's first item
+      const int64_t first = t0 * RT_TN;
+      while (l < r) {
+        const int64_t m = (l + r) >> 1;
+        if (a.seen.items[m] < first) l = m + 1; else r = m;
+      }
+      lo = l;
+    }
+    row_u[tid] = u;
+    row_c[tid] = u >= 0 ? a.user_lin[u] : 0.f;
+    row_s[tid] = s0;
+    row_n[tid] = n;
+    seen_p[tid] = lo;
+    seen_e[tid] = hi;
+  }
+  __syncthreads();
+
+  // A operand: lane holds U[col][8*qq + 4*h + cc], as in retrieve_topk_kernel
+  float av[NQ][4];
+  {
+    const int64_t u = row_u[col];
+    const bool ok = u >= 0;
+    const float* row = a.user + (ok ? u : 0) * (int64_t)a.D;
+#pragma unroll
+    for (int qq = 0; qq < NQ; ++qq)
+#pragma unroll
+      for (int cc = 0; cc < 4; ++cc) {
+        const int d = 8 * qq + 4 * h + cc;
+        av[qq][cc] = (ok && d < a.D) ? row[d] : 0.f;
+      }
+  }
+  // The user constants stay in LDS beside the target keys (16 more registers do not fit next to av[32][4] and the
+  // counters at D = 256).  A row without a live user holds RK_NONE keys, so it needs no `live` bit: nothing is counted.
+  int cnt[16][G];
+#pragma unroll
+  for (int r = 0; r < 16; ++r)
+#pragma unroll
+    for (int g = 0; g < G; ++g) cnt[r][g] = 0;
+
+  for (int64_t t = t0; t < t1; ++t) {
+    const int64_t base = t * RT_TN;
+    if (a.seen.off) {
+      __syncthreads();  // the previous tile's reads of seenb are done
+      if (tid < RT_UT) {
+        uint32_t* wb = seenb + tid * RT_WAVES;
+#pragma unroll
+        for (int j = 0; j < RT_WAVES; ++j) wb[j] = 0;
+        int64_t p = seen_p[tid];
+        const int64_t e = seen_e[tid];
+        while (p < e) {
+          const int64_t it = (int64_t)a.seen.items[p];
+          if (it >= base + RT_TN) break;
+          if (it >= base) wb[(it - base) >> 5] |= 1u << ((it - base) & 31);
+          ++p;
+        }
+        seen_p[tid] = p;
+      }
+      __syncthreads();
+    }
+
+    const int64_t item = base + w * 32 + col;
+    const float* sb = a.S + item * Dp + 4 * h;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+    for (int qq = 0; qq < NQ; ++qq) {
+      const float4 b = *reinterpret_cast<const float4*>(sb + 8 * qq);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[qq][0], b.x, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[qq][1], b.y, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[qq][2], b.z, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[qq][3], b.w, acc, 0, 0, 0);
+    }
+    const float ci = a.c[item];
+    const bool in_range = item < a.n_items;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int ur = (r & 3) + 8 * (r >> 2) + 4 * h;
+      const bool seen = (seenb[ur * RT_WAVES + w] >> col) & 1u;
+      const float s = (acc[r] + row_c[ur]) + ci;
+      const uint64_t key = (in_range && !seen) ? trs_topk_key(s, (uint32_t)item) : 0;
+#pragma unroll
+      for (int g = 0; g < G; ++g) cnt[r][g] += key > tk[ur * G + g] ? 1 : 0;
+    }
+  }
+
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int ur = (r & 3) + 8 * (r >> 2) + 4 * h;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      const int c = trs_group_sum_i<32>(cnt[r][g]);  // over the 32 columns of this half wave
+      if (col == 0) part[w][ur * G + g] = c;
+    }
+  }
+  __syncthreads();
+  if (tid < RT_UT * G) {
+    const int row = tid / G, g = tid % G;
+    int64_t total = 0;
+#pragma unroll
+    for (int j = 0; j < RT_WAVES; ++j) total += part[j][tid];
+    if (g < row_n[row] && total > 0 && tk[tid] != RK_NONE)
+      atomicAdd(reinterpret_cast<unsigned long long*>(a.ranks + row_s[row] + g), (unsigned long long)total);
+  }
+}
+
 static int check_csr(const trs_csr* c, const char* who, const char* what) {
   TRS_REQUIRE(c->off && c->items && c->n_rows >= 0, "%s: %s CSR has NULL arrays", who, what);
   return TRS_OK;
@@ -482,17 +725,24 @@ static int run_retrieve(const char* who, RetrieveArgs& a, int Dp, int64_t splits
   return TRS_OK;
 }
 
+// What every launcher over a folded buffer checks: the query count and the buffer.
+static int rt_check_fold(const char* who, int64_t n_items, int D, int64_t n_q, const void* fold_dev,
+                         int64_t fold_bytes) {
+  TRS_REQUIRE(n_q >= 0, "%s: negative n_q", who);
+  const int64_t fneed = trs_item_fold_bytes(n_items, D);
+  TRS_REQUIRE(fneed > 0, "%s: D=%d outside 1..%d", who, D, TRS_RETRIEVE_DMAX);
+  TRS_REQUIRE(fold_dev && fold_bytes >= fneed, "%s: fold buffer too small (%lld < %lld)", who, (long long)fold_bytes,
+              (long long)fneed);
+  return TRS_OK;
+}
+
 // What trs_retrieve_topk and trs_neighbours_topk check alike: k, the query count, the folded buffer, the workspace.
 static int rt_check_topk(const char* who, int64_t n_items, int D, int k, int64_t n_q, const void* fold_dev,
                          int64_t fold_bytes, const void* workspace_dev, int64_t workspace_bytes) {
   TRS_REQUIRE(k >= 1 && k <= TRS_RETRIEVE_KMAX, "%s: k=%d outside 1..%d (larger k: score rows + trs_topk)", who, k,
               TRS_RETRIEVE_KMAX);
   TRS_REQUIRE(k <= n_items, "%s: k=%d > n_items=%lld", who, k, (long long)n_items);
-  TRS_REQUIRE(n_q >= 0, "%s: negative n_q", who);
-  const int64_t fneed = trs_item_fold_bytes(n_items, D);
-  TRS_REQUIRE(fneed > 0, "%s: D=%d outside 1..%d", who, D, TRS_RETRIEVE_DMAX);
-  TRS_REQUIRE(fold_dev && fold_bytes >= fneed, "%s: fold buffer too small (%lld < %lld)", who, (long long)fold_bytes,
-              (long long)fneed);
+  TRS_TRY(rt_check_fold(who, n_items, D, n_q, fold_dev, fold_bytes));
   TRS_REQUIRE(workspace_bytes >= trs_retrieve_workspace_bytes(n_q, k) && (workspace_dev || n_q == 0),
               "%s: workspace too small (%lld < %lld)", who, (long long)workspace_bytes,
               (long long)trs_retrieve_workspace_bytes(n_q, k));
@@ -654,5 +904,101 @@ extern "C" int trs_rank_metrics(const int64_t* ids_dev, int64_t n_q, int32_t k, 
   hipLaunchKernelGGL(rank_metrics_kernel, dim3(trs_grid(n_q, TRS_BLOCK)), dim3(TRS_BLOCK), 0, (hipStream_t)stream,
                      ids_dev, n_q, (int)k, users_dev, *rel, metrics_out_dev);
   TRS_CHECK_LAUNCH("rank_metrics_kernel");
+  return TRS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ exact ranks (host)
+namespace {
+
+static_assert(RK_G == 1, "RK_G > 1 needs the row starts sum_q ceil(m_q / RK_G) in the workspace (a scan over the queries)");
+static_assert(RT_UT * RK_G <= TRS_BLOCK, "one thread per (row, target) in the final reduction");
+
+template <int NQ>
+static void launch_rank_count(const RankArgs& a, dim3 grid, hipStream_t s) {
+  hipLaunchKernelGGL((rank_count_kernel<NQ, RK_G>), grid, dim3(TRS_BLOCK), 0, s, a);
+}
+
+}  // namespace
+
+extern "C" int64_t trs_item_ranks_workspace_bytes(int64_t n_q, int64_t n_targets) {
+  if (n_q <= 0 || n_targets < 0) return 0;
+  return (n_q + 1 + n_targets) * 8;  // a row start per query (+ 1), then a key per target
+}
+
+extern "C" int trs_item_ranks(int net, const trs_tables* T, const void* fold_dev, int64_t fold_bytes,
+                              const int64_t* users_dev, int64_t n_q, const trs_csr* targets, const trs_csr* seen,
+                              int64_t* ranks_out_dev, float* values_out_dev, void* workspace_dev,
+                              int64_t workspace_bytes, void* stream) {
+  const char* who = "trs_item_ranks";
+  hipStream_t s = (hipStream_t)stream;
+  TRS_REQUIRE(T != nullptr, "%s: tables is NULL", who);
+  TRS_REQUIRE(net == TRS_NET_LINEAR || net == TRS_NET_FM, "%s: net must be TRS_NET_LINEAR or TRS_NET_FM", who);
+  TRS_REQUIRE(T->user && T->user_lin && T->n_users > 0 && T->n_items > 0, "%s: user table is NULL/empty", who);
+  TRS_TRY(rt_check_fold(who, T->n_items, T->D, n_q, fold_dev, fold_bytes));
+  TRS_REQUIRE(targets != nullptr, "%s: targets CSR is NULL", who);
+  TRS_TRY(check_csr(targets, who, "targets"));
+  TRS_REQUIRE(targets->n_rows == n_q, "%s: targets has %lld rows for n_q=%lld queries", who,
+              (long long)targets->n_rows, (long long)n_q);
+  if (seen) TRS_TRY(check_csr(seen, who, "seen"));
+  const int stages = trs_tuning().ranks_stages;
+  TRS_REQUIRE(stages >= 1 && stages <= 3, "%s: RANKS_STAGES=%d outside 1..3", who, stages);
+  if (n_q == 0) return TRS_OK;
+  TRS_REQUIRE(users_dev && ranks_out_dev, "%s: users/ranks_out is NULL", who);
+  TRS_REQUIRE(workspace_dev && workspace_bytes >= trs_item_ranks_workspace_bytes(n_q, 0),
+              "%s: workspace too small (%lld < %lld before the targets)", who, (long long)workspace_bytes,
+              (long long)trs_item_ranks_workspace_bytes(n_q, 0));
+  // the number of pairs lives on the device: one 8-byte read-back, the only synchronisation of the call
+  int64_t n_t = 0;
+  if (hipMemcpyAsync(&n_t, targets->off + n_q, sizeof(n_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess) {
+    trs_set_error("%s: reading targets->off[n_q] failed: %s", who, hipGetErrorString(hipGetLastError()));
+    return TRS_E_LAUNCH;
+  }
+  TRS_REQUIRE(n_t >= 0, "%s: targets->off[n_q]=%lld < 0", who, (long long)n_t);
+  if (n_t == 0) return TRS_OK;
+  TRS_REQUIRE(workspace_bytes >= trs_item_ranks_workspace_bytes(n_q, n_t), "%s: workspace too small (%lld < %lld)", who,
+              (long long)workspace_bytes, (long long)trs_item_ranks_workspace_bytes(n_q, n_t));
+  const int Dp = rt_dp(T->D);
+  const int64_t n_pad = rt_items_pad(T->n_items);
+  RankArgs a = {};
+  a.S = (const float*)fold_dev;
+  a.c = a.S + n_pad * Dp;
+  a.user = T->user;
+  a.user_lin = T->user_lin;
+  a.n_users = T->n_users;
+  a.n_items = T->n_items;
+  a.n_tiles = n_pad / RT_TN;
+  a.D = T->D;
+  a.Dp = Dp;
+  a.fm = net == TRS_NET_FM;
+  a.users = users_dev;
+  a.n_q = n_q;
+  a.n_t = n_t;
+  a.targets = *targets;
+  if (seen) a.seen = *seen;
+  a.tkey = (uint64_t*)workspace_dev + (n_q + 1);
+  a.ranks = ranks_out_dev;
+  a.values = values_out_dev;
+  a.rstart = targets->off;  // RK_G == 1: row j is target j
+  const int64_t vgrid = (n_t + RT_TN - 1) / RT_TN, row_tiles = rt_user_tiles(n_t);
+  TRS_REQUIRE(vgrid < ((int64_t)1 << 31), "%s: too many targets in one call", who);
+  if (stages & 1) {
+    hipLaunchKernelGGL(rank_values_kernel, dim3((unsigned)vgrid), dim3(TRS_BLOCK), 0, s, a);
+    TRS_CHECK_LAUNCH("rank_values_kernel");
+  }
+  if (!(stages & 2)) return TRS_OK;
+  int64_t splits = (RT_SPLIT_TARGET + row_tiles - 1) / row_tiles;
+  if (splits > a.n_tiles) splits = a.n_tiles;
+  a.tiles_per_split = (a.n_tiles + splits - 1) / splits;
+  const int64_t used = (a.n_tiles + a.tiles_per_split - 1) / a.tiles_per_split;  // splits that own at least one tile
+  const dim3 grid((unsigned)row_tiles, (unsigned)used);
+  switch (Dp) {
+    case 16: launch_rank_count<2>(a, grid, s); break;
+    case 32: launch_rank_count<4>(a, grid, s); break;
+    case 64: launch_rank_count<8>(a, grid, s); break;
+    case 128: launch_rank_count<16>(a, grid, s); break;
+    default: launch_rank_count<32>(a, grid, s); break;
+  }
+  TRS_CHECK_LAUNCH("rank_count_kernel");
   return TRS_OK;
 }

@@ -57,6 +57,7 @@ struct TrsTuning {
   int gemm16_no_glds;     // TRS_GEMM16_NO_GLDS  1: bf16 NT GEMMs on the register-staged 256 x 256 kernel
   int bn_final_two_sweeps;  // TRS_BN_FINAL_TWO_SWEEPS  1: the two-sweep finalise kernels
   int foldin_depth;       // TRS_FOLDIN_DEPTH    visits whose rows trs_fold_in_users keeps requested: 1 | 2 | 4 | 8 (4)
+  int ranks_stages;       // TRS_RANKS_STAGES    launches of trs_item_ranks, for timing one alone: bit 0 keys, bit 1 counting (3)
 };
 TrsTuning& trs_tuning();
 

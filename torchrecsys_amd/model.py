@@ -29,6 +29,7 @@ from .collaborative.fm import FM
 from .collaborative.linear import Linear
 from .dataset.dataset import FastDataLoader, ProcessData, sample_negatives_reference_stream
 from .engine import SparseScorerTrainer
+from .evaluate import ranks as rank_eval
 from .evaluate.metrics import Metrics
 from .helper.cuda import gpu, host_threads
 from .helper.loss import hinge_loss  # noqa: F401  (part of the reference's module surface)
@@ -795,6 +796,32 @@ class TorchRecSys(torch.nn.Module):
         return hasattr(self.net, 'table_params') and k <= ops._lib.RETRIEVE_KMAX and \
             self.n_factors <= ops._lib.RETRIEVE_DMAX
 
+    def _generic_form(self, dev, meta):
+        """What the generic path's score rows rank by: (S, c, table parameters) of the folded form for Linear / FM up to
+        TRS_RETRIEVE_DMAX factors; None (the scorer's own score_all_items rows) for the MLP and wider tables."""
+        if not hasattr(self.net, 'table_params'):
+            return None
+        fold = ops.item_fold(self.net.NET, self.net.tables(), self.n_items, self.n_factors, dev, meta)
+        if fold is None:
+            return None
+        S, c = ops.fold_views(fold, self.n_items, self.n_factors)
+        return S, c, self.net.table_params()
+
+    def _generic_rows(self, us, meta, form):
+        """Score rows of the dense users `us` (a GENERIC_CHUNK of them): (rows ranked by, rows in output units)."""
+        dev = us.device
+        if form is None:
+            rows = torch.stack([self.net.score_all_items(int(u), meta) for u in us.tolist()])
+            return rows, rows
+        S, c, tp = form
+        Ut = torch.zeros((us.numel(), S.shape[1]), dtype=torch.float32, device=dev)
+        Ut[:, :self.n_factors] = tp[0].data[us]
+        Tz, keep = ops.make_tables(Ut, S, tp[2].data[us].contiguous(), c.view(-1, 1))
+        rows = torch.stack([ops.score_all_items("linear", Tz, r, self.n_items, dev) for r in range(us.numel())])
+        out_rows = rows if self.net.NET == "linear" else \
+            torch.stack([self.net.score_all_items(int(u), meta) for u in us.tolist()])
+        return rows, out_rows
+
     def _rank_dense(self, users, k, exclude_seen, rel=None):
         """Top-k of dense users (int64 GPU tensor): (ids (n,k) dense int64 with -1 padding, scores (n,k) fp32, metrics
         (n,4) float64 or None).  Linear / FM with k <= KMAX: the fused kernel; otherwise score rows + mask + top-k."""
@@ -817,25 +844,10 @@ class TorchRecSys(torch.nn.Module):
         ids = torch.empty((n, k), dtype=torch.int64, device=dev)
         scores = torch.empty((n, k), dtype=torch.float32, device=dev)
         ar = torch.arange(k, device=dev)
-        fold = None
-        if hasattr(self.net, 'table_params'):
-            fold = ops.item_fold(self.net.NET, self.net.tables(), self.n_items, self.n_factors, dev, meta)
-        if fold is not None:
-            S, c = ops.fold_views(fold, self.n_items, self.n_factors)
-            tp = self.net.table_params()
+        form = self._generic_form(dev, meta)
         for s in range(0, n, self.GENERIC_CHUNK):
             us = users[s:s + self.GENERIC_CHUNK]
-            if fold is None:
-                rows = torch.stack([self.net.score_all_items(int(u), meta) for u in us.tolist()])
-                out_rows = rows
-            else:
-                Ut = torch.zeros((us.numel(), S.shape[1]), dtype=torch.float32, device=dev)
-                Ut[:, :self.n_factors] = tp[0].data[us]
-                Tz, keep = ops.make_tables(Ut, S, tp[2].data[us].contiguous(), c.view(-1, 1))
-                rows = torch.stack([ops.score_all_items("linear", Tz, r, self.n_items, dev)
-                                    for r in range(us.numel())])
-                out_rows = rows if self.net.NET == "linear" else \
-                    torch.stack([self.net.score_all_items(int(u), meta) for u in us.tolist()])
+            rows, out_rows = self._generic_rows(us, meta, form)
             if seen is not None:
                 ops.mask_seen(rows, us, seen)
                 n_seen = (seen[0][us + 1] - seen[0][us])
@@ -874,6 +886,152 @@ class TorchRecSys(torch.nn.Module):
             keep = ids >= 0
             ids[keep] = idx.cpu().to(torch.int64)[ids[keep]]
         return (ids, scores.cpu()) if return_scores else ids
+
+    # ------------------------------------------------------------------------------------------------ exact ranks
+    RANK_TARGET_BLOCK = 1024  # targets per compare block of the generic path: (block, n_items) booleans
+
+    @staticmethod
+    def _group_pairs(du, di, n_items):
+        """Distinct (dense user, dense item) pairs sorted by (user, item), as a query list with a query-indexed CSR:
+        (query users (n_q,), offsets (n_q + 1,), items (n_t,), inverse (n,)), all int64 — input pair j is CSR entry
+        inverse[j], so duplicate pairs share one entry."""
+        uniq, inv = torch.unique(du * int(n_items) + di, return_inverse=True)
+        pu = torch.div(uniq, int(n_items), rounding_mode="floor")
+        qusers, counts = torch.unique_consecutive(pu, return_counts=True)
+        off = torch.zeros(qusers.numel() + 1, dtype=torch.int64)
+        off[1:] = torch.cumsum(counts, 0)
+        return qusers, off, uniq - pu * int(n_items), inv
+
+    def _ranks_dense(self, qusers, off, items, exclude_seen, want_values=False):
+        """Exact ranks of a query-indexed CSR of dense targets (int64 tensors: query users (n_q,), offsets (n_q + 1,),
+        sorted distinct items per row): (ranks (n_t,) int64 CPU, values (n_t,) fp32 CPU in output units or None).
+        Linear / FM up to TRS_RETRIEVE_DMAX factors: trs_item_ranks per RECOMMEND_CHUNK of queries; otherwise the
+        generic path's score rows, the targets' values read before the seen entries become -inf, and a count of
+        (row > v_t) | ((row == v_t) & (id < t)) per target."""
+        dev = _device()
+        seen = self._seen_csr() if exclude_seen else None
+        meta = self._item_meta_dev()
+        off = off.cpu()
+        nq = qusers.numel()
+        ranks = torch.empty(items.numel(), dtype=torch.int64, device=dev)
+        values = torch.empty(items.numel(), dtype=torch.float32, device=dev) if want_values else None
+        qusers, items = qusers.to(dev), items.to(dev)
+        if hasattr(self.net, 'table_params') and self.n_factors <= ops._lib.RETRIEVE_DMAX:
+            T = self.net.tables()
+            fold = ops.item_fold(self.net.NET, T, self.n_items, self.n_factors, dev, meta)
+            for s in range(0, nq, self.RECOMMEND_CHUNK):
+                e = min(s + self.RECOMMEND_CHUNK, nq)
+                lo, hi = int(off[s]), int(off[e])
+                r, v = ops.item_ranks(self.net.NET, T, fold, qusers[s:e].contiguous(),
+                                      ((off[s:e + 1] - lo).to(dev), items[lo:hi].to(torch.int32).contiguous()), seen,
+                                      want_values)
+                ranks[lo:hi] = r
+                if want_values:
+                    values[lo:hi] = v
+            return ranks.cpu(), values.cpu() if want_values else None
+        form = self._generic_form(dev, meta)
+        ar = torch.arange(self.n_items, device=dev)
+        for s in range(0, nq, self.GENERIC_CHUNK):
+            us = qusers[s:s + self.GENERIC_CHUNK]
+            rows, out_rows = self._generic_rows(us, meta, form)
+            segs = [(int(off[s + r]), int(off[s + r + 1])) for r in range(us.numel())]
+            vts = [rows[r, items[lo:hi]] for r, (lo, hi) in enumerate(segs)]  # before masking: a target may be seen
+            if want_values:
+                for r, (lo, hi) in enumerate(segs):
+                    values[lo:hi] = out_rows[r, items[lo:hi]]
+            if seen is not None:
+                ops.mask_seen(rows, us, seen)
+            for r, (lo, hi) in enumerate(segs):
+                for b in range(lo, hi, self.RANK_TARGET_BLOCK):
+                    t = items[b:min(b + self.RANK_TARGET_BLOCK, hi)]
+                    vt = vts[r][b - lo:b - lo + t.numel()][:, None]
+                    row = rows[r][None, :]
+                    ranks[b:b + t.numel()] = ((row > vt) | ((row == vt) & (ar[None, :] < t[:, None]))).sum(1)
+        return ranks.cpu(), values.cpu() if want_values else None
+
+    @_host_side
+    def rank_items(self, user_ids, item_ids, exclude_seen: bool = True, return_scores: bool = False):
+        """Where item_ids[j] lands in the full ranking of user_ids[j]: an (n,) int64 CPU tensor of 0-based ranks in
+        input order; with return_scores also the (n,) fp32 values in the scorer's output units (as recommend()).
+        rank = the number of candidate items other than the target that recommend() orders before it: value descending
+        (Linear score, FM logit z), ties by ascending item id.  Candidates are all items, with exclude_seen without the
+        user's train items; a target that is itself a train item is ranked as if it were a candidate, and the user's
+        other targets compete like any other item.  For a candidate target and top_k <= TRS_RETRIEVE_KMAX,
+        recommend(u, top_k, exclude_seen)[r] == t exactly when rank_items([u], [t], exclude_seen) == r: the kernel computes
+        the target's value with the instruction sequence recommend()'s tile loop uses.
+        Unequal lengths raise ValueError, an unknown user or item IndexError; duplicate pairs get the same answer.
+        Linear and FM up to TRS_RETRIEVE_DMAX factors run one more pass of recommend()'s matrix-core tile loop whose
+        epilogue counts the items above each target; the MLP and wider tables count over score rows one user at a time."""
+        self.net = self.net.eval()
+        ulist = user_ids.tolist() if hasattr(user_ids, "tolist") else list(user_ids)
+        ilist = item_ids.tolist() if hasattr(item_ids, "tolist") else list(item_ids)
+        if len(ulist) != len(ilist):
+            raise ValueError(f"rank_items takes as many item ids as user ids, got {len(ulist)} and {len(ilist)}")
+        if not ulist:
+            e = torch.empty(0, dtype=torch.int64)
+            return (e, torch.empty(0, dtype=torch.float32)) if return_scores else e
+        du = self._dense_users(ulist)
+        di = self._dense_rows(ilist, getattr(self.data_processor, "item_index", None), self.n_items, 'item')
+        qusers, off, items, inv = self._group_pairs(du, di, self.n_items)
+        ranks, values = self._ranks_dense(qusers, off, items, exclude_seen, return_scores)
+        return (ranks[inv], values[inv]) if return_scores else ranks[inv]
+
+    @_host_side
+    def evaluate_ranks(self, k=(1, 10, 100), metrics=('auc', 'mrr', 'precision', 'recall', 'ndcg', 'map'),
+                       exclude_seen: bool = True, users=None):
+        """Rank-aware metrics over the full catalogue against the test split, from the exact rank of every (user,
+        held-out item) pair (rank_items); returns {'auc': .., 'mrr': .., 'precision@10': .., .., 'n_users': int} and
+        prints the entries as evaluate_ranking() does.
+        Users, T_u (the user's distinct test items, without its train items when exclude_seen) and the candidates C_u are
+        those of evaluate_ranking(); users with an empty T_u, or whose candidates are all relevant, are skipped.
+        metrics: 'auc', 'mrr', 'mean_rank' and, for every k (an int or a sequence of ints >= 1, no upper limit; k >
+        n_items behaves as n_items), 'hit_rate', 'precision', 'recall', 'ndcg', 'map' — the formulas are in
+        evaluate/ranks.py.  Per-user values in float64, averaged over the evaluated users in ascending user order.
+        Data parallel: as evaluate_ranking() (users with user_id % world == rank, sums all-reduced)."""
+        ks = [int(k)] if isinstance(k, (int, np.integer)) else [int(x) for x in k]
+        metrics = [metrics] if isinstance(metrics, str) else list(metrics)
+        rank_eval.check(metrics, ks)
+        rank, world = tdist.world_info()
+        if world > 1 and (getattr(self, 'pre_sharded', False) or self.dp_partition != 'user'):
+            raise ValueError("evaluate_ranks under data parallelism needs dp_partition='user' without pre_sharded: "
+                             "a rank must hold every train and test row of the users it evaluates")
+        self.net = self.net.eval()
+        dev = _device()
+        roff, ritems = self._relevance_csr(exclude_seen)
+        if users is None:
+            dense = torch.unique(self.data_processor.test_data['user_id'].to(torch.int64))
+        else:
+            dense = torch.unique(self._dense_users(users))
+        if world > 1:
+            dense = dense[dense % world == rank]
+        dense = dense.to(dev)
+        cnt = roff[dense + 1] - roff[dense]
+        dense, cnt = dense[cnt > 0], cnt[cnt > 0]
+        names = rank_eval.entries(metrics, ks)
+        sums = np.zeros(len(names) + 1)
+        if dense.numel():
+            n_c = torch.full_like(cnt, self.n_items)
+            if exclude_seen:
+                soff = self._seen_csr()[0]
+                n_c -= soff[dense + 1] - soff[dense]
+            off = torch.zeros(dense.numel() + 1, dtype=torch.int64, device=dev)
+            off[1:] = torch.cumsum(cnt, 0)
+            within = torch.arange(int(off[-1]), device=dev) - torch.repeat_interleave(off[:-1], cnt)
+            items = ritems[torch.repeat_interleave(roff[dense], cnt) + within].to(torch.int64)
+            ranks, _ = self._ranks_dense(dense, off, items, exclude_seen)
+            keep, per = rank_eval.per_user(ranks.numpy(), off.cpu().numpy(), n_c.cpu().numpy(), ks, metrics,
+                                           self.n_items)
+            sums = np.array([float(np.sum(per[name])) for name in names] + [float(keep.sum())])
+        if world > 1:
+            sums = np.array(tdist.allreduce_scalar_sum(sums.tolist(), dev))
+        n = int(sums[-1])
+        results = {}
+        for j, name in enumerate(names):
+            value = float(sums[j] / n) if n else 0.0
+            results[name] = value
+            print(f'|--- Testing {name}: {value:.4f}')
+        results['n_users'] = n
+        return results
 
     # ------------------------------------------------------------------------------------------------ fold-in
     def _check_fold_in(self, what, epochs, lr, loss, l2, seed, max_tries, reject_seen):

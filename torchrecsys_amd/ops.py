@@ -843,6 +843,31 @@ def fold_in_users(net, fold, n_items, D, hist, loss, epochs, lr, l2, seed, shuff
     return U, b, ls
 
 
+def item_ranks(net, T, fold, users, targets_csr, seen=None, want_values=False):
+    """Exact ranks of each query's target items over the catalogue (trs_item_ranks; the definition is in
+    include/trs.h "exact ranks").  users: dense int64 GPU tensor; targets_csr: (offsets int64 (n + 1,), items int32) GPU
+    CSR, row q = the sorted, distinct dense targets of users[q]; seen: (offsets, items) CSR or None.  Returns (ranks int64
+    (n_targets,), values fp32 (n_targets,) in the scorer's output units or None), in CSR order."""
+    lib = _lib.load()
+    _dev(users, "query users", torch.int64)
+    off, items = targets_csr
+    n, dev = users.numel(), users.device
+    if off.numel() != n + 1:
+        raise ValueError(f"targets CSR has {off.numel() - 1} rows for {n} query users")
+    n_t = items.numel()
+    ranks = torch.empty(n_t, dtype=torch.int64, device=dev)
+    values = torch.empty(n_t, dtype=torch.float32, device=dev) if want_values else None
+    if n == 0 or n_t == 0:
+        return ranks, values
+    ws_bytes = lib.trs_item_ranks_workspace_bytes(n, n_t)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    ct, cs = csr(off, items), csr(*seen) if seen is not None else None
+    check(lib.trs_item_ranks(NET_ID[net], C.byref(T), ptr(fold), fold.numel(), ptr(users), n, C.byref(ct),
+                             C.byref(cs) if cs is not None else None, ptr(ranks), ptr(values), ptr(ws), ws_bytes,
+                             _stream()), "trs_item_ranks")
+    return ranks, values
+
+
 def mask_seen(scores, users, seen):
     """Seen entries of score rows (n, n_items) fp32 -> -inf (trs_mask_seen), in place."""
     _dev(scores, "score rows", torch.float32)
