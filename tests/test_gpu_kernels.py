@@ -1,9 +1,16 @@
 # -*- coding: utf-8 -*-
-"""Kernel-level parity: libtrs_hip.so (through the C-ABI) against oracle/ on the same seeded inputs.  GPU only."""
+"""Kernel-level parity: libtrs_hip.so (through the C-ABI) against oracle/ on the same seeded inputs.  GPU only.
+
+The SGD-step tests are split into a case (`*_case()`: ids, tables, lr — no GPU, conditioned and sized so that one lost
+row reference is at least three allowances of the criterion), the GPU run, and the criterion on numpy tables
+(step_sensitivity.criterion_for); tests/test_step_sensitivity_host.py checks the first against the last without a GPU."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
+import step_sensitivity as sens
 from conftest import rel_err
 from oracle import loader as oloader
 from oracle import nets as onets
@@ -134,22 +141,42 @@ def test_forward_and_fwd_bwd(net, D, M, idx_dtype):
             assert abs(ls1.item() - ls2.item()) <= 1e-5 * abs(ls1.item())
 
 
-@pytest.mark.parametrize("net,D,M", [("fm", 64, 0), ("fm", 16, 2), ("linear", 32, 1), ("linear", 80, 0)])
+SGD_THREE_STEPS = [("fm", 64, 0), ("fm", 16, 2), ("linear", 32, 1), ("linear", 80, 0)]
+
+
+def lr_of(B, D, lr, at_least=0.05, hot=False):
+    """lr = None: the step size at which the table criterion sees one lost reference (tests/step_sensitivity.py)"""
+    return sens.step_lr(B, at_least, hot, D) if lr is None else lr
+
+
+@functools.lru_cache(maxsize=4)
+def sgd_three_steps_case(net, D, M, lr=None):
+    """The input of test_sgd_update_three_steps (no GPU): one batch of 300, three steps on it."""
+    def build(bump):
+        B = 300
+        p, batch, _ = make_case(net, D, M, B, seed=3 + 1000 * bump)
+        return sens.StepCase(net, sens.condition_tables(net, p), [batch] * 3, lr_of(B, D, lr), M=M, D=D)
+    return sens.conditioned(build, first=lr is not None)
+
+
+@pytest.mark.parametrize("net,D,M", SGD_THREE_STEPS)
 def test_sgd_update_three_steps(net, D, M):
     ops = _ops()
-    B, lr = 300, 0.05
-    p, batch, _ = make_case(net, D, M, B, seed=3)
+    case = sgd_three_steps_case(net, D, M)
+    p, batch, B, lr = case.p, case.batches[0], case.B, case.lr
     t, T, Bt, ids, err, keep = to_dev(net, p, batch, np.int64)
-    ref = {k: v.copy() for k, v in p.items()}
+    losses = []
     for step in range(3):
         loss_sum = torch.zeros(1, dtype=torch.float32, device=DEV)
         _, _, gr, gl = ops.score_fwd_bwd(net, T, Bt, B, D, M, DEV, loss_sum, want_scores=False)
         ops.score_sgd_update(net, T, Bt, gr, gl, lr)
-        _, _, loss, grads = onets.train_forward_backward(net, ref, batch)
-        ooptim.sgd_step(ref, grads, lr)
-        assert abs(loss_sum.item() / B - float(loss)) <= TOL * max(abs(float(loss)), 1e-3)
-    for k, v in ref.items():
-        assert rel_err(t[k].cpu().numpy(), v) < TOL, k
+        losses.append(loss_sum.item())
+    sens.assert_losses(case, losses)
+    sens.criterion_for(case)(tables_to_host(t), case.ref, p)
+
+
+def tables_to_host(t, names=None):
+    return {k: t[k].cpu().numpy() for k in (names or t)}
 
 
 @pytest.mark.parametrize("D", [1, 16, 64, 80, 200, 3, 7, 12, 40])
@@ -925,9 +952,11 @@ def test_colsum_rowdot_outer_gather():
             assert np.array_equal(xg[pas * 50:(pas + 1) * 50].cpu().numpy(), np.concatenate(cols, axis=1))
 
 
-@pytest.mark.parametrize("net,D", [("fm", 64), ("fm", 8), ("fm", 128), ("fm", 80), ("fm", 10), ("linear", 32),
-                                   ("linear", 256), ("linear", 7), ("fm", 512), ("fm", 1024), ("linear", 3),
-                                   ("fm", 201), ("linear", 12), ("fm", 33)])
+FAST_SGD_STEP = [("fm", 64), ("fm", 8), ("fm", 128), ("fm", 80), ("fm", 10), ("linear", 32), ("linear", 256), ("linear", 7),
+                 ("fm", 512), ("fm", 1024), ("linear", 3), ("fm", 201), ("linear", 12), ("fm", 33)]
+
+
+@pytest.mark.parametrize("net,D", FAST_SGD_STEP)
 def test_fast_sgd_step_matches_oracle_and_generic_path(net, D):
     """csrc/fast_step.hip (3-kernel exact SGD step, ids given) vs the oracle and vs the generic staged path.  The last
     six widths are the row shapes (4,64,2), (4,64,4), (1,4,1), (1,64,4), (4,4,1) and (1,64,1) of csrc/score_kernels.h's
@@ -936,16 +965,25 @@ def test_fast_sgd_step_matches_oracle_and_generic_path(net, D):
     check_fast_sgd_step(net, D)
 
 
+@functools.lru_cache(maxsize=4)
+def fast_sgd_step_case(net, D, lr=None):
+    """The input of check_fast_sgd_step (no GPU): one batch of 777 on 90 users and 41 items, three steps on it."""
+    def build(bump):
+        B = 777
+        p, batch, _ = make_case(net, D, 0, B, NU=90, NI=41, seed=D + 1000 * bump)
+        return sens.StepCase(net, sens.condition_tables(net, p), [batch] * 3, lr_of(B, D, lr), D=D)
+    return sens.conditioned(build, first=lr is not None)
+
+
 def check_fast_sgd_step(net, D, first_stamp=1, prepare_scratch=None):
     """first_stamp / prepare_scratch(scratch, net, NU, NI, B, D): the step stamps and the state of the duplicate-detection
     scratch a long run arrives with (tests/test_gpu_long_run.py)."""
     ops = _ops()
-    B, lr = 777, 0.05
-    p, batch, _ = make_case(net, D, 0, B, NU=90, NI=41, seed=D)
+    case = fast_sgd_step_case(net, D)
+    p, batch, B, lr = case.p, case.batches[0], case.B, case.lr
     t, T, Bt, ids, err, keep = to_dev(net, p, batch, np.int32)
     gz = torch.empty((2, B), device=DEV)
     du = torch.empty((B, D), device=DEV)
-    ref = {k: v.copy() for k, v in p.items()}
     losses = torch.zeros(3, device=DEV)
     scratch = ops.train_scratch(90, 41, B, D, DEV) if D != 8 else None  # D == 8 exercises the all-atomic variant
     if prepare_scratch is not None:
@@ -953,11 +991,8 @@ def check_fast_sgd_step(net, D, first_stamp=1, prepare_scratch=None):
     for step in range(3):
         ops.train_steps_sgd(net, T, None, None, 0, 0, 0, B, 1, lr, ids["user_id"], ids["pos_item_id"],
                             ids["neg_item_id"], gz, du, losses[step:step + 1], err, scratch, first_stamp + step)
-        _, _, loss, grads = onets.train_forward_backward(net, ref, batch)
-        ooptim.sgd_step(ref, grads, lr)
-        assert abs(losses[step].item() / B - float(loss)) <= TOL * max(abs(float(loss)), 1e-3)
-    for k, v in ref.items():
-        assert rel_err(t[k].cpu().numpy(), v) < TOL, k
+    sens.assert_losses(case, losses.cpu().numpy())
+    sens.criterion_for(case)(tables_to_host(t), case.ref, p)
     assert err.item() == 0
     # generic path from the same start: same result to rounding
     t2, T2, Bt2, ids2, err2, keep2 = to_dev(net, p, batch, np.int32)
@@ -969,15 +1004,37 @@ def check_fast_sgd_step(net, D, first_stamp=1, prepare_scratch=None):
         assert rel_err(t[k].cpu().numpy(), t2[k].cpu().numpy()) < 1e-6, k
 
 
+RESIDENT_TOL = 1e-6  # fast path against generic path: the same sums in another order
+
+
+@functools.lru_cache(maxsize=4)
+def resident_stream_case(lr=None):
+    """The input of test_fast_sgd_steps_from_resident_stream (no GPU): a stream of 5000 interactions, 5 batches of 512
+    from epoch position 1024 as the device RNG derives them (oracle/loader.py restates it).  The criterion's bar is ten
+    times tighter than TOL, so a tenth of the usual step size per triple meets the same ratio."""
+    def build(bump):
+        rs = np.random.RandomState(3 + 1000 * bump)
+        N, NU, NI, D, B = 5000, 300, 77, 16, 512
+        su, si = rs.randint(0, NU, N).astype(np.int32), rs.randint(0, NI, N).astype(np.int32)
+        p, _, _ = make_case("fm", D, 0, 8, NU=NU, NI=NI, seed=1)
+        key, seed_, n_steps = 0xFEEDBEEF12, 4242, 5
+        batches = []
+        for s_ in range(n_steps):
+            t0 = 1024 + s_ * B
+            out = oloader.device_batch(su, si, None, key, t0, B, NI, seed_, t0)
+            batches.append(sens.batch_of(np.asarray(out["user"]), np.asarray(out["pos"]), np.asarray(out["neg"])))
+        return sens.StepCase("fm", sens.condition_tables("fm", p), batches, max(0.1, sens.step_lr(B) * RESIDENT_TOL / TOL) if lr is None else lr,
+                             tol=RESIDENT_TOL, su=su, si=si, NU=NU, NI=NI, D=D, key=key, seed_=seed_)
+    return sens.conditioned(build, first=lr is not None)
+
+
 def test_fast_sgd_steps_from_resident_stream():
     """The C step loop deriving its batches from the stream == batch_prepare + generic step, step by step."""
     ops = _ops()
-    rs = np.random.RandomState(3)
-    N, NU, NI, D, B, lr = 5000, 300, 77, 16, 512, 0.1
-    su, si = rs.randint(0, NU, N).astype(np.int32), rs.randint(0, NI, N).astype(np.int32)
-    p, _, _ = make_case("fm", D, 0, 8, NU=NU, NI=NI, seed=1)
+    case = resident_stream_case()
+    p, su, si, NU, NI, D, B, lr = case.p, case.su, case.si, case.NU, case.NI, case.D, case.B, case.lr
     dsu, dsi = torch.from_numpy(su).to(DEV), torch.from_numpy(si).to(DEV)
-    key, seed_, n_steps = 0xFEEDBEEF12, 4242, 5
+    key, seed_, n_steps = case.key, case.seed_, case.nb
     # fast: one C call for 5 steps starting at epoch position 1024
     ta = {k: torch.from_numpy(v.copy()).to(DEV) for k, v in p.items()}
     Ta, keepa = ops.make_tables(ta["user.weight"], ta["item.weight"], ta["linear_user.weight"], ta["linear_item.weight"])
@@ -994,14 +1051,15 @@ def test_fast_sgd_steps_from_resident_stream():
     for s in range(n_steps):
         t0 = 1024 + s * B
         out = ops.batch_prepare(dsu, dsi, None, key, t0, B, NI, seed_, t0)
+        for q, name in (("user", "user_id"), ("pos", "pos_item_id"), ("neg", "neg_item_id")):  # (the case's batches)
+            assert np.array_equal(out[q].cpu().numpy().astype(np.int64), case.batches[s][name]), (s, q)
         Bt, kb = ops.make_batch(out["user"], out["pos"], out["neg"], None, None, err)
         _, _, gr, gl = ops.score_fwd_bwd("fm", Tb, Bt, B, D, 0, DEV, lb[s:s + 1], want_scores=False)
         ops.score_sgd_update("fm", Tb, Bt, gr, gl, lr)
     torch.cuda.synchronize()
     assert torch.equal(bufs[0], out["user"]) and torch.equal(bufs[1], out["pos"]) and torch.equal(bufs[2], out["neg"])
     assert np.allclose(la.cpu().numpy(), lb.cpu().numpy(), rtol=1e-6)
-    for k in p:
-        assert rel_err(ta[k].cpu().numpy(), tb[k].cpu().numpy()) < 1e-6, k
+    sens.ValueCriterion(RESIDENT_TOL)(tables_to_host(ta), tables_to_host(tb), p)
     assert err.item() == 0
 
 
@@ -1051,8 +1109,12 @@ def test_gemm_fused_bn_statistics(B, passes, K, H, bf16):
     assert rel_err(rm1.cpu().numpy(), rm2.cpu().numpy()) < 1e-6 and rel_err(rv1.cpu().numpy(), rv2.cpu().numpy()) < 2e-6
 
 
-@pytest.mark.parametrize("net,D,skew", [("fm", 64, False), ("fm", 64, True), ("fm", 16, True), ("linear", 32, True),
-                                        ("fm", 80, False), ("fm", 10, True), ("fm", 128, False)])
+BIG_FLAG_MODE_BUMP = {("linear", 32, True): 1}  # the seed bumps of flag_mode_case's big form (0 otherwise)
+FLAG_MODE = [("fm", 64, False), ("fm", 64, True), ("fm", 16, True), ("linear", 32, True), ("fm", 80, False), ("fm", 10, True),
+             ("fm", 128, False)]
+
+
+@pytest.mark.parametrize("net,D,skew", FLAG_MODE)
 @pytest.mark.parametrize("n_users", [300, 3_000_000])
 @pytest.mark.parametrize("one_launch", [False, True, "ordered"])
 def test_flag_mode_matches_oracle(net, D, skew, n_users, one_launch, tune):
@@ -1069,33 +1131,49 @@ def test_flag_mode_matches_oracle(net, D, skew, n_users, one_launch, tune):
     check_flag_mode(net, D, skew, n_users, one_launch, tune)
 
 
+@functools.lru_cache(maxsize=4)
+def flag_mode_case(net, D, skew, n_users, big=False, lr=None):
+    """The input of check_flag_mode (no GPU): 3 batches of 512 on 300 users that occur (at their places in a table of
+    n_users rows) and 57 or 5000 items, one hot item under skew.  big (the ordered form on the 3M-row table): mostly lone
+    references, 16 000 users and 20 000 items for batches of 2 048 — about 40 % of the triples carry a flag."""
+    def build(bump):
+        rs = np.random.RandomState(D + skew + 1000 * bump)
+        NU, NI, B, nb = n_users, 57 if n_users == 300 else 5000, 512, 3
+        NUS = 300  # users that occur
+        if big:
+            NUS, NI, B = 16000, 20000, 2048
+        p, _, _ = make_case(net, D, 0, 8, NU=NUS, NI=NI, seed=2)
+        urows = np.sort(rs.choice(NU, NUS, replace=False)) if NU > 300 else np.arange(300)  # the users that occur
+        u_small = rs.randint(0, NUS, nb * B)
+        i = rs.randint(0, NI, nb * B)
+        j = rs.randint(0, NI, nb * B)
+        if skew:
+            i[rs.rand(nb * B) < 0.4] = 7
+            j[rs.rand(nb * B) < 0.4] = 7
+        return sens.StepCase(net, sens.condition_tables(net, p), sens.batches_of(u_small, i, j, B, nb), lr_of(B, D, lr), D=D, NU=NU, NI=NI, NUS=NUS,
+                             urows=urows, u_small=u_small, i=i, j=j)
+    # (big: 36 000 rows of tables — the seed is written down, and checked by tests/test_step_sensitivity_host.py)
+    return sens.conditioned(build, first=lr is not None,
+                            bump=BIG_FLAG_MODE_BUMP.get((net, D, skew), 0) if big and lr is None else None)
+
+
 def check_flag_mode(net, D, skew, n_users, one_launch, tune, first_stamp=1, prepare_scratch=None):
     ops = _ops()
-    rs = np.random.RandomState(D + skew)
-    NU, NI, B, nb, lr = n_users, 57 if n_users == 300 else 5000, 512, 3, 0.05
-    NUS = 300  # users that occur
-    if one_launch == "ordered" and n_users > 300:
-        # mostly lone references (16 000 users and 20 000 items for batches of 2 048) and four iterations per wave: about
-        # 40 % of the triples carry a flag, so the workgroups count themselves in after iteration 2 of 4 (mid-loop)
-        NUS, NI, B = 16000, 20000, 2048
+    big = one_launch == "ordered" and n_users > 300
+    if big:  # four iterations per wave: the workgroups count themselves in after iteration 2 of 4 (mid-loop)
         tune(K1_ITERS=4)
-    p, _, _ = make_case(net, D, 0, 8, NU=NUS, NI=NI, seed=2)
-    urows = np.sort(rs.choice(NU, NUS, replace=False)) if NU > 300 else np.arange(300)  # the users that occur
-    u_small = rs.randint(0, NUS, nb * B)
+    case = flag_mode_case(net, D, skew, n_users, big)
+    p, NU, NI, NUS, B, nb, lr = case.p, case.NU, case.NI, case.NUS, case.B, case.nb, case.lr
+    urows, u_small, i, j = case.urows, case.u_small, case.i, case.j
     u = urows[u_small]
-    i = rs.randint(0, NI, nb * B)
-    j = rs.randint(0, NI, nb * B)
-    if skew:
-        i[rs.rand(nb * B) < 0.4] = 7
-        j[rs.rand(nb * B) < 0.4] = 7
     lin = ("user_bias.weight", "item_bias.weight") if net == "linear" else ("linear_user.weight", "linear_item.weight")
     t = {k: torch.from_numpy(v.copy()).to(DEV) for k, v in p.items()}
     if NU > 300:  # full-size user tables holding the 300 small rows at their places
-        big = torch.zeros((NU, D), device=DEV)
-        big[torch.from_numpy(urows).to(DEV)] = t["user.weight"]
+        bigD = torch.zeros((NU, D), device=DEV)
+        bigD[torch.from_numpy(urows).to(DEV)] = t["user.weight"]
         big1 = torch.zeros((NU, 1), device=DEV)
         big1[torch.from_numpy(urows).to(DEV)] = t[lin[0]]
-        t["user.weight"], t[lin[0]] = big, big1
+        t["user.weight"], t[lin[0]] = bigD, big1
     T, keep = ops.make_tables(t["user.weight"], t["item.weight"], t[lin[0]], t[lin[1]])
     err = torch.zeros(1, dtype=torch.int32, device=DEV)
     ordered = one_launch == "ordered"
@@ -1114,6 +1192,7 @@ def check_flag_mode(net, D, skew, n_users, one_launch, tune, first_stamp=1, prep
             assert nf == int(anyf.sum()) and anyf[:nf].all() and not anyf[nf:].any()
         u, i, j = uo, io, jo  # what the steps (and the oracle below) see
         u_small = np.array([small_of[int(x)] for x in u])
+    run = case.oracle_on(sens.batches_of(u_small, i, j, B, nb)) if ordered else case.oracle()  # (ordered: as the steps see them)
     for b in range(nb):
         sl = slice(b * B, (b + 1) * B)
         ucnt = np.unique(u[sl], return_counts=True)
@@ -1142,16 +1221,10 @@ def check_flag_mode(net, D, skew, n_users, one_launch, tune, first_stamp=1, prep
     torch.cuda.synchronize()
     if one_launch:  # every launch counted all its workgroups in, and the library knows how many it scheduled
         assert sync[1].value > 0 and sync[1].value % 3 == 0 and int(sync[0][0].item()) == sync[1].value
-    ref = {k: v.copy() for k, v in p.items()}
-    for b in range(nb):
-        batch = {"user_id": u_small[b * B:(b + 1) * B], "pos_item_id": i[b * B:(b + 1) * B], "neg_item_id": j[b * B:(b + 1) * B]}
-        _, _, loss, grads = onets.train_forward_backward(net, ref, batch)
-        ooptim.sgd_step(ref, grads, lr)
-        assert abs(losses[b].item() / B - float(loss)) <= TOL * max(abs(float(loss)), 1e-3)
+    sens.assert_losses(case, losses.cpu().numpy(), run)
     ut = torch.from_numpy(urows).to(DEV)
-    for k, v in ref.items():
-        got = t[k][ut] if (NU > 300 and k in ("user.weight", lin[0])) else t[k]
-        assert rel_err(got.cpu().numpy(), v) < TOL, k
+    got = {k: (t[k][ut] if (NU > 300 and k in ("user.weight", lin[0])) else t[k]).cpu().numpy() for k in run.after}
+    sens.criterion_for(case)(got, run.after, p)
     assert err.item() == 0
 
 
@@ -1216,20 +1289,34 @@ def test_flagged_first_order_any_batch_length(B, dense):
     assert err.item() == 0
 
 
-@pytest.mark.parametrize("net,D", [("fm", 64), ("linear", 32), ("fm", 128)])
+NO_SHARED_ROW = [("fm", 64), ("linear", 32), ("fm", 128)]
+
+
+@functools.lru_cache(maxsize=4)
+def no_shared_row_case(net, D, lr=None):
+    """The input of test_flag_mode_ordered_batches_without_any_shared_row (no GPU): 2 batches of 2048 on 4096 users and
+    8192 items, no row named twice in a batch."""
+    def build(bump):
+        NU, NI, B, nb = 4096, 8192, 2048, 2
+        rs = np.random.RandomState(D + 1000 * bump)
+        p, _, _ = make_case(net, D, 0, 8, NU=NU, NI=NI, seed=3)
+        u = np.concatenate([rs.permutation(NU)[:B] for _ in range(nb)])
+        it = [rs.permutation(NI) for _ in range(nb)]
+        i, j = np.concatenate([x[:B] for x in it]), np.concatenate([x[B:2 * B] for x in it])
+        return sens.StepCase(net, sens.condition_tables(net, p), sens.batches_of(u, i, j, B, nb), lr_of(B, D, lr), D=D, NU=NU, NI=NI, u=u, i=i, j=j)
+    return sens.conditioned(build, first=lr is not None)
+
+
+@pytest.mark.parametrize("net,D", NO_SHARED_ROW)
 def test_flag_mode_ordered_batches_without_any_shared_row(net, D, tune):
     """Flagged-first order, edge: no row is named twice in a batch — n_flagged = 0, the one-launch step counts its
     workgroups in before their first iteration, no wave has anything to apply — 2 steps == oracle SGD steps; and the
     arrival counter still advances by the grid per launch."""
     import ctypes
     ops = _ops()
-    NU, NI, B, nb, lr = 4096, 8192, 2048, 2, 0.05
     tune(K1_ITERS=4)
-    rs = np.random.RandomState(D)
-    p, _, _ = make_case(net, D, 0, 8, NU=NU, NI=NI, seed=3)
-    u = np.concatenate([rs.permutation(NU)[:B] for _ in range(nb)])
-    it = [rs.permutation(NI) for _ in range(nb)]
-    i, j = np.concatenate([x[:B] for x in it]), np.concatenate([x[B:2 * B] for x in it])
+    case = no_shared_row_case(net, D)
+    p, NU, NI, B, nb, lr, u, i, j = case.p, case.NU, case.NI, case.B, case.nb, case.lr, case.u, case.i, case.j
     lin = ("user_bias.weight", "item_bias.weight") if net == "linear" else ("linear_user.weight", "linear_item.weight")
     t = {k: torch.from_numpy(v.copy()).to(DEV) for k, v in p.items()}
     T, keep = ops.make_tables(t["user.weight"], t["item.weight"], t[lin[0]], t[lin[1]])
@@ -1248,19 +1335,15 @@ def test_flag_mode_ordered_batches_without_any_shared_row(net, D, tune):
                         ustage=torch.empty((B, D), device=DEV), sync=sync, n_flagged=ef.n_flagged_from(0))
     torch.cuda.synchronize()
     assert sync[1].value > 0 and sync[1].value % nb == 0 and int(sync[0][0].item()) == sync[1].value
-    ref = {k: v.copy() for k, v in p.items()}
-    for b in range(nb):
-        batch = {"user_id": u[b * B:(b + 1) * B], "pos_item_id": i[b * B:(b + 1) * B], "neg_item_id": j[b * B:(b + 1) * B]}
-        _, _, loss, grads = onets.train_forward_backward(net, ref, batch)
-        ooptim.sgd_step(ref, grads, lr)
-        assert abs(losses[b].item() / B - float(loss)) <= TOL * max(abs(float(loss)), 1e-3)
-    for k, v in ref.items():
-        assert rel_err(t[k].cpu().numpy(), v) < TOL, k
+    sens.assert_losses(case, losses.cpu().numpy())
+    sens.criterion_for(case)(tables_to_host(t), case.ref, p)
     assert err.item() == 0
 
 
-@pytest.mark.parametrize("net,D,skew", [("fm", 64, False), ("fm", 64, True), ("fm", 16, True), ("linear", 32, True),
-                                        ("fm", 80, False), ("fm", 10, True)])
+PRESORTED_ITEM = [("fm", 64, False), ("fm", 64, True), ("fm", 16, True), ("linear", 32, True), ("fm", 80, False), ("fm", 10, True)]
+
+
+@pytest.mark.parametrize("net,D,skew", PRESORTED_ITEM)
 @pytest.mark.parametrize("inline_user", [False, True, "items", "userflags"])
 def test_presorted_item_update_matches_oracle(net, D, skew, inline_user):
     """trs_epoch_presort + the atomic-free per-run item update: 3 batches in one C call == oracle SGD steps.
@@ -1272,17 +1355,28 @@ def test_presorted_item_update_matches_oracle(net, D, skew, inline_user):
     check_presorted_item_update(net, D, skew, inline_user)
 
 
+@functools.lru_cache(maxsize=4)
+def presorted_item_update_case(net, D, skew, lr=None):
+    """The input of check_presorted_item_update (no GPU): 3 batches of 512 on 300 users and 57 items, one hot item under
+    skew."""
+    def build(bump):
+        rs = np.random.RandomState(D + skew + 1000 * bump)
+        NU, NI, B, nb = 300, 57, 512, 3
+        p, _, _ = make_case(net, D, 0, 8, NU=NU, NI=NI, seed=2)
+        u = rs.randint(0, NU, nb * B)
+        i = rs.randint(0, NI, nb * B)
+        j = rs.randint(0, NI, nb * B)
+        if skew:
+            i[rs.rand(nb * B) < 0.4] = 7
+            j[rs.rand(nb * B) < 0.4] = 7
+        return sens.StepCase(net, sens.condition_tables(net, p), sens.batches_of(u, i, j, B, nb), lr_of(B, D, lr), D=D, NU=NU, NI=NI, u=u, i=i, j=j)
+    return sens.conditioned(build, first=lr is not None)
+
+
 def check_presorted_item_update(net, D, skew, inline_user, first_stamp=1, prepare_scratch=None):
     ops = _ops()
-    rs = np.random.RandomState(D + skew)
-    NU, NI, B, nb, lr = 300, 57, 512, 3, 0.05
-    p, _, _ = make_case(net, D, 0, 8, NU=NU, NI=NI, seed=2)
-    u = rs.randint(0, NU, nb * B)
-    i = rs.randint(0, NI, nb * B)
-    j = rs.randint(0, NI, nb * B)
-    if skew:
-        i[rs.rand(nb * B) < 0.4] = 7
-        j[rs.rand(nb * B) < 0.4] = 7
+    case = presorted_item_update_case(net, D, skew)
+    p, NU, NI, B, nb, lr, u, i, j = case.p, case.NU, case.NI, case.B, case.nb, case.lr, case.u, case.i, case.j
     lin = ("user_bias.weight", "item_bias.weight") if net == "linear" else ("linear_user.weight", "linear_item.weight")
     t = {k: torch.from_numpy(v.copy()).to(DEV) for k, v in p.items()}
     T, keep = ops.make_tables(t["user.weight"], t["item.weight"], t[lin[0]], t[lin[1]])
@@ -1315,14 +1409,8 @@ def check_presorted_item_update(net, D, skew, inline_user, first_stamp=1, prepar
         ops.train_steps_sgd(net, T, None, None, 0, 0, 0, B, nb, lr, *ids, gz, du, losses, err,
                             scratch, first_stamp, None, sk, sv, ps.key_bytes)
     torch.cuda.synchronize()
-    ref = {k: v.copy() for k, v in p.items()}
-    for b in range(nb):
-        batch = {"user_id": u[b * B:(b + 1) * B], "pos_item_id": i[b * B:(b + 1) * B], "neg_item_id": j[b * B:(b + 1) * B]}
-        _, _, loss, grads = onets.train_forward_backward(net, ref, batch)
-        ooptim.sgd_step(ref, grads, lr)
-        assert abs(losses[b].item() / B - float(loss)) <= TOL * max(abs(float(loss)), 1e-3)
-    for k, v in ref.items():
-        assert rel_err(t[k].cpu().numpy(), v) < TOL, k
+    sens.assert_losses(case, losses.cpu().numpy())
+    sens.criterion_for(case)(tables_to_host(t), case.ref, p)
     assert err.item() == 0
 
 
@@ -1411,35 +1499,50 @@ def check_presorted_adaptive_rules(net, D, skew, kind, first_stamp=1, prepare_sc
     return cuts_listed
 
 
-@pytest.mark.parametrize("net,D,M,skew", [("fm", 64, 1, False), ("fm", 16, 3, True), ("linear", 32, 1, True),
-                                          ("linear", 8, 2, False), ("fm", 10, 1, True)])
-@pytest.mark.parametrize("meta_sorted,B", [(False, 512), (True, 512), (True, 509), (True, 3), ("hot", 2048)])
+PRESORTED_META = [("fm", 64, 1, False), ("fm", 16, 3, True), ("linear", 32, 1, True), ("linear", 8, 2, False), ("fm", 10, 1, True)]
+PRESORTED_META_FORMS = [(False, 512), (True, 512), (True, 509), (True, 3), ("hot", 2048)]
+
+
+@pytest.mark.parametrize("net,D,M,skew", PRESORTED_META)
+@pytest.mark.parametrize("meta_sorted,B", PRESORTED_META_FORMS)
 def test_presorted_step_with_metadata_matches_oracle(net, D, M, skew, meta_sorted, B):
     """Metadata scorers on the presorted step (SGD): K1 = the scorer's staging mode (ids from the item -> metadata
     table, user update in place, FM: per-pass field sums staged), user / item rows through the sorted runs (FM: w +=
     sum(c*S) - sum(c)*w), metadata tables through the atomic scatter of the staged fields: 3 batches == oracle steps.
-    "hot": 90 % of the items carry category 0 of the first column, batch 2048, a ten times larger step — that row's run
+    "hot": 90 % of the items carry category 0 of the first column, batch 2048 — that row's run
     is ~3 700 references long and is cut into ~58 pieces of 64; FM's pieces subtract sum(c)*w with the w they loaded,
     which other pieces may already have touched (second order in the step size): held to the same 1e-5."""
     check_presorted_step_with_metadata(net, D, M, skew, meta_sorted, B)
 
 
+@functools.lru_cache(maxsize=4)
+def presorted_metadata_case(net, D, M, skew, hot, B, lr=None):
+    """The input of check_presorted_step_with_metadata (no GPU): 3 batches of B on 300 users, 57 items and M metadata
+    columns; hot: 90 % of the items in category 0 of the first column."""
+    def build(bump):
+        rs = np.random.RandomState(D + M + skew + 1000 * bump)
+        NU, NI, nb = 300, 57, 3
+        p, _, _ = make_case(net, D, M, 8, NU=NU, NI=NI, seed=2)
+        sizes = [p[f"metadata.{m}.weight"].shape[0] for m in range(M)]
+        item_meta = np.stack([rs.randint(0, sizes[m], NI) for m in range(M)], axis=1).astype(np.int32)
+        if hot:
+            item_meta[rs.rand(NI) < 0.9, 0] = 0
+        u, i, j = rs.randint(0, NU, nb * B), rs.randint(0, NI, nb * B), rs.randint(0, NI, nb * B)
+        if skew:
+            i[rs.rand(nb * B) < 0.4] = 7
+            j[rs.rand(nb * B) < 0.4] = 7
+        return sens.StepCase(net, sens.condition_tables(net, p), sens.batches_of(u, i, j, B, nb, item_meta),
+                             lr_of(B, D, lr, 0.5 if hot else 0.05, hot), D=D, M=M, NU=NU, NI=NI,
+                             u=u, i=i, j=j, item_meta=item_meta, sizes=sizes)
+    return sens.conditioned(build, first=lr is not None)
+
+
 def check_presorted_step_with_metadata(net, D, M, skew, meta_sorted, B, first_stamp=1, prepare_scratch=None):
     from torchrecsys_amd import _lib
     ops = _ops()
-    rs = np.random.RandomState(D + M + skew)
-    NU, NI, nb, lr = 300, 57, 3, 0.05
-    hot = meta_sorted == "hot"
-    p, _, _ = make_case(net, D, M, 8, NU=NU, NI=NI, seed=2)
-    sizes = [p[f"metadata.{m}.weight"].shape[0] for m in range(M)]
-    item_meta = np.stack([rs.randint(0, sizes[m], NI) for m in range(M)], axis=1).astype(np.int32)
-    if hot:
-        item_meta[rs.rand(NI) < 0.9, 0] = 0
-        lr = 0.5
-    u, i, j = rs.randint(0, NU, nb * B), rs.randint(0, NI, nb * B), rs.randint(0, NI, nb * B)
-    if skew:
-        i[rs.rand(nb * B) < 0.4] = 7
-        j[rs.rand(nb * B) < 0.4] = 7
+    case = presorted_metadata_case(net, D, M, skew, meta_sorted == "hot", B)
+    p, NU, NI, nb, lr, u, i, j = case.p, case.NU, case.NI, case.nb, case.lr, case.u, case.i, case.j
+    item_meta, sizes = case.item_meta, case.sizes
     lin = ("user_bias.weight", "item_bias.weight") if net == "linear" else ("linear_user.weight", "linear_item.weight")
     t = {k: torch.from_numpy(v.copy()).to(DEV) for k, v in p.items()}
     metas = [t[f"metadata.{m}.weight"] for m in range(M)]
@@ -1475,16 +1578,8 @@ def check_presorted_step_with_metadata(net, D, M, skew, meta_sorted, B, first_st
                         scratch, first_stamp, None, sk, sv, ps.key_bytes, udup,
                         torch.empty((B, D), device=DEV), usorted, None, ms)
     torch.cuda.synchronize()
-    ref = {k: v.copy() for k, v in p.items()}
-    for b in range(nb):
-        sl = slice(b * B, (b + 1) * B)
-        batch = {"user_id": u[sl], "pos_item_id": i[sl], "neg_item_id": j[sl],
-                 "pos_metadata_id": item_meta[i[sl]].astype(np.int64), "neg_metadata_id": item_meta[j[sl]].astype(np.int64)}
-        _, _, loss, grads = onets.train_forward_backward(net, ref, batch)
-        ooptim.sgd_step(ref, grads, lr)
-        assert abs(losses[b].item() / B - float(loss)) <= TOL * max(abs(float(loss)), 1e-3)
-    for k, v in ref.items():
-        assert rel_err(t[k].cpu().numpy(), v) < TOL, k
+    sens.assert_losses(case, losses.cpu().numpy())
+    sens.criterion_for(case)(tables_to_host(t), case.ref, p)
     assert err.item() == 0
 
 

@@ -14,8 +14,8 @@ norm-wise criterion cannot see:
 
 Tables are small (300 users, 57 items); B = 131 (prime: a partial last wave for every G) with the grid capped at two
 workgroups for the direct kernels, B = 192 and 3 batches with one hot item for the presorted and flag-mode steps."""
-import contextlib
 import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -24,6 +24,7 @@ import torch
 import mining_ref
 import multineg_ref
 import row_shapes
+import step_sensitivity as sens
 import test_gpu_mining as t_mine
 import test_gpu_multineg as t_multi
 import test_gpu_warp as t_warp
@@ -32,6 +33,7 @@ from conftest import rel_err
 from oracle import nets as onets
 from oracle import optim as ooptim
 from row_shapes import ALL, FULL, RAGGED
+from step_sensitivity import batch_of, float64_oracle
 from test_gpu_kernels import DEV, TOL, dense_from_staging, make_case
 
 pytestmark = pytest.mark.gpu
@@ -149,14 +151,6 @@ def make_item_meta(rs, p, M):
     return im, sizes
 
 
-def batch_of(u, i, j, item_meta=None, sl=slice(None)):
-    b = {"user_id": u[sl].astype(np.int64), "pos_item_id": i[sl].astype(np.int64), "neg_item_id": j[sl].astype(np.int64)}
-    if item_meta is not None and item_meta.shape[1]:
-        b["pos_metadata_id"] = item_meta[i[sl]].astype(np.int64)
-        b["neg_metadata_id"] = item_meta[j[sl]].astype(np.int64)
-    return b
-
-
 def referenced_rows(p, u, i, j, item_meta=None):
     items = np.union1d(i, j)
     out = {}
@@ -180,22 +174,60 @@ def device_batch(u, i, j, item_meta, err):
     return ids, Bt, keep
 
 
-def oracle_sgd(net, p, u, i, j, B, nb, lr, losses, item_meta=None):
-    """nb oracle SGD steps on consecutive batches of B; every step's loss against losses[b] at TOL."""
-    ref = {k: v.copy() for k, v in p.items()}
-    for b in range(nb):
-        batch = batch_of(u, i, j, item_meta, slice(b * B, (b + 1) * B))
-        _, _, loss, grads = onets.train_forward_backward(net, ref, batch)
-        ooptim.sgd_step(ref, grads, lr)
-        assert abs(losses[b].item() / B - float(loss)) <= TOL * max(abs(float(loss)), 1e-3), b
-    return ref
+def step_case(net, D, M, B, nb, ids_seed, repeat=False, skew=False, hot=False, lr=None, per_row=False):
+    """The input of the SGD-step cells (no GPU), conditioned (tests/step_sensitivity.py).  repeat: one batch, nb steps on
+    it; otherwise nb consecutive batches.  hot: 90 % of the items in category 0 of the first metadata column."""
+    def build(bump):
+        rs = np.random.RandomState(ids_seed + 1000 * bump)
+        p = sens.condition_tables(net, make_params(net, D, M))
+        item_meta, sizes = make_item_meta(rs, p, M) if M else (None, None)
+        if hot:
+            item_meta[1:NI - 1][rs.rand(NI - 2) < 0.9, 0] = 0
+        u, i, j = make_ids(rs, B if repeat else nb * B, skew=skew)
+        batches = [batch_of(u, i, j, item_meta)] * nb if repeat else sens.batches_of(u, i, j, B, nb, item_meta)
+        step = 0.05 if per_row else sens.step_lr(B, 0.5 if hot else 0.05, hot, D)
+        return sens.StepCase(net, p, batches, step if lr is None else lr, D=D, u=u, i=i, j=j, item_meta=item_meta, sizes=sizes,
+                             per_row=per_row and lr is None)
+    return sens.conditioned(build, first=lr is not None)
 
 
-def assert_tables(t, ref, tol=TOL):
-    for k, v in ref.items():
-        e = rel_err(t[k].cpu().numpy(), v)
-        print(f"{k}: {e:.2e}")
-        assert e < tol, k
+@functools.lru_cache(maxsize=4)
+def generic_step_case(net, D, lr=None):
+    """test_generic_sgd_step: one batch of 131, two steps"""
+    return step_case(net, D, 0, 131, 2, D, repeat=True, lr=lr)
+
+
+@functools.lru_cache(maxsize=4)
+def three_kernel_step_case(net, D, lr=None):
+    """test_three_kernel_sgd_step: one batch of 131, three steps"""
+    return step_case(net, D, 0, 131, 3, D, repeat=True, lr=lr)
+
+
+@functools.lru_cache(maxsize=4)
+def two_launch_step_case(net, D, lr=None):
+    """test_presorted_two_launch_step and test_flag_mode_step: 3 batches of 192, one hot item"""
+    return step_case(net, D, 0, 192, 3, D, skew=True, lr=lr)
+
+
+@functools.lru_cache(maxsize=4)
+def metadata_step_case(net, D, M, hot, lr=None):
+    """test_presorted_step_with_metadata: 3 batches of 192, one hot item, M metadata columns.
+    FM without the hot category keeps lr = 0.05 and is judged per row as well (a quarter of the row's smallest single
+    reference: step_sensitivity.RowChangeCriterion).  Its runs subtract sum(c) * w, and a run that a
+    64-reference chunk boundary cuts in two does so with a w the other piece may already have added to — second order in
+    the step size, and timing dependent.  At the step size the value criterion needs (lr / B = 5.9e-3) that term was
+    measured at 0.7e-5 ... 1.8e-5 of max|item.weight| on exactly the rows that straddle a boundary, at the widths whose
+    rows take a whole wave (D = 132, 512, 516; below 1.2e-6 at D <= 64): a tenth of the smallest single reference, but
+    past the 1e-5 of the value criterion.  At lr = 0.05 it is 500 times smaller and the per-row criterion sees every
+    reference."""
+    return step_case(net, D, M, 192, 3, D + M, skew=True, hot=bool(hot), lr=lr, per_row=net == "fm" and not hot)
+
+
+def assert_step(case, t, losses, run=None):
+    """the criterion of the SGD-step cells: every step's loss, then the tables (got, ref, before)"""
+    run = run or case.oracle()
+    sens.assert_losses(case, losses.cpu().numpy(), run)
+    sens.criterion_for(case)({k: t[k].cpu().numpy() for k in run.after}, run.after, case.p)
 
 
 def zero_err():
@@ -281,10 +313,8 @@ def test_score_all_items(net, D, M, tune):
 def test_generic_sgd_step(net, D, tune):
     ops = _ops()
     tune(GRID_CAP=2)
-    B, lr, steps = 131, 0.05, 2
-    rs = np.random.RandomState(D)
-    p = make_params(net, D, 0)
-    u, i, j = make_ids(rs, B)
+    case = generic_step_case(net, D)
+    p, u, i, j, B, lr, steps = case.p, case.u, case.i, case.j, case.B, case.lr, case.nb
     g = Guards()
     t, T, keep = guarded_tables(net, p, g)
     err = zero_err()
@@ -295,8 +325,7 @@ def test_generic_sgd_step(net, D, tune):
         ops.score_fwd_bwd(net, T, Bt, B, D, 0, DEV, losses[s:s + 1], want_scores=False, grad_rows=gr, grad_lin=gl)
         ops.score_sgd_update(net, T, Bt, gr, gl, lr)
     torch.cuda.synchronize()
-    ref = oracle_sgd(net, p, np.tile(u, steps), np.tile(i, steps), np.tile(j, steps), B, steps, lr, losses)
-    assert_tables(t, ref)
+    assert_step(case, t, losses)
     assert err.item() == 0
     g.check(referenced_rows(p, u, i, j))
 
@@ -312,10 +341,8 @@ def test_three_kernel_sgd_step(net, D, with_scratch, tune):
     test_fast_sgd_step_matches_oracle_and_generic_path."""
     ops = _ops()
     tune(GRID_CAP=2)
-    B, lr, steps = 131, 0.05, 3
-    rs = np.random.RandomState(D)
-    p = make_params(net, D, 0)
-    u, i, j = make_ids(rs, B)
+    case = three_kernel_step_case(net, D)
+    p, u, i, j, B, lr, steps = case.p, case.u, case.i, case.j, case.B, case.lr, case.nb
     g = Guards()
     t, T, keep = guarded_tables(net, p, g)
     err = zero_err()
@@ -326,8 +353,7 @@ def test_three_kernel_sgd_step(net, D, with_scratch, tune):
     for s in range(steps):
         ops.train_steps_sgd(net, T, None, None, 0, 0, 0, B, 1, lr, *ids, gz, du, losses[s:s + 1], err, scratch, 1 + s)
     torch.cuda.synchronize()
-    ref = oracle_sgd(net, p, np.tile(u, steps), np.tile(i, steps), np.tile(j, steps), B, steps, lr, losses)
-    assert_tables(t, ref)
+    assert_step(case, t, losses)
     assert err.item() == 0
     g.check(referenced_rows(p, u, i, j))
 
@@ -341,10 +367,8 @@ def test_presorted_two_launch_step(net, D, inline_user):
     """trs_epoch_presort + the sorted-run updates (trs_launch_sorted_item_update, _updates_fused, _user_dup_update), one hot
     item: 3 batches in one C call == oracle steps, as test_presorted_item_update_matches_oracle."""
     ops = _ops()
-    B, nb, lr = 192, 3, 0.05
-    rs = np.random.RandomState(D)
-    p = make_params(net, D, 0)
-    u, i, j = make_ids(rs, nb * B, skew=True)
+    case = two_launch_step_case(net, D)
+    p, u, i, j, B, nb, lr = case.p, case.u, case.i, case.j, case.B, case.nb, case.lr
     g = Guards()
     t, T, keep = guarded_tables(net, p, g)
     err = zero_err()
@@ -361,8 +385,7 @@ def test_presorted_two_launch_step(net, D, inline_user):
         ops.train_steps_sgd(net, T, None, None, 0, 0, 0, B, nb, lr, *ids, gz, du, losses, err, scratch, 1, None, sk, sv,
                             ps.key_bytes)
     torch.cuda.synchronize()
-    ref = oracle_sgd(net, p, u, i, j, B, nb, lr, losses)
-    assert_tables(t, ref)
+    assert_step(case, t, losses)
     assert err.item() == 0
     g.check(referenced_rows(p, u, i, j))
 
@@ -381,10 +404,9 @@ def test_flag_mode_step(net, D, mode, tune):
     one_launch, ordered = mode != "two", mode == "ordered"
     if mode.startswith("one-nt"):
         tune(K1_NT=int(mode[-1]))
-    B, nb, lr = 192, 3, 0.05
-    rs = np.random.RandomState(D)
-    p = make_params(net, D, 0)
-    u, i, j = make_ids(rs, nb * B, skew=True)
+    case = two_launch_step_case(net, D)
+    p, u, i, j, B, nb, lr = case.p, case.u, case.i, case.j, case.B, case.nb, case.lr
+    run = None
     g = Guards()
     t, T, keep = guarded_tables(net, p, g)
     err = zero_err()
@@ -398,6 +420,7 @@ def test_flag_mode_step(net, D, mode, tune):
             a_, b_ = np.stack([u[sl], i[sl], j[sl]], 1), np.stack([uo[sl], io[sl], jo[sl]], 1)
             assert np.array_equal(a_[np.lexsort(a_.T)], b_[np.lexsort(b_.T)])
         u, i, j = uo, io, jo
+        run = case.oracle_on(sens.batches_of(u, i, j, B, nb))
     gz, du, ustage = torch.empty((2, B), device=DEV), g.staging("du", B, D), g.staging("ustage", B, D)
     losses = torch.zeros(nb, device=DEV)
     sync = (torch.zeros(288, dtype=torch.int32, device=DEV), ctypes.c_uint32(0)) if one_launch else None
@@ -418,8 +441,7 @@ def test_flag_mode_step(net, D, mode, tune):
         BRANCH.setdefault(row_shapes.variant(D), {})[mode] = branch
         print(f"one-launch step, shape {row_shapes.variant(D)}, {mode}: {branch}")
     assert err.item() == 0, f"err {err.item()} (bit 2 = 4: the bounded grid wait ran out)"
-    ref = oracle_sgd(net, p, u, i, j, B, nb, lr, losses)
-    assert_tables(t, ref)
+    assert_step(case, t, losses, run)
     g.check(referenced_rows(p, u, i, j))
 
 
@@ -444,17 +466,6 @@ def adaptive_ids(rs, n):
     whenever the two counts agree — a sixth of 57 items per batch of 192.  That is a property of the input, so the
     input avoids it: an item is a positive or a negative, never both, and every term of a row's sum has one sign."""
     return make_ids(rs, n, split=True)
-
-
-@contextlib.contextmanager
-def float64_oracle():
-    """oracle/ computes in numpy fp32 (its module constant F32); with the constant swapped, the same code runs in
-    float64 on float64 tables — the yardstick for how far fp32 rounding alone moves a result."""
-    onets.F32 = ooptim.F32 = np.float64
-    try:
-        yield
-    finally:
-        onets.F32 = ooptim.F32 = np.float32
 
 
 def oracle_adaptive(net, kind, hp, p, u, i, j, B, nb, item_meta=None):
@@ -591,22 +602,22 @@ META_CELLS = [(n, D, 1, True) for n, D in cells("presorted step with metadata", 
              [(n, D, 3, True) for n, D in cells("presorted step with metadata", META_M3)]
 
 
+# (builder, its distinct argument tuples): what tests/test_step_sensitivity_host.py walks
+STEP_CASES = [(generic_step_case, cells("generic step: score_fwd_bwd + score_sgd_update", ALL)),
+              (three_kernel_step_case, cells("3-kernel step", ALL)),
+              (two_launch_step_case, cells("presorted two-launch step", ALL)),
+              (metadata_step_case, sorted({(n, D, M, v == "hot") for n, D, M, v in META_CELLS}))]
+
+
 @pytest.mark.parametrize("net,D,M,meta_sorted", META_CELLS)
 def test_presorted_step_with_metadata(net, D, M, meta_sorted):
     """launch_meta_stage[_mt] / score_kernel MODE 2 + the sorted item, user and metadata runs
     (trs_launch_sorted_meta_update) or the atomic scatter of the staged fields (meta_sorted False): 3 batches == oracle
-    steps, as test_presorted_step_with_metadata_matches_oracle.  "hot": 90 % of the items in category 0 and a ten times
-    larger step — that row's run is cut into pieces of 64."""
+    steps, as test_presorted_step_with_metadata_matches_oracle.  "hot": 90 % of the items in category 0 — that row's run
+    is cut into pieces of 64.  (Step sizes and criterion: metadata_step_case.)"""
     ops = _ops()
-    B, nb, lr = 192, 3, 0.05
-    hot = meta_sorted == "hot"
-    rs = np.random.RandomState(D + M)
-    p = make_params(net, D, M)
-    item_meta, sizes = make_item_meta(rs, p, M)
-    if hot:
-        item_meta[1:NI - 1][rs.rand(NI - 2) < 0.9, 0] = 0
-        lr = 0.5
-    u, i, j = make_ids(rs, nb * B, skew=True)
+    case = metadata_step_case(net, D, M, meta_sorted == "hot")
+    p, u, i, j, B, nb, lr, item_meta, sizes = case.p, case.u, case.i, case.j, case.B, case.nb, case.lr, case.item_meta, case.sizes
     g = Guards()
     t, T, keep = guarded_tables(net, p, g)
     err = zero_err()
@@ -621,8 +632,7 @@ def test_presorted_step_with_metadata(net, D, M, meta_sorted):
     ops.train_steps_sgd(net, T, None, None, 0, 0, 0, B, nb, lr, *ids, gz, du, losses, err,
                         ops.train_scratch(NU, NI, B, D, DEV), 1, None, sk, sv, ps.key_bytes, udup, ustage, usorted, None, ms)
     torch.cuda.synchronize()
-    ref = oracle_sgd(net, p, u, i, j, B, nb, lr, losses, item_meta)
-    assert_tables(t, ref)
+    assert_step(case, t, losses)
     assert err.item() == 0
     g.check(referenced_rows(p, u, i, j, item_meta))
 

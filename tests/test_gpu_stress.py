@@ -2,10 +2,13 @@
 """Randomised shapes for the presorted two-launch step (SGD / SparseAdam / Adagrad): odd batch sizes, tiny tables (every
 row duplicated many times), batches smaller than one 64-reference chunk, D from 1 to 200, skewed ids — each compared
 with the oracle on a few steps.  GPU only."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
+import step_sensitivity as sens
 from conftest import rel_err
 from oracle import nets as onets
 from oracle import optim as ooptim
@@ -32,15 +35,40 @@ def _cases():
     return out
 
 
-@pytest.mark.parametrize("case", _cases(), ids=lambda c: f"{c[0]}-{c[1]}-D{c[2]}-B{c[3]}-U{c[4]}-I{c[5]}-n{c[6]}-{c[7]}")
-def test_presorted_step_random_shapes(case):
-    from torchrecsys_amd import _lib, ops
+STRESS_TOL = 3e-5  # this module's bar on losses and tables
+SGD_CASES = [c for c in _cases() if c[7] == "sgd"]
+
+
+def case_inputs(case, bump=0):
     seed_, net, D, B, NU, NI, nb, kind, skew = case
-    rs = np.random.RandomState(seed_)
+    rs = np.random.RandomState(seed_ + 1000 * bump)
     p, _, _ = make_case(net, D, 0, 8, NU=NU, NI=NI, seed=seed_)
     u, i, j = rs.randint(0, NU, nb * B), rs.randint(0, NI, nb * B), rs.randint(0, NI, nb * B)
     if skew:
         i[rs.rand(nb * B) < 0.5] = NI - 1
+    return p, u, i, j
+
+
+@functools.lru_cache(maxsize=4)
+def sgd_case_by_number(number, lr=None):
+    """The input of the sgd cases (no GPU), conditioned (tests/step_sensitivity.py); the criterion's bar is 3e-5, so the
+    step size per triple is three times the usual one."""
+    case = next(c for c in SGD_CASES if c[0] == number)
+    net, B, nb = case[1], case[3], case[6]
+
+    def build(bump):
+        p, u, i, j = case_inputs(case, bump)
+        return sens.StepCase(net, sens.condition_tables(net, p), sens.batches_of(u, i, j, B, nb),
+                             sens.step_lr(B, D=case[2]) * STRESS_TOL / sens.TOL if lr is None else lr, tol=STRESS_TOL, u=u, i=i, j=j)
+    return sens.conditioned(build, first=lr is not None)
+
+
+@pytest.mark.parametrize("case", _cases(), ids=lambda c: f"{c[0]}-{c[1]}-D{c[2]}-B{c[3]}-U{c[4]}-I{c[5]}-n{c[6]}-{c[7]}")
+def test_presorted_step_random_shapes(case):
+    from torchrecsys_amd import _lib, ops
+    seed_, net, D, B, NU, NI, nb, kind, skew = case
+    sgd = sgd_case_by_number(seed_) if kind == "sgd" else None
+    p, u, i, j = (sgd.p, sgd.u, sgd.i, sgd.j) if sgd else case_inputs(case)
     lin = ("user_bias.weight", "item_bias.weight") if net == "linear" else ("linear_user.weight", "linear_item.weight")
     names = ["user.weight", "item.weight", lin[0], lin[1]]
     t = {k: torch.from_numpy(v.copy()).to(DEV) for k, v in p.items()}
@@ -51,7 +79,7 @@ def test_presorted_step_random_shapes(case):
     ids, sk, sv, udup, usorted, idup = ps.step_args(0)
     gz, du = torch.empty((2, B), device=DEV), torch.empty((B, D), device=DEV)
     losses = torch.zeros(nb, device=DEV)
-    lr, b1, b2, eps, lr_decay = {"sgd": (0.05, 0, 0, 0, 0), "sparse_adam": (0.01, 0.9, 0.999, 1e-8, 0.0),
+    lr, b1, b2, eps, lr_decay = {"sgd": (sgd.lr if sgd else None, 0, 0, 0, 0), "sparse_adam": (0.01, 0.9, 0.999, 1e-8, 0.0),
                                  "adagrad": (0.05, 0, 0, 1e-10, 0.01)}[kind]
     s1 = {k: torch.zeros_like(t[k]) for k in names}
     s2 = {k: torch.zeros_like(t[k]) for k in names}
@@ -80,6 +108,11 @@ def test_presorted_step_random_shapes(case):
                             torch.empty((B, D), device=DEV), usorted, o,
                             item_dup=idup if kind == "sgd" else None)  # plain SGD: K1 also takes item rows referenced once
     torch.cuda.synchronize()
+    if sgd:
+        sens.assert_losses(sgd, losses.cpu().numpy(), tol=STRESS_TOL)
+        sens.criterion_for(sgd)({k: t[k].cpu().numpy() for k in names}, sgd.ref, p)
+        assert err.item() == 0
+        return
     ref = {k: v.copy() for k, v in p.items()}
     r1 = {k: np.zeros_like(v) for k, v in p.items()}
     r2 = {k: np.zeros_like(v) for k, v in p.items()}
