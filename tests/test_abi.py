@@ -112,10 +112,9 @@ def test_ctypes_structs_follow_the_header_member_by_member():
     assert _lib.load().trs_train_steps_sgd(None, None) == -1  # validated on the host, no launch
 
 
-def test_one_launch_step_kernels_keep_four_waves_per_simd(tmp_path):
-    """Register guard on the shipped code objects (no GPU, no recompilation): the one-launch step kernels of the c4 /
-    c2 row shapes (FM, 16-byte lanes, whole rows: 32 or 16 lanes per triple) need at most 128 VGPRs — four waves per
-    SIMD; at 133-135 the same kernel ran 2 us per step slower (profiles/EXPERIMENTS.md) — and no scratch."""
+def _shipped_kernel_registers(tmp_path):
+    """{mangled kernel name: (VGPRs, scratch bytes per lane)} of every gfx950 kernel in the shipped library, read from
+    its code objects' notes (no GPU, no recompilation)."""
     import re
     import shutil
     import subprocess
@@ -145,8 +144,37 @@ def test_one_launch_step_kernels_keep_four_waves_per_simd(tmp_path):
             if name and vg and sc:
                 found[name.group(1)] = (int(vg.group(1)), int(sc.group(1)))
     shutil.rmtree(tmp_path, ignore_errors=True)
+    return found
+
+
+def test_one_launch_step_kernels_keep_four_waves_per_simd(tmp_path):
+    """Register guard on the shipped code objects (no GPU, no recompilation): the one-launch step kernels of the c4 /
+    c2 row shapes (FM, 16-byte lanes, whole rows: 32 or 16 lanes per triple) need at most 128 VGPRs — four waves per
+    SIMD; at 133-135 the same kernel ran 2 us per step slower (profiles/EXPERIMENTS.md) — and no scratch."""
+    import re
+    found = _shipped_kernel_registers(tmp_path)
     hot = {n: v for n, v in found.items()
            if re.search(r"fwd_stage_kernelILi1ELi4ELi(32|16)ELi1ELi0ELb1ELi3ELi0ELi[013]E", n)}
     assert len(hot) == 6, sorted(hot)
     for n, (vgpr, scratch) in hot.items():
         assert vgpr <= 128 and scratch == 0, (n, vgpr, scratch)
+
+
+def test_retrieval_tile_loop_kernels_keep_their_registers(tmp_path):
+    """Register guard for the two kernels that run the shared tile loop of csrc/retrieve.hip: every instance of
+    retrieve_topk_kernel<NQ, SELF> and rank_count_kernel<NQ> has no scratch and at most the VGPRs it had when each
+    kernel carried its own copy of the loop.  rank_count_kernel<2> sits exactly on the
+    128-VGPR line of four waves per SIMD."""
+    import re
+    found = _shipped_kernel_registers(tmp_path)
+    limit = {"retrieve_topk_kernelILi%dELb0E": {2: 188, 4: 195, 8: 211, 16: 245, 32: 256},
+             "retrieve_topk_kernelILi%dELb1E": {2: 188, 4: 195, 8: 211, 16: 243, 32: 256},
+             "rank_count_kernelILi%dEE": {2: 128, 4: 136, 8: 152, 16: 184, 32: 248}}
+    seen = {n: v for n, v in found.items() if re.search(r"\d(retrieve_topk_kernel|rank_count_kernel)I", n)}
+    assert len(seen) == 10 + 5, sorted(seen)
+    for pat, by_nq in limit.items():
+        for nq, most in by_nq.items():
+            hit = [n for n in seen if (pat % nq) in n]
+            assert len(hit) == 1, (pat % nq, hit)
+            vgpr, scratch = seen[hit[0]]
+            assert scratch == 0 and vgpr <= most, (hit[0], vgpr, scratch, most)

@@ -43,8 +43,8 @@ def _rank(m, users, targets, exclude_seen, **kw):
     return np.split(got.numpy(), cuts)
 
 
-CASES = [(1, 0, 333), (7, 0, 333), (16, 2, 333), (100, 0, 333), (256, 0, 333), (7, 1, 1), (7, 1, 127), (7, 1, 128),
-         (7, 1, 129), (7, 1, 100_003)]
+CASES = [(1, 0, 333), (7, 0, 333), (16, 2, 333), (24, 0, 333), (64, 0, 333), (100, 0, 333), (256, 0, 333), (7, 1, 1),
+         (7, 1, 127), (7, 1, 128), (7, 1, 129), (7, 1, 100_003)]
 
 
 @pytest.mark.parametrize("net_type", ["linear", "fm"])

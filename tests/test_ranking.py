@@ -119,7 +119,7 @@ def _users(n_users, n, seed):
     return us
 
 
-CASES = ([(D, 0, 333) for D in (1, 7, 16, 64, 100, 128, 256)] + [(16, M, 333) for M in (1, 3)] +
+CASES = ([(D, 0, 333) for D in (1, 7, 16, 24, 64, 100, 128, 256)] + [(16, M, 333) for M in (1, 3)] +
          [(7, 1, n) for n in (1, 127, 128, 129, 100_003)])
 
 

@@ -39,7 +39,7 @@ def test_symbols_declared_exported_and_bound():
     decl = header[header.index("int trs_item_ranks("):]
     assert decl[:decl.index(")")].count(",") == 12
     assert header.index("trs_item_ranks") > header.index("trs_fold_in_users")  # after the fold-in block
-    # the workspace: a row start per query (+ 1) and a key per target, monotone in both
+    # the workspace: n_q + 1 words that are no longer used (the size is ABI) and a key per target, monotone in both
     ws = lib.trs_item_ranks_workspace_bytes
     assert ws(0, 5) == 0 and ws(3, 0) == 32 and ws(3, 10) == 32 + 80 and ws(4, 10) > ws(3, 10) and ws(3, -1) == 0
 

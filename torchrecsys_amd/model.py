@@ -796,6 +796,36 @@ class TorchRecSys(torch.nn.Module):
         return hasattr(self.net, 'table_params') and k <= ops._lib.RETRIEVE_KMAX and \
             self.n_factors <= ops._lib.RETRIEVE_DMAX
 
+    @staticmethod
+    def _empty_topk(n, k, return_scores):
+        """What recommend() and its kin return when there is no query or k <= 0: (n, max(k, 0)) ids (and scores)."""
+        e = torch.empty((n, max(k, 0)), dtype=torch.int64)
+        return (e, torch.empty(e.shape, dtype=torch.float32)) if return_scores else e
+
+    def _chunked(self, call, queries):
+        """call(chunk) -> tuple of tensors (or None) per RECOMMEND_CHUNK of `queries`: the tuple of concatenations.
+        `queries` is not empty (the callers return _empty_topk first)."""
+        assert queries.numel() > 0
+        outs = [call(queries[s:s + self.RECOMMEND_CHUNK]) for s in range(0, queries.numel(), self.RECOMMEND_CHUNK)]
+        return tuple(None if o[0] is None else torch.cat(o) for o in zip(*outs))
+
+    @staticmethod
+    def _original_ids(ids, index):
+        """Dense ids (CPU tensor, changed in place) -> the caller's ids through `index` (None: the same); -1 stays."""
+        if index is not None:
+            keep = ids >= 0
+            ids[keep] = index.cpu().to(torch.int64)[ids[keep]]
+        return ids
+
+    @staticmethod
+    def _topk_rows(rows, out_rows, k, n_valid):
+        """Tail of the generic paths: ops.topk of each score row, out_rows' values there, and id -1 / score -inf from
+        position n_valid[r] on.  (ids (g, k) int64, scores (g, k) fp32)."""
+        top = torch.stack([ops.topk(rows[r], k) for r in range(rows.shape[0])])
+        sc = torch.gather(out_rows, 1, top)
+        pad = torch.arange(k, device=rows.device)[None, :] >= n_valid[:, None]
+        return torch.where(pad, torch.full_like(top, -1), top), torch.where(pad, torch.full_like(sc, float('-inf')), sc)
+
     def _generic_form(self, dev, meta):
         """What the generic path's score rows rank by: (S, c, table parameters) of the folded form for Linear / FM up to
         TRS_RETRIEVE_DMAX factors; None (the scorer's own score_all_items rows) for the MLP and wider tables."""
@@ -832,18 +862,12 @@ class TorchRecSys(torch.nn.Module):
         if self._fused_retrieval(k):
             T = self.net.tables()
             fold = ops.item_fold(self.net.NET, T, self.n_items, self.n_factors, dev, meta)
-            outs = [ops.retrieve_topk(self.net.NET, T, fold, users[s:s + self.RECOMMEND_CHUNK], k, seen, rel)
-                    for s in range(0, n, self.RECOMMEND_CHUNK)]
-            ids = torch.cat([o[0] for o in outs])
-            scores = torch.cat([o[1] for o in outs])
-            met = torch.cat([o[2] for o in outs]) if rel is not None else None
-            return ids, scores, met
+            return self._chunked(lambda us: ops.retrieve_topk(self.net.NET, T, fold, us, k, seen, rel), users)
         # generic path: existing score rows, seen entries -> -inf, trs_topk, -1 beyond the user's unseen items.
         # Linear / FM rank the rows of the folded form (Linear scores, FM logits z: score_all_items of a Linear scorer
         # over S / c with the users' rows padded to Dp); FM's returned scores are its own sigmoid rows.
         ids = torch.empty((n, k), dtype=torch.int64, device=dev)
         scores = torch.empty((n, k), dtype=torch.float32, device=dev)
-        ar = torch.arange(k, device=dev)
         form = self._generic_form(dev, meta)
         for s in range(0, n, self.GENERIC_CHUNK):
             us = users[s:s + self.GENERIC_CHUNK]
@@ -853,11 +877,7 @@ class TorchRecSys(torch.nn.Module):
                 n_seen = (seen[0][us + 1] - seen[0][us])
             else:
                 n_seen = torch.zeros_like(us)
-            top = torch.stack([ops.topk(rows[r], k) for r in range(rows.shape[0])])
-            pad = ar[None, :] >= (self.n_items - n_seen)[:, None]
-            sc = torch.gather(out_rows, 1, top)
-            ids[s:s + us.numel()] = torch.where(pad, torch.full_like(top, -1), top)
-            scores[s:s + us.numel()] = torch.where(pad, torch.full_like(sc, float('-inf')), sc)
+            ids[s:s + us.numel()], scores[s:s + us.numel()] = self._topk_rows(rows, out_rows, k, self.n_items - n_seen)
         met = ops.rank_metrics(ids, users, rel) if rel is not None and n else None
         return ids, scores, met
 
@@ -876,15 +896,10 @@ class TorchRecSys(torch.nn.Module):
         ulist = user_ids.tolist() if hasattr(user_ids, "tolist") else list(user_ids)
         k = min(int(top_k), self.n_items)
         if k <= 0 or not ulist:
-            e = torch.empty((len(ulist), max(k, 0)), dtype=torch.int64)
-            return (e, torch.empty(e.shape, dtype=torch.float32)) if return_scores else e
+            return self._empty_topk(len(ulist), k, return_scores)
         users = self._dense_users(ulist).to(_device())
         ids, scores, _ = self._rank_dense(users, k, exclude_seen)
-        ids = ids.cpu()
-        idx = getattr(self.data_processor, "item_index", None)
-        if idx is not None:
-            keep = ids >= 0
-            ids[keep] = idx.cpu().to(torch.int64)[ids[keep]]
+        ids = self._original_ids(ids.cpu(), getattr(self.data_processor, "item_index", None))
         return (ids, scores.cpu()) if return_scores else ids
 
     # ------------------------------------------------------------------------------------------------ exact ranks
@@ -1149,23 +1164,16 @@ class TorchRecSys(torch.nn.Module):
         n = rank.size
         k = min(int(top_k), self.n_items)
         if k <= 0 or n == 0:
-            e = torch.empty((n, max(k, 0)), dtype=torch.int64)
-            return (e, torch.empty(e.shape, dtype=torch.float32)) if return_scores else e
+            return self._empty_topk(n, k, return_scores)
         fold, hist, U, b, _ = self._fold_in_dense(off, items, opts, False)
         # a temporary table set whose user side is the folded-in rows: the fused kernel reads nothing else of it
         T, keep = ops.make_tables(U, self.net.item.weight.data, b.view(-1, 1), self.net.table_params()[3].data)
         users = torch.arange(n, dtype=torch.int64, device=U.device)
         seen = hist if exclude_seen and hist[1].numel() else None  # every history empty: nothing to exclude
-        outs = [ops.retrieve_topk(self.net.NET, T, fold, users[s:s + self.RECOMMEND_CHUNK], k, seen)
-                for s in range(0, n, self.RECOMMEND_CHUNK)]
+        ids, scores, _ = self._chunked(lambda us: ops.retrieve_topk(self.net.NET, T, fold, us, k, seen), users)
         r = torch.from_numpy(rank)
-        ids = torch.cat([o[0] for o in outs]).cpu()[r]
-        scores = torch.cat([o[1] for o in outs]).cpu()[r]
-        idx = getattr(self.data_processor, "item_index", None)
-        if idx is not None:
-            good = ids >= 0
-            ids[good] = idx.cpu().to(torch.int64)[ids[good]]
-        return (ids, scores) if return_scores else ids
+        ids = self._original_ids(ids.cpu()[r], getattr(self.data_processor, "item_index", None))
+        return (ids, scores.cpu()[r]) if return_scores else ids
 
     # ------------------------------------------------------------------------------------------------ neighbours
     def _dense_rows(self, ids, index, n_rows, what):
@@ -1200,14 +1208,10 @@ class TorchRecSys(torch.nn.Module):
         qlist = query_ids.tolist() if hasattr(query_ids, "tolist") else list(query_ids)
         k = min(int(top_k), n_rows)
         if k <= 0 or not qlist:
-            e = torch.empty((len(qlist), max(k, 0)), dtype=torch.int64)
-            return (e, torch.empty(e.shape, dtype=torch.float32)) if return_scores else e
+            return self._empty_topk(len(qlist), k, return_scores)
         queries = self._dense_rows(qlist, index, n_rows, what).to(_device())
         ids, scores = self._neighbours_dense(what, queries, k, metric == 'cosine')
-        ids = ids.cpu()
-        if index is not None:
-            keep = ids >= 0
-            ids[keep] = index.cpu().to(torch.int64)[ids[keep]]
+        ids = self._original_ids(ids.cpu(), index)
         return (ids, scores.cpu()) if return_scores else ids
 
     def _neighbours_dense(self, what, queries, k, cosine):
@@ -1223,29 +1227,21 @@ class TorchRecSys(torch.nn.Module):
             n_rows, rows = self.n_items, self.net.item.weight.data
         else:
             n_rows = self.n_items
-            fold = ops.item_fold(self.net.NET, self.net.tables(), n_rows, D, dev, self._item_meta_dev())
-            n_pad = (n_rows + 127) // 128 * 128
-            Dp = fold.numel() // (4 * n_pad) - 1
-            rows = fold.view(torch.float32)[:n_pad * Dp].view(n_pad, Dp)
+            rows = ops.fold_rows(ops.item_fold(self.net.NET, self.net.tables(), n_rows, D, dev, self._item_meta_dev()),
+                                 n_rows)
         nf = ops.neighbour_fold(rows, n_rows, D, cosine)
         if k <= ops._lib.RETRIEVE_KMAX:
-            outs = [ops.neighbours_topk(nf, n_rows, D, queries[s:s + self.RECOMMEND_CHUNK], k)
-                    for s in range(0, n, self.RECOMMEND_CHUNK)]
-            return torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])
+            return self._chunked(lambda qs: ops.neighbours_topk(nf, n_rows, D, qs, k), queries)
         X, zero = ops.fold_views(nf, n_rows, D)
         ids = torch.empty((n, k), dtype=torch.int64, device=dev)
         scores = torch.empty((n, k), dtype=torch.float32, device=dev)
-        pad = (torch.arange(k, device=dev) >= n_rows - 1)[None, :]
         for s in range(0, n, self.GENERIC_CHUNK):
             qs = queries[s:s + self.GENERIC_CHUNK]
             g = qs.numel()
             Tz, keep = ops.make_tables(X[qs].contiguous(), X, zero[:g].view(-1, 1), zero.view(-1, 1))
             sims = torch.stack([ops.score_all_items("linear", Tz, r, n_rows, dev) for r in range(g)])
             sims[torch.arange(g, device=dev), qs] = float('-inf')
-            top = torch.stack([ops.topk(sims[r], k) for r in range(g)])
-            sc = torch.gather(sims, 1, top)
-            ids[s:s + g] = torch.where(pad, torch.full_like(top, -1), top)
-            scores[s:s + g] = torch.where(pad, torch.full_like(sc, float('-inf')), sc)
+            ids[s:s + g], scores[s:s + g] = self._topk_rows(sims, sims, k, torch.full((g,), n_rows - 1, device=dev))
         return ids, scores
 
     @_host_side

@@ -761,12 +761,24 @@ def item_fold(net, T, n_items, D, device, item_meta=None):
     return buf
 
 
-def fold_views(fold, n_items, D):
-    """(S (n_items, Dp) fp32, c (n_items,) fp32) views of a trs_item_fold buffer (layout: include/trs.h)."""
+def fold_rows(fold, n_items):
+    """The padded (n_pad, Dp) fp32 row block of a trs_item_fold buffer (layout: include/trs.h)."""
     n_pad = (n_items + 127) // 128 * 128
     Dp = fold.numel() // (4 * n_pad) - 1
-    f = fold.view(torch.float32)
-    return f[:n_items * Dp].view(n_items, Dp), f[n_pad * Dp:n_pad * Dp + n_items]
+    return fold.view(torch.float32)[:n_pad * Dp].view(n_pad, Dp)
+
+
+def fold_views(fold, n_items, D):
+    """(S (n_items, Dp) fp32, c (n_items,) fp32) views of a trs_item_fold buffer."""
+    S = fold_rows(fold, n_items)
+    return S[:n_items], fold.view(torch.float32)[S.numel():S.numel() + n_items]
+
+
+def _topk_out(n, k, dev):
+    """What a fused top-k call writes: (ids (n, k) int64, scores (n, k) fp32, workspace, workspace bytes)."""
+    ws_bytes = _lib.load().trs_retrieve_workspace_bytes(n, k)
+    return (torch.empty((n, k), dtype=torch.int64, device=dev), torch.empty((n, k), dtype=torch.float32, device=dev),
+            torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev), ws_bytes)
 
 
 def retrieve_topk(net, T, fold, users, k, seen=None, rel=None):
@@ -775,12 +787,8 @@ def retrieve_topk(net, T, fold, users, k, seen=None, rel=None):
     lib = _lib.load()
     _dev(users, "query users", torch.int64)
     n = users.numel()
-    dev = users.device
-    ids = torch.empty((n, k), dtype=torch.int64, device=dev)
-    scores = torch.empty((n, k), dtype=torch.float32, device=dev)
-    met = torch.empty((n, 4), dtype=torch.float64, device=dev) if rel is not None else None
-    ws_bytes = lib.trs_retrieve_workspace_bytes(n, k)
-    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    ids, scores, ws, ws_bytes = _topk_out(n, k, users.device)
+    met = torch.empty((n, 4), dtype=torch.float64, device=users.device) if rel is not None else None
     cs, cr = csr(*seen) if seen is not None else None, csr(*rel) if rel is not None else None
     check(lib.trs_retrieve_topk(NET_ID[net], C.byref(T), ptr(fold), fold.numel(), ptr(users), n, int(k),
                                 C.byref(cs) if cs is not None else None, C.byref(cr) if cr is not None else None,
@@ -808,11 +816,7 @@ def neighbours_topk(fold, n_rows, D, queries, k):
     lib = _lib.load()
     _dev(queries, "query rows", torch.int64)
     n = queries.numel()
-    dev = queries.device
-    ids = torch.empty((n, k), dtype=torch.int64, device=dev)
-    scores = torch.empty((n, k), dtype=torch.float32, device=dev)
-    ws_bytes = lib.trs_retrieve_workspace_bytes(n, k)
-    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    ids, scores, ws, ws_bytes = _topk_out(n, k, queries.device)
     check(lib.trs_neighbours_topk(ptr(fold), fold.numel(), int(n_rows), int(D), ptr(queries), n, int(k), ptr(ids),
                                   ptr(scores), ptr(ws), ws_bytes, _stream()), "trs_neighbours_topk")
     return ids, scores
