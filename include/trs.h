@@ -100,7 +100,7 @@ const char* trs_last_error(void);
  *      trs_mask_seen, trs_rank_metrics.  (Entry points added since without touching an existing signature or struct:
  *      the in-batch softmax group, trs_batch_prepare_mined, trs_batch_prepare_multi, trs_score_multi_fwd_bwd,
  *      trs_score_warp_fwd_bwd, TRS_LOSS_WARP, trs_stage_add_l2, trs_neighbour_fold, trs_neighbours_topk,
- *      trs_fold_in_users, trs_item_ranks, trs_item_ranks_workspace_bytes.) */
+ *      trs_fold_in_users, trs_item_ranks, trs_item_ranks_workspace_bytes, trs_mmr_rerank, trs_list_ild.) */
 #define TRS_ABI_VERSION 6
 #define TRS_SYNC_WORDS 288
 #define TRS_SYNC_REBASE 0x40000000u /* arrivals after which trs_train_steps_sgd zeroes sync_dev and its host count */
@@ -730,6 +730,49 @@ int trs_item_ranks(int net, const trs_tables* tables, const void* fold_dev, int6
                    const int64_t* users_dev, int64_t n_q, const trs_csr* targets, const trs_csr* seen,
                    int64_t* ranks_out_dev, float* values_out_dev, void* workspace_dev, int64_t workspace_bytes,
                    void* stream);
+
+/* ------------------------------------- diversified re-ranking (recommend_diverse / evaluate_diversity) */
+/* Greedy Maximal-Marginal-Relevance (MMR; Carbonell & Goldstein, SIGIR 1998) selection of k entries out of each query's
+ * candidate pool, and the intra-list diversity of given lists.  Added without touching an existing signature or struct.
+ * Inputs per query: a pool of N entries, 1 <= N <= TRS_RETRIEVE_KMAX, in the order trs_retrieve_topk returned them: ids
+ * p_0 .. p_{N-1} (int64; -1 = "no item", which trs_retrieve_topk only writes as a suffix) and their scores v_j (fp32, the
+ * scorer's output units); X, a trs_neighbour_fold buffer of the item side (cosine or dot) of (n_items, D); lambda in
+ * [0, 1].  Pool positions are "entries" below; every operation is a separately rounded fp32 operation.
+ *   valid      entry j is valid iff 0 <= p_j < n_items; n_valid = the number of valid entries.  An id >= n_items (or
+ *              below -1) is never used as an address: the entry is invalid and bit 0 of *err_flag_dev (may be NULL) is set.
+ *   relevance  v_min / v_max = the smallest / largest v over the valid entries (scan in ascending position with < / >
+ *              from the first valid entry); rel_j = (v_j - v_min) / (v_max - v_min), or 0 for all j when v_max == v_min.
+ *              Then, along the valid entries in ascending position, rel_j <- rel_j < rel_prev ? rel_j : rel_prev:
+ *              relevance is non-increasing along the pool, so a last-bit non-monotonicity of the fp32 sigmoid cannot
+ *              reorder what trs_retrieve_topk ordered by the logit.
+ *   sim        sim(x, y) = <X_x, X_y> in fp32; the order of the sum (and whether products are fused into it) is free.
+ *   a, b       a = 1.0f - lambda, b = lambda.
+ *   pick 0     the first valid entry (position 0 of a pool as trs_retrieve_topk writes it), when n_valid > 0.
+ *   pick t>=1  for every unselected valid entry j: pen_j = the largest sim(p_j, p_s) over the selected s (running
+ *              maximum from -inf with >: a NaN similarity is ignored), m_j = a * rel_j - b * pen_j (two products, one
+ *              difference: three roundings).  The pick is the entry with the largest m_j; ties (-0.0 = +0.0) go to the
+ *              lowest position, and a NaN ranks below every number: scan in ascending position, j replaces the best so
+ *              far iff m_j is a number and (the best so far is a NaN or m_j > it).
+ * Outputs for 1 <= k <= N, picks in pick order: ids_out (n_q, k) int64; scores_out (n_q, k) fp32, the picked entries'
+ * original v; pos_out (n_q, k) int32 or NULL, their pool positions.  Positions from min(k, n_valid) on hold -1, -inf and
+ * -1.  lambda = 0 therefore returns the first k valid pool entries in pool order.
+ * One launch, one workgroup per query: the pool's rows are gathered once into registers, each step hands the last pick's
+ * row to every entry through LDS — k * N * Dp multiply-adds per query instead of the N^2 * Dp of a similarity matrix.
+ * Deterministic (no float atomics).
+ * TRS_E_ARG, nothing launched: n_q < 0 (or >= 2^31); N or k outside 1..TRS_RETRIEVE_KMAX; k > N; lambda outside [0, 1] or
+ * not a number; D outside 1..TRS_RETRIEVE_DMAX; n_items < 1; fold_bytes != trs_item_fold_bytes(n_items, D); with n_q > 0 a
+ * NULL nfold / pool_ids / pool_scores / ids_out / scores_out.  n_q == 0: TRS_OK, nothing launched. */
+int trs_mmr_rerank(const void* nfold_dev, int64_t fold_bytes, int64_t n_items, int32_t D, const int64_t* pool_ids_dev,
+                   const float* pool_scores_dev, int64_t n_q, int32_t N, int32_t k, float lambda, int64_t* ids_out_dev,
+                   float* scores_out_dev, int32_t* pos_out_dev, int32_t* err_flag_dev, void* stream);
+/* Intra-list diversity of the lists ids (n_q, k) int64, 1 <= k <= TRS_RETRIEVE_KMAX, over the rows of the same kind of
+ * buffer: ild_out[q] (float64) = the mean over the unordered pairs {x, y} of valid entries (0 <= id < n_items; an entry
+ * counts once per position, also when an id repeats) of 1 - sim(x, y); sim in fp32 as above, 1 - sim and the sum in
+ * float64 in a fixed order; 0.0 with fewer than two valid entries.  An id outside [0, n_items) is never used as an address.
+ * TRS_E_ARG, nothing launched: n_q, k, D, n_items, fold_bytes as above; with n_q > 0 a NULL nfold / ids / ild_out.
+ * n_q == 0: TRS_OK, nothing launched. */
+int trs_list_ild(const void* nfold_dev, int64_t fold_bytes, int64_t n_items, int32_t D, const int64_t* ids_dev,
+                 int64_t n_q, int32_t k, double* ild_out_dev, void* stream);
 
 /* ------------------------------------------------------------------------------- in-batch softmax (fit) */
 /* Training loss of fit(loss='softmax') for the Linear / FM scorers (Yi et al., RecSys 2019).  Batch

@@ -180,6 +180,8 @@ PROTOTYPES = {
     "trs_item_ranks_workspace_bytes": (C.c_int64, [_i64, _i64]),
     "trs_item_ranks": (C.c_int, [C.c_int, _T, _vp, _i64, _vp, _i64, C.POINTER(TrsCsr), C.POINTER(TrsCsr), _vp, _vp, _vp,
                                  _i64, _vp]),
+    "trs_mmr_rerank": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _i32, _i32, _f, _vp, _vp, _vp, _vp, _vp]),
+    "trs_list_ild": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _i64, _i32, _vp, _vp]),
     "trs_mask_seen": (C.c_int, [_vp, _i64, _i64, _vp, C.POINTER(TrsCsr), _vp]),
     "trs_rank_metrics": (C.c_int, [_vp, _i64, _i32, _vp, C.POINTER(TrsCsr), _vp, _vp]),
     "trs_softmax_workspace_bytes": (C.c_int64, [_i64, _i32]),

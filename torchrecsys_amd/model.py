@@ -29,6 +29,7 @@ from .collaborative.fm import FM
 from .collaborative.linear import Linear
 from .dataset.dataset import FastDataLoader, ProcessData, sample_negatives_reference_stream
 from .engine import SparseScorerTrainer
+from .evaluate import diversity as diversity_eval
 from .evaluate import ranks as rank_eval
 from .evaluate.metrics import Metrics
 from .helper.cuda import gpu, host_threads
@@ -852,16 +853,18 @@ class TorchRecSys(torch.nn.Module):
             torch.stack([self.net.score_all_items(int(u), meta) for u in us.tolist()])
         return rows, out_rows
 
-    def _rank_dense(self, users, k, exclude_seen, rel=None):
+    def _rank_dense(self, users, k, exclude_seen, rel=None, fold=None):
         """Top-k of dense users (int64 GPU tensor): (ids (n,k) dense int64 with -1 padding, scores (n,k) fp32, metrics
-        (n,4) float64 or None).  Linear / FM with k <= KMAX: the fused kernel; otherwise score rows + mask + top-k."""
+        (n,4) float64 or None).  Linear / FM with k <= KMAX: the fused kernel; otherwise score rows + mask + top-k.
+        fold: the item fold of the current tables when the caller has built it already (fused path only)."""
         dev = users.device
         seen = self._seen_csr() if exclude_seen else None
         meta = self._item_meta_dev()
         n = users.numel()
         if self._fused_retrieval(k):
             T = self.net.tables()
-            fold = ops.item_fold(self.net.NET, T, self.n_items, self.n_factors, dev, meta)
+            if fold is None:
+                fold = ops.item_fold(self.net.NET, T, self.n_items, self.n_factors, dev, meta)
             return self._chunked(lambda us: ops.retrieve_topk(self.net.NET, T, fold, us, k, seen, rel), users)
         # generic path: existing score rows, seen entries -> -inf, trs_topk, -1 beyond the user's unseen items.
         # Linear / FM rank the rows of the folded form (Linear scores, FM logits z: score_all_items of a Linear scorer
@@ -1269,6 +1272,56 @@ class TorchRecSys(torch.nn.Module):
         5 GB for 10 M users at 128 factors."""
         return self._similar('user', user_ids, top_k, metric, return_scores)
 
+    # ------------------------------------------------------------------------------------------------ diversity
+    def _diverse_dense(self, users, k, pool, lam, cosine, exclude_seen, want_ild=False):
+        """MMR lists of dense users (int64 GPU tensor, not empty): the fused top-`pool` over one item fold, one neighbour
+        fold of the item side (the rows _neighbours_dense uses), trs_mmr_rerank per RECOMMEND_CHUNK.  (ids (n, k) dense
+        int64 with -1 padding, scores (n, k) fp32, per-list intra-list diversity on the cosine fold (n,) float64 or None)."""
+        dev = users.device
+        D = self.n_factors
+        fold = ops.item_fold(self.net.NET, self.net.tables(), self.n_items, D, dev, self._item_meta_dev())
+        pids, pscores, _ = self._rank_dense(users, pool, exclude_seen, fold=fold)
+        rows = self.net.item.weight.data if self.net.n_meta_tables() == 0 else ops.fold_rows(fold, self.n_items)
+        nf = ops.neighbour_fold(rows, self.n_items, D, cosine)
+        step = self.RECOMMEND_CHUNK
+        outs = [ops.mmr_rerank(nf, self.n_items, D, pids[s:s + step], pscores[s:s + step], k, lam)
+                for s in range(0, users.numel(), step)]
+        ids, scores = torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])
+        ild = None
+        if want_ild:
+            nc = nf if cosine else ops.neighbour_fold(rows, self.n_items, D, True)
+            ild = torch.cat([ops.list_ild(nc, self.n_items, D, ids[s:s + step]) for s in range(0, users.numel(), step)])
+        return ids, scores, ild
+
+    @_host_side
+    def recommend_diverse(self, user_ids, top_k: int = 10, diversity: float = 0.3, pool=None, metric: str = 'cosine',
+                          exclude_seen: bool = True, return_scores: bool = False):
+        """recommend() with redundancy traded against relevance inside each list: greedy Maximal-Marginal-Relevance
+        (MMR) selection of top_k items out of each user's `pool` best ones.  Same conventions as recommend(): original
+        ids in and out, an (n, k) int64 CPU tensor, k = min(top_k, n_items), id -1 / score -inf where a user has fewer
+        candidates; with return_scores also the picked items' own (n, k) fp32 scores, in pick order.
+        The first pick is the user's best item; every further pick maximises
+            (1 - diversity) * rel_j  -  diversity * max over the picked s of sim(j, s)
+        with rel the pool's scores scaled to [0, 1] per user and sim the cosine (metric='cosine') or inner product
+        ('dot') of the items' folded rows S_i = item_i + sum_m meta_m(i), the rows similar_items() compares; ties go to
+        the better-ranked item.  diversity=0 returns recommend()'s list, diversity=1 ignores relevance after the first
+        pick.  The rule, operation by operation, is in include/trs.h "diversified re-ranking".
+        pool defaults to min(TRS_RETRIEVE_KMAX, max(4 top_k, 32), n_items); the fused top-k caps it at
+        TRS_RETRIEVE_KMAX = 128.  ValueError: the MLP (no folded rows), n_factors > TRS_RETRIEVE_DMAX, top_k > pool,
+        pool > TRS_RETRIEVE_KMAX, a diversity outside [0, 1], an unknown metric.  Per call one item fold, one
+        normalised copy of it and one selection launch per 65 536 users; under torch.distributed every rank answers
+        from its own replica."""
+        k, pool = diversity_eval.check('recommend_diverse', self.net_type, self.n_factors, self.n_items, top_k,
+                                       diversity, pool, metric, ops._lib.RETRIEVE_KMAX, ops._lib.RETRIEVE_DMAX)
+        self.net = self.net.eval()
+        ulist = user_ids.tolist() if hasattr(user_ids, "tolist") else list(user_ids)
+        if k <= 0 or not ulist:
+            return self._empty_topk(len(ulist), k, return_scores)
+        users = self._dense_users(ulist).to(_device())
+        ids, scores, _ = self._diverse_dense(users, k, pool, float(diversity), metric == 'cosine', exclude_seen)
+        ids = self._original_ids(ids.cpu(), getattr(self.data_processor, "item_index", None))
+        return (ids, scores.cpu()) if return_scores else ids
+
     def _relevance_csr(self, exclude_seen):
         """CSR of the test split's distinct (user, item) pairs over dense users; with exclude_seen without the pairs
         that are also in the train split (this rank's train rows: under dp_partition 'user' all rows of its users)."""
@@ -1330,6 +1383,59 @@ class TorchRecSys(torch.nn.Module):
             value = float(sums[col[metric]] / n) if n else 0.0
             results[f'{metric}@{k}'] = value
             print(f'|--- Testing {metric}@{k}: {value:.4f}')
+        results['n_users'] = n
+        return results
+
+    @_host_side
+    def evaluate_diversity(self, k: int = 10, diversity: float = 0.0, pool=None, metric: str = 'cosine',
+                           exclude_seen: bool = True, users=None):
+        """Beyond-accuracy metrics of the lists of recommend_diverse(top_k=k, diversity=..., pool=..., metric=...) next
+        to their accuracy, for the users evaluate_ranking() evaluates (selected the same way); returns {'ild@k',
+        'coverage@k', 'novelty@k', 'hit_rate@k', 'recall@k', 'ndcg@k', 'n_users'} and prints them as evaluate_ranking()
+        does.  diversity=0 evaluates plain recommend().
+          ild@k      mean over users of the mean of 1 - cosine over the pairs of the list's items (always the cosine of
+                     the folded item rows, whatever `metric` the selection used); 0 for a list with fewer than two items
+          coverage@k |union of the returned items| / n_items
+          novelty@k  mean over users of the mean over the list's items of -log2((c_i + 1) / (n_users + 1)), c_i = the
+                     distinct train users of item i
+          hit_rate@k, recall@k, ndcg@k   evaluate_ranking()'s formulas on the re-ranked lists
+        Per-user values in float64, averaged over the evaluated users in ascending user order (evaluate/diversity.py).
+        Under torch.distributed with more than one rank: ValueError (coverage needs the union over all ranks)."""
+        kk, pool = diversity_eval.check('evaluate_diversity', self.net_type, self.n_factors, self.n_items, k,
+                                        diversity, pool, metric, ops._lib.RETRIEVE_KMAX, ops._lib.RETRIEVE_DMAX)
+        rank, world = tdist.world_info()
+        if world > 1:
+            raise ValueError("evaluate_diversity does not run under data parallelism: coverage@k is the union of the "
+                             "lists over all ranks; evaluate on one rank")
+        self.net = self.net.eval()
+        dev = _device()
+        rel = self._relevance_csr(exclude_seen)
+        if users is None:
+            dense = torch.unique(self.data_processor.test_data['user_id'].to(torch.int64))
+        else:
+            dense = torch.unique(self._dense_users(users))
+        dense = dense.to(dev)
+        dense = dense[(rel[0][dense + 1] - rel[0][dense]) > 0]
+        names = ('ild', 'coverage', 'novelty', 'hit_rate', 'recall', 'ndcg')
+        values = dict.fromkeys(names, 0.0)
+        n = 0
+        if dense.numel() and kk > 0:
+            ids, _, ild = self._diverse_dense(dense, kk, pool, float(diversity), metric == 'cosine', exclude_seen,
+                                              want_ild=True)
+            m = ops.rank_metrics(ids, dense, rel).cpu().numpy()
+            n = m.shape[0]
+            item_users = torch.bincount(self._seen_csr()[1].long(), minlength=self.n_items).cpu().numpy()
+            lists = ids.cpu().numpy()
+            values = {'ild': float(np.sum(ild.cpu().numpy())) / n,
+                      'coverage': diversity_eval.coverage(lists, self.n_items),
+                      'novelty': float(np.sum(diversity_eval.novelty_per_user(lists, item_users, self.n_users))) / n,
+                      'hit_rate': float(np.sum(m[:, 0] >= 1)) / n,
+                      'recall': float(np.sum(m[:, 0] / m[:, 3])) / n,
+                      'ndcg': float(np.sum(m[:, 1] / m[:, 2])) / n}
+        results = {}
+        for name in names:
+            results[f'{name}@{k}'] = values[name]
+            print(f'|--- Testing {name}@{k}: {values[name]:.4f}')
         results['n_users'] = n
         return results
 

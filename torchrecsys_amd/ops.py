@@ -872,6 +872,42 @@ def item_ranks(net, T, fold, users, targets_csr, seen=None, want_values=False):
     return ranks, values
 
 
+def mmr_rerank(nfold, n_items, D, pool_ids, pool_scores, k, lam, want_pos=False, err_flag=None):
+    """Greedy MMR selection of k entries out of each row's candidate pool (trs_mmr_rerank; the rule is in include/trs.h
+    "diversified re-ranking").  nfold: a neighbour_fold buffer of the item side of (n_items, D); pool_ids (n, N) int64
+    dense ids with -1 padding and pool_scores (n, N) fp32, as retrieve_topk returns them; lam = lambda in [0, 1].
+    Returns GPU tensors (ids (n, k) int64, scores (n, k) fp32, pool positions (n, k) int32 or None)."""
+    lib = _lib.load()
+    _dev(nfold, "neighbour fold", torch.uint8)
+    _dev(pool_ids, "pool ids", torch.int64)
+    _dev(pool_scores, "pool scores", torch.float32)
+    if pool_ids.dim() != 2 or pool_scores.shape != pool_ids.shape:
+        raise ValueError(f"pool ids / scores must be two (n, N) matrices, got {tuple(pool_ids.shape)} and "
+                         f"{tuple(pool_scores.shape)}")
+    n, N = pool_ids.shape
+    dev = pool_ids.device
+    ids = torch.empty((n, int(k)), dtype=torch.int64, device=dev)
+    scores = torch.empty((n, int(k)), dtype=torch.float32, device=dev)
+    pos = torch.empty((n, int(k)), dtype=torch.int32, device=dev) if want_pos else None
+    check(lib.trs_mmr_rerank(ptr(nfold), nfold.numel(), int(n_items), int(D), ptr(pool_ids), ptr(pool_scores), n, N,
+                             int(k), float(lam), ptr(ids), ptr(scores), ptr(pos),
+                             ptr(_dev(err_flag, "err_flag", torch.int32)), _stream()), "trs_mmr_rerank")
+    return ids, scores, pos
+
+
+def list_ild(nfold, n_items, D, ids):
+    """Intra-list diversity of the lists ids (n, k) int64 (-1 = none) over a neighbour_fold buffer of (n_items, D): the
+    mean of 1 - similarity over each list's pairs of valid entries (trs_list_ild), float64 (n,) on the GPU."""
+    _dev(nfold, "neighbour fold", torch.uint8)
+    _dev(ids, "list ids", torch.int64)
+    if ids.dim() != 2:
+        raise ValueError(f"ids must be an (n, k) matrix, got {tuple(ids.shape)}")
+    out = torch.empty((ids.shape[0],), dtype=torch.float64, device=ids.device)
+    check(_lib.load().trs_list_ild(ptr(nfold), nfold.numel(), int(n_items), int(D), ptr(ids), ids.shape[0],
+                                   ids.shape[1], ptr(out), _stream()), "trs_list_ild")
+    return out
+
+
 def mask_seen(scores, users, seen):
     """Seen entries of score rows (n, n_items) fp32 -> -inf (trs_mask_seen), in place."""
     _dev(scores, "score rows", torch.float32)
