@@ -75,6 +75,9 @@ struct FastArgs {
   // flagged-first order (trs_epoch_flags_ordered): *nflag = the batch's triples that carry a flagged reference, all of them
   // at its first positions; NULL = any order
   const int32_t* nflag;
+  // INL 3, early mode (launch_fwd_stage fills them from TrsTuning): apply flagged references inside the main loop; count
+  // the references applied in the loop / in the tail into sync[TRS_SYNC_WORDS - 2] / [TRS_SYNC_WORDS - 1]
+  int apply_in_loop, apply_stats;
 };
 
 struct RawIds {   // loads issued, nothing consumed yet
@@ -207,7 +210,7 @@ struct DeferEntry {
 // tables far beyond the Infinity Cache (c4: 5.1 GB) are read and written once per epoch per row; keeping them out leaves
 // the cache to the item table, whose rows do come back (launch_fwd_stage decides by table size).
 template <int NET, int VEC, int G, int K, int SRC, bool FULL, int INL, int OPT = OPT_SGD, int NTU = 0>
-__global__ __launch_bounds__(TRS_BLOCK) void fwd_stage_kernel(const FastArgs a) {
+__global__ __launch_bounds__(TRS_BLOCK, (INL == 3 && VEC == 4 && G >= 4 && K == 1 && FULL) ? 4 : 1) void fwd_stage_kernel(const FastArgs a) {
   constexpr int N = K * VEC;
   constexpr int TPW = TRS_WAVE / G;
   constexpr bool DEFER = INL == 3;
@@ -225,9 +228,12 @@ __global__ __launch_bounds__(TRS_BLOCK) void fwd_stage_kernel(const FastArgs a) 
   const int64_t stride = nwave * TPW;  // triples between two iterations of one lane group
   float loss_acc = 0.f;
 
-#ifdef TRS_K1_STAMPS  // diagnostic build only (tools/k1_stamps.py): s_memrealtime (100 MHz) at four points of every workgroup
-  uint64_t* stamps = reinterpret_cast<uint64_t*>(a.gz) + 4 * (int64_t)blockIdx.x;  // (gz is unused in INL 3)
-  if (INL == 3 && threadIdx.x == 0) stamps[0] = __builtin_amdgcn_s_memrealtime();
+#ifdef TRS_K1_STAMPS  // diagnostic build only (tools/k1_stamps.py): s_memrealtime (100 MHz) at five points of every workgroup
+  uint64_t* stamps = reinterpret_cast<uint64_t*>(a.gz) + 8 * (int64_t)blockIdx.x;  // (gz is unused in INL 3)
+  if (INL == 3 && threadIdx.x == 0) {
+    stamps[0] = __builtin_amdgcn_s_memrealtime();
+    stamps[4] = 0;  // in-loop apply issued by wave 0 (0: it had nothing to apply, or the path is off)
+  }
 #endif
   // Flagged-first batches (a.nflag): every flagged row of the step is read in the launch's first `fi` iterations, so a
   // workgroup counts itself in on the arrival counter as soon as its four waves are past them — mid-loop, with a plain
@@ -259,11 +265,12 @@ __global__ __launch_bounds__(TRS_BLOCK) void fwd_stage_kernel(const FastArgs a) 
   // early mode: a wave lists its flagged references in ITS OWN part of the list (no LDS atomic) and applies them itself
   // right after its last iteration — a wave's loads of the rows it staged come back behind its own stores to the same
   // addresses, so it needs no barrier with the other waves: the look at the arrival counter and the first round of staged
-  // rows are issued behind the last row loads and come back with them.  (Applying them INSIDE the loop, a round per
-  // iteration, was built: the 1 200 waves with something to apply looked at the counter's line once per iteration while
-  // the arrivals were still landing on it — 43 against 33 us per step — and the extra live registers cost a wave per SIMD.)
+  // rows are issued behind the last row loads and come back with them.  (Applying them INSIDE the loop with a look per
+  // iteration was built first: the 1 200 waves with something to apply looked at the counter's line once per iteration
+  // while the arrivals were still landing on it — 43 against 33 us per step — and the extra live registers cost a wave
+  // per SIMD.  The form with ONE late look per wave is `inloop` below.)
   constexpr int CAPW = DEFER_ITERS * TPW * 3, DU = 4, KDD = (N * G + TRS_WAVE - 1) / TRS_WAVE;
-  const int wv = threadIdx.x >> 6;
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (scalar)
   int my_cnt = 0, next_e = 0;
   bool complete = false;
   auto entry_at = [&](int e) -> int { return early ? wv * CAPW + e : wv + NWV * e; };
@@ -301,6 +308,98 @@ __global__ __launch_bounds__(TRS_BLOCK) void fwd_stage_kernel(const FastArgs a) 
   // wave-uniform trip count: the wave's first group decides (its t is the smallest of the wave)
   const int64_t t_first = wave * TPW;
   const int64_t niter = t_first < B ? (B - t_first + stride - 1) / stride : 0;
+  // Early mode, applying INSIDE the loop (a.apply_in_loop, TrsTuning k1_apply_in_loop): the wave's list is final after
+  // iteration fi and every workgroup has counted itself in a few us into the launch, so the wave looks at the arrival
+  // counter ONCE, at the start of phase `ia` = the third from the end of its (even) trip count — behind the stores of
+  // phase ia - 1, in front of phase ia's id and row loads — and only if it counted itself in at least a phase earlier
+  // (fi < ia) and has something to apply.  With the look go the staged rows of a round of DUL references; nothing
+  // consumes them there.  They are consumed behind the reduce of phase ia: that reduce's wait for its rows lets only
+  // the phase's own id and row loads stay in flight (vmcnt counts in order), so it covers the round — no wait of its
+  // own, and one look per wave per launch instead of one per iteration (the form that polled: above).  If the look
+  // found the grid complete the round's atomics go out and the next round is requested, to be applied a phase later:
+  // three rounds, behind phases ia, ia + 1 and ia + 2 = the last.  What is left — more than 3 * DUL references, a
+  // look that did not find the grid complete, a flagged reference listed after the look (err bit 3), waves with too
+  // few iterations (ia <= fi) — goes to the tail from next_e, exactly as without this path.
+  constexpr int DUL = KDD >= 4 ? 1 : 2;  // (a round stays within 4 registers)
+  constexpr bool INLOOP = DEFER && K == 1;  // (the K > 1 shapes have no registers to spare: they keep the tail)
+  // (wave-uniform, and held in scalar registers: the compiler cannot see that niter is the same in every lane, and a
+  // per-lane `ia` would turn the whole in-loop state into vector registers and the branches below into exec masks)
+  const int ia = __builtin_amdgcn_readfirstlane((int)(((niter + 1) & ~(int64_t)1) - 3));
+  const bool inloop = __builtin_amdgcn_readfirstlane(INLOOP && early && a.apply_in_loop != 0 && fi < (int64_t)ia) != 0;
+  float xl[DUL][KDD];
+  uint32_t seen_l = 0;
+  int pend = 0, n_loop = 0;  // references of the round in flight; my_cnt at the look
+  // load_round_l / apply_round_l do what load_round / apply_round do, on rounds of DUL rows.  They are a second pair and
+  // not a parameter of the first because of registers: inside the loop the entry has to sit in scalar registers and the
+  // lane's offsets must not become loop invariants (c4's instantiation: 145 VGPRs with the tail's form used in the
+  // loop, 139 with this one, on the way to 128), while the tail keeps the parent's form so that the code behind the
+  // loop — all of it with the path off — stays what it was.  A change to one pair belongs in the other.
+  auto load_round_l = [&](int e0, int n_mine) {
+    int ln = lane;
+    asm volatile("" : "+v"(ln));  // an opaque copy: this block's address arithmetic is not hoisted out of the loop
+#pragma unroll
+    for (int k = 0; k < DUL; ++k) {
+      const bool has = e0 + k < n_mine;
+      // (the entry is the same in every lane: held in scalar registers, the row's address is scalar base + lane)
+      const uint32_t tw = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_list[has ? wv * CAPW + e0 + k : 0].tw);
+      const int64_t tk = has ? (int64_t)(tw >> 2) : 0;
+      const float* src = ((tw & 3u) == 0 ? a.du : a.ustage) + tk * (int64_t)D;
+#pragma unroll
+      for (int q = 0; q < KDD; ++q) {
+        const int e = q * TRS_WAVE + ln;
+        xl[k][q] = __hip_atomic_load(src + (e < D ? e : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // past L1
+      }
+    }
+  };
+  auto apply_round_l = [&](int e0, int n_mine) {
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+#pragma unroll
+    for (int k = 0; k < DUL; ++k) {
+      if (e0 + k >= n_mine) continue;  // (wave-uniform)
+      const DeferEntry ev = s_list[wv * CAPW + e0 + k];
+      const int which = __builtin_amdgcn_readfirstlane((int)(ev.tw & 3u));
+      const int row = __builtin_amdgcn_readfirstlane(ev.row);
+      const float c = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(ev.c)));
+      const float clin = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(ev.clin)));
+      float* dst = (which == 0 ? T.user : T.item) + (int64_t)row * D;
+#pragma unroll
+      for (int q = 0; q < KDD; ++q) {
+        const int e = q * TRS_WAVE + ln;
+        if (e < D) atomicAdd(dst + e, c * xl[k][q]);
+      }
+      if (ln == 0) atomicAdd((which == 0 ? T.user_lin : T.item_lin) + row, clin);
+    }
+  };
+  // behind phase ia - 1 = in front of phase ia's loads: nothing is consumed here
+  auto look = [&](int ph) {
+    if (INLOOP && inloop && ph == ia && __builtin_amdgcn_readfirstlane(my_cnt) > 0) {
+      seen_l = __hip_atomic_load(a.sync, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      n_loop = __builtin_amdgcn_readfirstlane(my_cnt);
+      load_round_l(0, n_loop);
+      pend = n_loop < DUL ? n_loop : DUL;
+#ifdef TRS_K1_STAMPS
+      if (threadIdx.x == 0) stamps[4] = __builtin_amdgcn_s_memrealtime();
+#endif
+    }
+  };
+  // behind the reduce of phases ia, ia + 1, ia + 2: the round issued one phase ago
+  auto consume = [&](int ph, int nph) {
+    if (INLOOP && pend > 0) {
+      if (next_e == 0) complete = (int32_t)((uint32_t)__builtin_amdgcn_readfirstlane((int)seen_l) - a.sync_target) >= 0;
+      if (complete) {  // every workgroup of the launch is past its flagged triples: nobody reads these rows any more
+        apply_round_l(next_e, n_loop);
+        next_e += pend;
+        pend = 0;
+        if (next_e < n_loop && ph + 1 < nph) {
+          load_round_l(next_e, n_loop);
+          pend = n_loop - next_e < DUL ? n_loop - next_e : DUL;
+        }
+      } else {
+        pend = 0;
+      }
+    }
+  };
 
   // Reduce one triple whose rows are in registers and write its staging (stores only: no waits on loads in flight).
   auto reduce = [&](TripleRows<VEC, K>& r, const TripleIds& id, int64_t tt) {
@@ -446,23 +545,30 @@ __global__ __launch_bounds__(TRS_BLOCK) void fwd_stage_kernel(const FastArgs a) 
   // (INL 3: handing the workgroup's (iteration, wave) chunks out dynamically through an LDS counter was built and
   // measured: no change — the launch's slow tail is whole workgroups on slower XCDs / CUs, not single waves)
   const int64_t niter2 = (niter + 1) & ~(int64_t)1;  // even trip count: surplus phases run on clamped, invalid triples
+  const int nph = __builtin_amdgcn_readfirstlane((int)niter2);
+  // (INL 3: issuing these two in front of the *a.nflag read and the barrier, so that nflag's HBM miss runs beside them,
+  // was measured by itself: 31.70-32.08 against 32.00-32.06 us per step, no difference — not kept)
   RawIds wE = issue_ids<SRC, INL>(a, t);
   RawIds wO = issue_ids<SRC, INL>(a, t + stride);
   idE = finalize_ids<SRC>(a, wE);
   load_rows<VEC, G, K, FULL, OPT, NTU>(rE, T, a.o, idE, lig);
   if (DEFER && early && fi == 0) arrive();
-  for (int64_t it = 0; it < niter2; it += 2) {
+  const int64_t nloop = DEFER ? (int64_t)nph : niter2;  // (INL 3: a scalar trip count, so the loop counter is scalar too)
+  for (int64_t it = 0; it < nloop; it += 2) {
     wE = issue_ids<SRC, INL>(a, t + 2 * stride);
     idO = finalize_ids<SRC>(a, wO);
     load_rows<VEC, G, K, FULL, OPT, NTU>(rO, T, a.o, idO, lig);
     reduce(rE, idE, t);
     if (DEFER && early && it + 1 == fi) arrive();  // (the rows already in flight belong to triples without a flagged reference)
+    consume((int)it, nph);
+    look((int)it + 1);  // (ia is odd: the phase that follows may be phase ia)
 
     wO = issue_ids<SRC, INL>(a, t + 3 * stride);
     idE = finalize_ids<SRC>(a, wE);
     load_rows<VEC, G, K, FULL, OPT, NTU>(rE, T, a.o, idE, lig);
     reduce(rO, idO, t + stride);
     if (DEFER && early && it + 2 == fi) arrive();
+    consume((int)it + 1, nph);
     t += 2 * stride;
   }
   if (DEFER && early && !arrived) arrive();  // a wave with fewer iterations than fi (the batch's tail)
@@ -473,15 +579,16 @@ __global__ __launch_bounds__(TRS_BLOCK) void fwd_stage_kernel(const FastArgs a) 
   __shared__ float s_loss[TRS_BLOCK / TRS_WAVE];
   const float wl = trs_wave_sum(loss_acc);
   if (lane == 0) s_loss[threadIdx.x >> 6] = wl;
-  if (DEFER && early && my_cnt > 0) {  // (wave-uniform)
+  const int n_in_loop = next_e;  // (K1_APPLY_STATS)
+  if (DEFER && early && my_cnt > next_e) {  // (wave-uniform) what the loop has not applied: everything, without the in-loop path
     float x[DU][KDD];
     const uint32_t seen = __hip_atomic_load(a.sync, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    load_round(x, 0, my_cnt);
+    load_round(x, next_e, my_cnt);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     complete = (int32_t)((uint32_t)__builtin_amdgcn_readfirstlane((int)seen) - a.sync_target) >= 0;
     if (complete) {  // every workgroup of the launch is past its flagged triples: nobody reads these rows any more
-      apply_round(x, 0, my_cnt);
-      for (int e0 = DU; e0 < my_cnt; e0 += DU) {
+      apply_round(x, next_e, my_cnt);
+      for (int e0 = next_e + DU; e0 < my_cnt; e0 += DU) {
         load_round(x, e0, my_cnt);
         apply_round(x, e0, my_cnt);
       }
@@ -508,6 +615,13 @@ __global__ __launch_bounds__(TRS_BLOCK) void fwd_stage_kernel(const FastArgs a) 
     const int total = s_total;
     const int n_mine = early ? my_cnt : (total > wv ? (total - wv + NWV - 1) / NWV : 0);
     const int e_first = early ? next_e : 0;
+    // K1_APPLY_STATS (tests): every reference of the wave's list is applied exactly once, in the loop or behind it
+    if (a.apply_stats && lane == 0) {
+      uint32_t* st = a.sync + (TRS_SYNC_WORDS - 2);
+      if (n_in_loop) (void)__hip_atomic_fetch_add(st, (uint32_t)n_in_loop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (n_mine > n_in_loop)
+        (void)__hip_atomic_fetch_add(st + 1, (uint32_t)(n_mine - n_in_loop), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
 #ifdef TRS_K1_STAMPS
     if (early && !s_left && threadIdx.x == 0) stamps[2] = stamps[3] = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -1389,6 +1503,8 @@ static int launch_fwd_stage(const FastArgs& a, hipStream_t s, uint32_t* deferred
         if (grid <= cap) {
           FastArgs b = a;
           b.sync_target = a.sync_base + (uint32_t)grid;
+          b.apply_in_loop = trs_tuning().k1_apply_in_loop != 0;
+          b.apply_stats = trs_tuning().k1_apply_stats != 0;
           if (ntu == 1)
             hipLaunchKernelGGL((fwd_stage_kernel<NET, VV, GG, KK, 0, FU, 3, OPT_SGD, 1>), gr, bl, 0, s, b);
           else if (ntu == 3)
