@@ -354,7 +354,8 @@ int trs_score_backward(int net, const trs_tables* tables, const trs_batch* batch
 #define TRS_OPT_ADAGRAD 2
 typedef struct trs_opt {
   int32_t kind;
-  float lr, beta1, beta2, eps, lr_decay;
+  float lr, beta1, beta2, eps, lr_decay; /* read as the decimals they were written as: 1 - beta and each step's step
+                                            size are formed in double from them, as torch does from its Python floats */
   int64_t step0;       /* optimiser step count before the first step of the call (same for the four tables) */
   float *user_s1, *user_s2, *item_s1, *item_s2;                 /* exp_avg | sum, exp_avg_sq | NULL        (n, D) */
   float *user_lin_s1, *user_lin_s2, *item_lin_s1, *item_lin_s2; /* the same for the 1-wide tables          (n, 1) */

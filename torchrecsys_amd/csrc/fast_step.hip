@@ -1795,6 +1795,9 @@ extern "C" int trs_train_steps_sgd(const trs_train_args* args, void* stream) {
     if (sorted) a.iown = nullptr;  // K1 marks users only
   }
   const int item_bits = trs_item_bits_for(tables->n_items);
+  // the rule's hyper-parameters as the doubles torch.optim holds (trs_common.h)
+  const double lr_w = adaptive ? trs_as_written(opt->lr) : 0.0, decay_w = adaptive ? trs_as_written(opt->lr_decay) : 0.0;
+  const double b1_w = adaptive ? trs_as_written(opt->beta1) : 0.0, b2_w = adaptive ? trs_as_written(opt->beta2) : 0.0;
   for (int32_t st = 0; st < n_steps; ++st) {
     a.t0 = first_pos + (int64_t)st * batch;
     a.sample_offset = (uint64_t)a.t0;
@@ -1825,10 +1828,10 @@ extern "C" int trs_train_steps_sgd(const trs_train_args* args, void* stream) {
       OptArgs& o = a.o;
       const double t = (double)(opt->step0 + st + 1);
       o.kind = opt->kind == TRS_OPT_SPARSE_ADAM ? OPT_ADAM : OPT_ADAGRAD;
-      o.beta1 = opt->beta1; o.beta2 = opt->beta2; o.eps = opt->eps;
+      o.omb1 = (float)(1.0 - b1_w); o.omb2 = (float)(1.0 - b2_w); o.eps = opt->eps;
       o.lr_eff = o.kind == OPT_ADAM
-                     ? (float)((double)opt->lr * sqrt(1.0 - pow((double)opt->beta2, t)) / (1.0 - pow((double)opt->beta1, t)))
-                     : (float)((double)opt->lr / (1.0 + (t - 1.0) * (double)opt->lr_decay));
+                     ? (float)(lr_w * sqrt(1.0 - pow(b2_w, t)) / (1.0 - pow(b1_w, t)))
+                     : (float)(lr_w / (1.0 + (t - 1.0) * decay_w));
       o.user_s1 = opt->user_s1; o.user_s2 = opt->user_s2; o.item_s1 = opt->item_s1; o.item_s2 = opt->item_s2;
       o.user_lin_s1 = opt->user_lin_s1; o.user_lin_s2 = opt->user_lin_s2;
       o.item_lin_s1 = opt->item_lin_s1; o.item_lin_s2 = opt->item_lin_s2;

@@ -16,7 +16,7 @@ enum { OPT_SGD = 0, OPT_ADAM = 1, OPT_ADAGRAD = 2 };
 struct OptArgs {
   int kind;
   float lr_eff;  // SGD: lr; ADAM: step_size of this step; ADAGRAD: clr of this step
-  float beta1, beta2, eps;
+  float omb1, omb2, eps;  // ADAM: 1 - beta1, 1 - beta2, formed in double on the host and rounded once (as torch does)
   // optimiser state, same shapes as the weight tables: s1 = exp_avg | sum, s2 = exp_avg_sq | unused
   float *user_s1, *user_s2, *item_s1, *item_s2;
   float *user_lin_s1, *user_lin_s2, *item_lin_s1, *item_lin_s2;
@@ -33,8 +33,8 @@ template <int OPT>
 __device__ __forceinline__ float opt_apply(float w, float g, float& s1, float& s2, const OptArgs& o) {
   if (OPT == OPT_ADAM) {
     const float m0 = s1, v0 = s2;
-    const float dm = (g - m0) * (1.0f - o.beta1);
-    const float dv = (g * g - v0) * (1.0f - o.beta2);
+    const float dm = (g - m0) * o.omb1;
+    const float dv = (g * g - v0) * o.omb2;
     s1 = m0 + dm;
     s2 = v0 + dv;
     const float numer = dm + m0;

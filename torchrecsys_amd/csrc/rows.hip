@@ -138,7 +138,7 @@ struct ApplyArgs {
   int64_t n;
   int32_t step_id;
   float lr_eff;  // SparseAdam: lr*sqrt(1-b2^t)/(1-b1^t); Adagrad: clr
-  float beta1, beta2, eps;
+  float omb1, omb2, eps;  // SparseAdam: 1 - beta1, 1 - beta2, formed in double on the host and rounded once
 };
 
 template <int LPR, int MODE>
@@ -167,8 +167,8 @@ __global__ __launch_bounds__(TRS_BLOCK) void rows_apply_kernel(const ApplyArgs a
       float w = a.table[base + d];
       if (MODE == 0) {
         const float m0 = a.s1[base + d], v0 = a.s2[base + d];
-        const float dm = (g - m0) * (1.0f - a.beta1);
-        const float dv = (g * g - v0) * (1.0f - a.beta2);
+        const float dm = (g - m0) * a.omb1;
+        const float dv = (g * g - v0) * a.omb2;
         a.s1[base + d] = m0 + dm;
         a.s2[base + d] = v0 + dv;
         const float numer = dm + m0;
@@ -290,10 +290,11 @@ extern "C" int trs_rows_apply_sparse_adam(float* table_dev, float* acc_dev, floa
   TRS_REQUIRE(step_count >= 1, "trs_rows_apply_sparse_adam: step_count must be >= 1");
   if (n == 0) return TRS_OK;
   // step_size = lr * sqrt(1 - beta2^t) / (1 - beta1^t), evaluated in double like the Python floats of torch
-  const double bc1 = 1.0 - pow((double)beta1, (double)step_count);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step_count);
+  const double b1_w = trs_as_written(beta1), b2_w = trs_as_written(beta2);  // (trs_common.h)
+  const double bc1 = 1.0 - pow(b1_w, (double)step_count);
+  const double bc2 = 1.0 - pow(b2_w, (double)step_count);
   ApplyArgs a = {table_dev, acc_dev, exp_avg_dev, exp_avg_sq_dev, stamp_dev, n_rows, D, idx_dev, idx_bytes, n,
-                 step_id, (float)((double)lr * sqrt(bc2) / bc1), beta1, beta2, eps};
+                 step_id, (float)(trs_as_written(lr) * sqrt(bc2) / bc1), (float)(1.0 - b1_w), (float)(1.0 - b2_w), eps};
   dispatch_apply<0>(a, (hipStream_t)stream);
   TRS_CHECK_LAUNCH("rows_apply_kernel<adam>");
   return TRS_OK;

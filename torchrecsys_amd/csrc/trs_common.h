@@ -38,6 +38,21 @@ void trs_set_error(const char* fmt, ...);
     }                                                                      \
   } while (0)
 
+// ------------------------------------------------------------------------------------------ hyper-parameters
+// The C ABI carries an optimiser's hyper-parameters as floats; torch.optim holds them as Python floats (doubles) and
+// forms 1 - beta, lr * sqrt(1 - beta2^t) / (1 - beta1^t) and lr / (1 + (t - 1) lr_decay) in double BEFORE rounding to
+// fp32.  1.0f - (float)0.999 is 1.3e-5 off (float)(1 - 0.999), which exp_avg_sq shows after a handful of steps.  The
+// double is recovered as the shortest decimal that rounds to the given float (0.999f -> 0.999): exact for every value
+// written with up to 7 significant digits, and within one fp32 step of the caller's double otherwise (as the float is).
+static inline double trs_as_written(float x) {
+  char buf[40];
+  for (int digits = 1; digits <= 9; ++digits) {
+    snprintf(buf, sizeof buf, "%.*g", digits, (double)x);
+    if (strtof(buf, nullptr) == x) return strtod(buf, nullptr);
+  }
+  return (double)x;
+}
+
 // Tuning / A-B knobs of the launch paths (kernel selection, launch shapes).  The defaults are the measured best; nothing
 // in the product path needs them.  Read from the TRS_* environment ONCE, when the library is first used (api.cpp) — no
 // launch path calls getenv — and changeable afterwards through trs_tuning_set (include/trs.h: tests, tools/).
