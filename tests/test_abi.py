@@ -178,3 +178,20 @@ def test_retrieval_tile_loop_kernels_keep_their_registers(tmp_path):
             assert len(hit) == 1, (pat % nq, hit)
             vgpr, scratch = seen[hit[0]]
             assert scratch == 0 and vgpr <= most, (hit[0], vgpr, scratch, most)
+
+
+def test_staged_gradient_kernels_keep_their_waves_per_simd(tmp_path):
+    """Register guard for the kernels that stage gradients through the shared pieces of csrc/score_kernels.h (DESIGN.md
+    4.1): every instance of score_kernel (MODE 2 lives in fast_step.hip's code object), multineg_kernel and warp_kernel
+    in the shipped library has no scratch and at least the waves per SIMD it had when each kernel carried its own copy
+    of the slot stager, the loss reduction and the row head.  tests/staged_kernel_waves.json holds those classes per
+    instance, read by _shipped_kernel_registers from the library built before the pieces were shared."""
+    import json
+    import re
+    found = _shipped_kernel_registers(tmp_path)
+    before = json.load(open(os.path.join(ROOT, "tests", "staged_kernel_waves.json")))
+    seen = {n: v for n, v in found.items() if re.search(r"\d(multineg_kernel|warp_kernel|score_kernel)I", n)}
+    assert sorted(seen) == sorted(before) and len(seen) == 96 + 48 + 72
+    for n, (vgpr, scratch) in seen.items():
+        waves = min(8, 512 // (8 * -(-vgpr // 8)))  # 512 VGPRs per lane and SIMD, allocated in blocks of 8
+        assert scratch == 0 and waves >= before[n], (n, vgpr, scratch, waves, before[n])

@@ -14,6 +14,7 @@ import torch
 
 import mining_ref
 import multineg_ref
+import row_shapes
 from conftest import rel_err
 from oracle import optim as ooptim
 
@@ -236,11 +237,14 @@ def test_mean_of_k_pairs_matches_k_calls_of_the_pair_kernel(net_type, M, D, K, B
 
 
 @pytest.mark.parametrize("loss", ["hinge", "bpr"])
-@pytest.mark.parametrize("net_type,M,D", [("fm", 0, 64), ("fm", 2, 20), ("linear", 0, 33), ("linear", 2, 128)])
+@pytest.mark.parametrize("D", row_shapes.ALL)
+@pytest.mark.parametrize("M", [0, 2])
+@pytest.mark.parametrize("net_type", ["linear", "fm"])
 def test_one_negative_is_the_pair_kernel_bit_for_bit(net_type, M, D, loss, tune):
-    """K = 1: the staged blocks, the loss and the AUC count of trs_score_fwd_bwd, bit for bit.  One workgroup walks the
-    whole batch in both kernels (GRID_CAP = 1), so the loss sums see their terms in the same order; with more workgroups
-    the order of their atomic adds is not fixed in either kernel."""
+    """K = 1: the staged blocks, the loss and the AUC count of trs_score_fwd_bwd, bit for bit, at every row shape's
+    ragged and largest width (both kernels write item slots through stage_item_slot of csrc/score_kernels.h).  One
+    workgroup walks the whole batch in both kernels (GRID_CAP = 1), so the loss sums see their terms in the same order;
+    with more workgroups the order of their atomic adds is not fixed in either kernel."""
     tune(GRID_CAP=1)
     NU, NI, B, K = 50, 60, 257, 1
     net, item_meta = build_net(net_type, M, NU, NI, D, D)

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import row_shapes
 import warp_ref
 from conftest import rel_err
 from oracle import optim as ooptim
@@ -297,10 +298,12 @@ def test_out_of_range_id_sets_the_flag_and_is_not_used_as_an_address(net_type, M
 
 
 # ------------------------------------------------------------------------------------------ 5. K = 1
-@pytest.mark.parametrize("M,D", [(0, 33), (2, 128), (0, 64)])
+@pytest.mark.parametrize("D", row_shapes.ALL)
+@pytest.mark.parametrize("M", [0, 2])
 def test_one_candidate_with_unit_weight_is_the_linear_hinge(M, D):
-    """K = 1, Linear (its hinge is on the score itself), rank_weight = [1], margin 1: trials in {0, 1}, the negative is
-    c_0, and the staged gradients are trs_score_fwd_bwd's hinge gradients at 1e-5."""
+    """K = 1, Linear (its hinge is on the score itself), rank_weight = [1], margin 1, at every row shape's ragged and
+    largest width: trials in {0, 1}, the negative is c_0, and the staged gradients are trs_score_fwd_bwd's hinge
+    gradients at 1e-5."""
     ops = _ops()
     from torchrecsys_amd import _lib
     NU, NI, B = 50, 60, 257

@@ -4,22 +4,25 @@
 // prepare_multi_kernel: integer work only — one thread per (candidate j, row t), rows along the lanes, so the slot-major
 // (1+K, B) id block is written in whole lines; the threads of candidate 0 also write the user and the positive.
 //
-// multineg_kernel (wave = 64): one aligned group of G lanes per row, 16-byte lanes, as score_kernel.  The user row and
-// its 1-wide term are loaded once and stay in registers.  Candidates go in rounds of C = min(G, 8, 16 / floats per lane) (slots past the last
-// candidate load it again: loads stay unconditional): lane c of the group reads candidate r0 + c's id, a shuffle hands
-// every id to the whole group, and the C item rows (+ 1-wide terms, + metadata rows) are independent unconditional
-// loads, all in flight before the first reduction (mine_kernel's pattern).  Every z is pass_forward_z's.
+// The two candidate kernels, multineg_kernel and warp_kernel (wave = 64), share their mapping and the parts written
+// once below: one aligned group of G lanes per row, 16-byte lanes, as score_kernel; cand_row_head checks the row's ids
+// and leaves the user row, its 1-wide term and the positive's pass in registers; candidates go in rounds of C =
+// cand_round() (round_forward: C independent unconditional passes in flight before the first reduction, mine_kernel's
+// pattern; slots past the last candidate load it again).  Every z is pass_forward_z's.  Gradients are staged — item
+// slots through stage_item_slot in the layout of staged_item_field / staged_meta_field (score_kernels.h) —, never added
+// to a table here: every gradient of a step comes from the pre-update tables.  No LDS (but block_add_loss_auc), no
+// scratch memory.  What is each kernel's own:
+//
+// multineg_kernel (S = 1 + K item slots)
 //   pair losses     one sweep: candidate j's weight needs only its own score and the positive's; the user row's
 //                   gradient and the positive's weight are accumulated and written after the sweep.
 //   sampled softmax every zh before any weight: sweep 1 keeps the running (maximum, sum of exponentials) of the row.
 //                   K <= C: the single round's rows are still in registers and the gradients follow at once.
 //                   Otherwise sweep 2 re-reads the rows (L2-hot), recomputes each z — bit-identical, the same code on
 //                   the same tables — and stages the gradients.  Forward-only mode stops after sweep 1.
-// Gradients are staged, never added to a table here: every gradient of a step comes from the pre-update tables.  No LDS
-// (but the block's loss reduction), no scratch memory.
 //
-// warp_kernel (trs_score_warp_fwd_bwd): the same mapping and round_forward for the WARP loss — the
-// first candidate that violates the margin is trained on alone, weighted by a rank estimate; described above the kernel.
+// warp_kernel (trs_score_warp_fwd_bwd; S = 2, the pair layout): the first candidate that violates the
+// margin is trained on alone, weighted by a rank estimate; described above the kernel.
 #include "score_kernels.h"
 
 using namespace trs;
@@ -95,9 +98,56 @@ struct MultiArgs {
   int32_t* err;
 };
 
+// ---------------------------------------------------------------------- what the two candidate kernels share
+// (A: MultiArgs or WarpArgs — the id blocks, B, Kn, err and the tables are named alike)
+
+// Candidates per round (a power of two): at most 8, the lane group, and MULTI_ROW_VGPRS of item rows in flight.
+template <int VEC, int G, int K>
+constexpr int cand_round() {
+  constexpr int CR = MULTI_ROW_VGPRS / (K * VEC) < 8 ? (MULTI_ROW_VGPRS / (K * VEC) < 1 ? 1 : MULTI_ROW_VGPRS / (K * VEC)) : 8;
+  return G < CR ? G : CR;
+}
+
+// The head of a row: every id of the row against its table first (integer work, spread over the group) — a row with
+// an id out of range sets the error flag and carries no loss and zero gradients (live = false), as score_kernel's dead
+// triples —, then the user row with its 1-wide term and the positive's pass (z0; sp = pass_forward's score).
+template <int NET, int VEC, int G, int K, typename A>
+__device__ __forceinline__ void cand_row_head(const A& a, int M, int64_t tc, bool valid, int lig, bool& live,
+                                              RowReg<VEC, K>& ur, float& u_lin, RowReg<VEC, K>& pr,
+                                              RowReg<VEC, K>& Sp, float& z0, float& sp) {
+  const trs_tables& T = a.T;
+  int64_t uid = a.user[tc];
+  int bad = 0;
+  if ((uint64_t)uid >= (uint64_t)T.n_users) { bad = 1; uid = 0; }
+  for (int s = lig; s < 1 + a.Kn; s += G) {
+    const int64_t e = (int64_t)s * a.B + tc;
+    if ((uint64_t)(int64_t)a.items[e] >= (uint64_t)T.n_items) bad = 1;
+    for (int m = 0; m < M; ++m)
+      if ((uint64_t)(int64_t)a.meta[e * M + m] >= (uint64_t)T.n_meta[m]) bad = 1;
+  }
+  bad = trs_group_or<G>(bad);
+  if (valid && bad && lig == 0 && a.err) atomicOr(a.err, 1);
+  live = valid && !bad;
+
+  row_load<VEC, G, K>(ur, T.user, uid, T.D, lig);
+  u_lin = T.user_lin[uid];
+  int64_t pid = a.items[tc];
+  if ((uint64_t)pid >= (uint64_t)T.n_items) pid = 0;
+  float p_lin, lin_p;
+  bool okp = true;
+  z0 = pass_forward_z<NET, VEC, G, K>(T, ur, u_lin, pid, a.meta, 4, tc, true, lig, pr, Sp, p_lin, lin_p, okp);
+  sp = NET == TRS_NET_FM ? sigmoidf_(z0) : z0;
+}
+
+// The metadata ids of row t's item slot `slot` (0 the positive, 1 + j candidate j) in the (1+K, B, M) block, as
+// stage_item_slot takes them.
+template <typename A>
+__device__ __forceinline__ auto slot_meta_ids(const A& a, int M, int slot, int64_t t) {
+  return [&a, M, slot, t](int m) -> int64_t { return a.meta[((int64_t)slot * a.B + t) * M + m]; };
+}
+
 // The forward part of one round: the ids of candidates r0 .. r0 + C - 1 (lane c of the group reads candidate r0 + c's,
 // a shuffle hands them round) and their C independent passes.
-// (A: MultiArgs or WarpArgs — the id blocks, B, Kn and the tables are named alike)
 template <int NET, int VEC, int G, int K, int C, typename A>
 __device__ __forceinline__ void round_forward(const A& a, const RowReg<VEC, K>& ur, float u_lin, int r0,
                                               int64_t tc, int lig, int gbase, RowReg<VEC, K> (&ir)[C],
@@ -123,15 +173,14 @@ __device__ __forceinline__ void round_forward(const A& a, const RowReg<VEC, K>& 
 template <int NET, int VEC, int G, int K, bool SM, bool META>
 __global__ __launch_bounds__(TRS_BLOCK) void multineg_kernel(const MultiArgs a) {
   constexpr int N = K * VEC;
-  constexpr int CR = MULTI_ROW_VGPRS / N < 8 ? (MULTI_ROW_VGPRS / N < 1 ? 1 : MULTI_ROW_VGPRS / N) : 8;  // candidate rows in flight
-  constexpr int C = G < CR ? G : CR;           // candidates per round (a power of two)
-  constexpr int TPW = TRS_WAVE / G;            // rows per wave per iteration
+  constexpr int C = cand_round<VEC, G, K>();
+  constexpr int TPW = TRS_WAVE / G;  // rows per wave per iteration
   const trs_tables& T = a.T;
   const int D = T.D;
   const int M = META ? T.M : 0;
   const int64_t B = a.B;
   const int Kn = a.Kn;
-  const int S1 = 1 + Kn;
+  const int S1 = 1 + Kn;  // item slots of the staged layout: the positive, then candidate j in slot 1 + j
   const int lane = threadIdx.x & 63;
   const int lig = lane % G;
   const int gbase = lane - lig;
@@ -140,7 +189,6 @@ __global__ __launch_bounds__(TRS_BLOCK) void multineg_kernel(const MultiArgs a) 
   const bool grad = a.grad_rows != nullptr;
   const float invK = 1.0f / (float)Kn;
   const float wK = a.inv_B * invK;  // weight of one pair of the mean over B rows and K pairs
-  const int64_t BD = B * (int64_t)D;
   float* const gr = a.grad_rows;
   float* const gl = a.grad_lin;
 
@@ -153,31 +201,10 @@ __global__ __launch_bounds__(TRS_BLOCK) void multineg_kernel(const MultiArgs a) 
     const bool valid = t < B;
     const int64_t tc = valid ? t : 0;  // loads stay unconditional
 
-    // every id of the row against its table first (integer work, spread over the group): a row with an id out of range
-    // carries no loss and zero gradients, as score_kernel's dead triples
-    int64_t uid = a.user[tc];
-    int bad = 0;
-    if ((uint64_t)uid >= (uint64_t)T.n_users) { bad = 1; uid = 0; }
-    for (int s = lig; s < S1; s += G) {
-      const int64_t e = (int64_t)s * B + tc;
-      if ((uint64_t)(int64_t)a.items[e] >= (uint64_t)T.n_items) bad = 1;
-      for (int m = 0; m < M; ++m)
-        if ((uint64_t)(int64_t)a.meta[e * M + m] >= (uint64_t)T.n_meta[m]) bad = 1;
-    }
-    bad = trs_group_or<G>(bad);
-    if (valid && bad && lig == 0 && a.err) atomicOr(a.err, 1);
-    const bool live = valid && !bad;
-
-    RowReg<VEC, K> ur;
-    row_load<VEC, G, K>(ur, T.user, uid, D, lig);
-    const float u_lin = T.user_lin[uid];
-    int64_t pid = a.items[tc];
-    if ((uint64_t)pid >= (uint64_t)T.n_items) pid = 0;
-    RowReg<VEC, K> pr, Sp;
-    float p_lin, lin_p;
-    bool okp = true;
-    const float z0 = pass_forward_z<NET, VEC, G, K>(T, ur, u_lin, pid, a.meta, 4, tc, true, lig, pr, Sp, p_lin, lin_p, okp);
-    const float sp = NET == TRS_NET_FM ? sigmoidf_(z0) : z0;  // = pass_forward's score
+    bool live;
+    RowReg<VEC, K> ur, pr, Sp;
+    float u_lin, z0, sp;
+    cand_row_head<NET, VEC, G, K>(a, M, tc, valid, lig, live, ur, u_lin, pr, Sp, z0, sp);
 
     const float zh0 = z0 * a.inv_tau;
     float mx = zh0, sum = 1.f, inv_sum = 1.f;  // sampled softmax: running maximum and sum of exponentials of the row
@@ -237,38 +264,9 @@ __global__ __launch_bounds__(TRS_BLOCK) void multineg_kernel(const MultiArgs a) 
 #pragma unroll
             for (int n = 0; n < N; ++n) acc.v[n] += g * Ss[c].v[n];
           }
-          if (grad && valid) {
-            RowReg<VEC, K> gv;
-            // the candidate's item row.  FM: g*(S - item) (= g*u when M == 0); Linear: g*u
-            if (NET == TRS_NET_FM && M != 0) {
-#pragma unroll
-              for (int n = 0; n < N; ++n) gv.v[n] = g * (Ss[c].v[n] - ir[c].v[n]);
-            } else {
-#pragma unroll
-              for (int n = 0; n < N; ++n) gv.v[n] = g * ur.v[n];
-            }
-            row_store<VEC, G, K>(gv, gr + (int64_t)(2 + j) * BD + t * (int64_t)D, D, lig);
-            // metadata fields (rows re-read: they are L1/L2-hot from the forward part)
-            for (int m = 0; m < M; ++m) {
-              if (NET == TRS_NET_FM) {
-                int64_t mid = a.meta[((int64_t)(1 + j) * B + t) * M + m];
-                if ((uint64_t)mid >= (uint64_t)T.n_meta[m]) mid = 0;
-                RowReg<VEC, K> mr;
-                row_load<VEC, G, K>(mr, T.meta[m], mid, D, lig);
-#pragma unroll
-                for (int n = 0; n < N; ++n) gv.v[n] = g * (Ss[c].v[n] - mr.v[n]);
-              } else {
-#pragma unroll
-                for (int n = 0; n < N; ++n) gv.v[n] = g * ur.v[n];
-              }
-              row_store<VEC, G, K>(gv, gr + (int64_t)(1 + S1 + m * S1 + 1 + j) * BD + t * (int64_t)D, D, lig);
-            }
-            if (lig == 0) {
-              gl[(int64_t)(2 + j) * B + t] = g;
-              for (int m = 0; m < M; ++m)  // Linear has no 1-wide metadata tables: those fields stay 0
-                gl[(int64_t)(1 + S1 + m * S1 + 1 + j) * B + t] = NET == TRS_NET_FM ? g : 0.f;
-            }
-          }
+          if (grad && valid)
+            stage_item_slot<NET, VEC, G, K>(T, M, S1, 1 + j, g, ur, ir[c], Ss[c], slot_meta_ids(a, M, 1 + j, t), gr, gl,
+                                            B, t, lig);
         }
       }
     };
@@ -327,77 +325,14 @@ __global__ __launch_bounds__(TRS_BLOCK) void multineg_kernel(const MultiArgs a) 
         for (int n = 0; n < N; ++n) gv.v[n] = gp * Sp.v[n] + acc.v[n];
       }
       row_store<VEC, G, K>(gv, gr + t * (int64_t)D, D, lig);
-      // field 1: the positive's item row
-      if (NET == TRS_NET_FM && M != 0) {
-#pragma unroll
-        for (int n = 0; n < N; ++n) gv.v[n] = gp * (Sp.v[n] - pr.v[n]);
-      } else {
-#pragma unroll
-        for (int n = 0; n < N; ++n) gv.v[n] = gp * ur.v[n];
-      }
-      row_store<VEC, G, K>(gv, gr + BD + t * (int64_t)D, D, lig);
-      for (int m = 0; m < M; ++m) {
-        if (NET == TRS_NET_FM) {
-          int64_t mid = a.meta[t * M + m];
-          if ((uint64_t)mid >= (uint64_t)T.n_meta[m]) mid = 0;
-          RowReg<VEC, K> mr;
-          row_load<VEC, G, K>(mr, T.meta[m], mid, D, lig);
-#pragma unroll
-          for (int n = 0; n < N; ++n) gv.v[n] = gp * (Sp.v[n] - mr.v[n]);
-        } else {
-#pragma unroll
-          for (int n = 0; n < N; ++n) gv.v[n] = gp * ur.v[n];
-        }
-        row_store<VEC, G, K>(gv, gr + (int64_t)(1 + S1 + m * S1) * BD + t * (int64_t)D, D, lig);
-      }
-      if (lig == 0) {
-        // the user's 1-wide term enters every z of the row with derivative 1: the softmax weights sum to exactly 0
-        gl[t] = SM ? 0.f : gp + gn_sum;
-        gl[B + t] = gp;
-        for (int m = 0; m < M; ++m) gl[(int64_t)(1 + S1 + m * S1) * B + t] = NET == TRS_NET_FM ? gp : 0.f;
-      }
+      stage_item_slot<NET, VEC, G, K>(T, M, S1, 0, gp, ur, pr, Sp, slot_meta_ids(a, M, 0, t), gr, gl, B, t, lig);
+      // the user's 1-wide term enters every z of the row with derivative 1: the softmax weights sum to exactly 0
+      if (lig == 0) gl[t] = SM ? 0.f : gp + gn_sum;
     }
   }
 
-  if (a.loss_sum) {  // as score_kernel: lanes -> wave -> block -> one atomic per block
-    __shared__ float s_loss[TRS_BLOCK / TRS_WAVE];
-    __shared__ int s_auc[TRS_BLOCK / TRS_WAVE];
-    const float wl = trs_wave_sum(loss_acc);
-    const int wa = trs_wave_sum_i(auc_acc);
-    if (lane == 0) {
-      s_loss[threadIdx.x >> 6] = wl;
-      s_auc[threadIdx.x >> 6] = wa;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      float L = 0.f;
-      int A = 0;
-#pragma unroll
-      for (int w = 0; w < TRS_BLOCK / TRS_WAVE; ++w) {
-        L += s_loss[w];
-        A += s_auc[w];
-      }
-      if (L != 0.f) atomicAdd(a.loss_sum, L);
-      if (A != 0 && a.auc_count) atomicAdd(a.auc_count, A);
-    }
-  }
+  if (a.loss_sum) block_add_loss_auc(loss_acc, auc_acc, a.loss_sum, a.auc_count);
 }
-
-template <int NET, bool SM>
-int launch_multi(const MultiArgs& a, hipStream_t s) {
-  RowCfg c;
-  TRS_TRY(row_cfg_for("trs_score_multi_fwd_bwd", a.T.D, c));
-  const int tpw = TRS_WAVE / c.g;
-  const int64_t waves = (a.B + tpw - 1) / tpw;
-  const dim3 gr(trs_grid(waves, TRS_BLOCK / TRS_WAVE)), bl(TRS_BLOCK);
-  return for_row_shape(c, [&](auto V, auto G, auto K) {
-    if (a.T.M > 0) hipLaunchKernelGGL((multineg_kernel<NET, V(), G(), K(), SM, true>), gr, bl, 0, s, a);
-    else hipLaunchKernelGGL((multineg_kernel<NET, V(), G(), K(), SM, false>), gr, bl, 0, s, a);
-    TRS_CHECK_LAUNCH("multineg_kernel");
-    return TRS_OK;
-  });
-}
-
 
 // ------------------------------------------------------------------------------------------------ WARP
 struct WarpArgs {
@@ -419,8 +354,7 @@ struct WarpArgs {
   int32_t* err;
 };
 
-// warp_kernel (wave = 64): multineg_kernel's mapping — one aligned group of G lanes per row, the user row and the
-// positive's pass in registers, candidates in rounds of C, every z pass_forward_z's.  What differs:
+// warp_kernel: what differs from multineg_kernel (the shared parts: the head of this file):
 //   first violator  within a round the lowest j with (z_j - z_p) + margin > 0, found by selects from the last slot down;
 //                   a group that has its J keeps scoring with its wave (the loads and shuffles stay whole-wave) and
 //                   ignores what it sees, again by select.
@@ -435,8 +369,7 @@ struct WarpArgs {
 template <int NET, int VEC, int G, int K, bool META>
 __global__ __launch_bounds__(TRS_BLOCK) void warp_kernel(const WarpArgs a) {
   constexpr int N = K * VEC;
-  constexpr int CR = MULTI_ROW_VGPRS / N < 8 ? (MULTI_ROW_VGPRS / N < 1 ? 1 : MULTI_ROW_VGPRS / N) : 8;
-  constexpr int C = G < CR ? G : CR;  // candidates per round (a power of two)
+  constexpr int C = cand_round<VEC, G, K>();
   constexpr int TPW = TRS_WAVE / G;
   constexpr bool FM = NET == TRS_NET_FM;
   const trs_tables& T = a.T;
@@ -444,7 +377,6 @@ __global__ __launch_bounds__(TRS_BLOCK) void warp_kernel(const WarpArgs a) {
   const int M = META ? T.M : 0;
   const int64_t B = a.B;
   const int Kn = a.Kn;
-  const int S1 = 1 + Kn;
   const int lane = threadIdx.x & 63;
   const int lig = lane % G;
   const int gbase = lane - lig;
@@ -464,30 +396,10 @@ __global__ __launch_bounds__(TRS_BLOCK) void warp_kernel(const WarpArgs a) {
     const bool valid = t < B;
     const int64_t tc = valid ? t : 0;  // loads stay unconditional
 
-    // every id of the row against its table first, as multineg_kernel
-    int64_t uid = a.user[tc];
-    int bad = 0;
-    if ((uint64_t)uid >= (uint64_t)T.n_users) { bad = 1; uid = 0; }
-    for (int s = lig; s < S1; s += G) {
-      const int64_t e = (int64_t)s * B + tc;
-      if ((uint64_t)(int64_t)a.items[e] >= (uint64_t)T.n_items) bad = 1;
-      for (int m = 0; m < M; ++m)
-        if ((uint64_t)(int64_t)a.meta[e * M + m] >= (uint64_t)T.n_meta[m]) bad = 1;
-    }
-    bad = trs_group_or<G>(bad);
-    if (valid && bad && lig == 0 && a.err) atomicOr(a.err, 1);
-    const bool live = valid && !bad;
-
-    RowReg<VEC, K> ur;
-    row_load<VEC, G, K>(ur, T.user, uid, D, lig);
-    const float u_lin = T.user_lin[uid];
-    int64_t pid = a.items[tc];
-    if ((uint64_t)pid >= (uint64_t)T.n_items) pid = 0;
-    RowReg<VEC, K> pr, Sp;
-    float p_lin, lin_p;
-    bool okp = true;
-    const float z0 = pass_forward_z<NET, VEC, G, K>(T, ur, u_lin, pid, a.meta, 4, tc, true, lig, pr, Sp, p_lin, lin_p, okp);
-    const float sp = FM ? sigmoidf_(z0) : z0;  // = pass_forward's score (the AUC count is on the scores, as today)
+    bool live;
+    RowReg<VEC, K> ur, pr, Sp;
+    float u_lin, z0, sp;  // (sp: the AUC count is on the scores, the hinge on z)
+    cand_row_head<NET, VEC, G, K>(a, M, tc, valid, lig, live, ur, u_lin, pr, Sp, z0, sp);
 
     bool done = !live;  // group-uniform: J found, the row past the batch, or a bad id
     int trials = 0;
@@ -531,65 +443,12 @@ __global__ __launch_bounds__(TRS_BLOCK) void warp_kernel(const WarpArgs a) {
           // d loss / d z: + w / B at the chosen candidate, - w / B at the positive (no sigmoid factor: the hinge is on z)
           const float gn = w * a.inv_B, gp = -gn;
           RowReg<VEC, K> g;
-          // field 0: user.  FM: gp*(Sp-u) + gn*(Sn-u) (= gp*i + gn*j when M == 0); Linear: gp*Sp + gn*Sn
-          if (FM) {
-            if (M == 0) {
-#pragma unroll
-              for (int n = 0; n < N; ++n) g.v[n] = gp * pr.v[n] + gn * ni.v[n];
-            } else {
-#pragma unroll
-              for (int n = 0; n < N; ++n) g.v[n] = gp * (Sp.v[n] - ur.v[n]) + gn * (Sn.v[n] - ur.v[n]);
-            }
-          } else {
-#pragma unroll
-            for (int n = 0; n < N; ++n) g.v[n] = gp * Sp.v[n] + gn * Sn.v[n];
-          }
+          pair_user_field<NET>(g, M != 0, gp, gn, ur, pr, ni, Sp, Sn);
           row_store<VEC, G, K>(g, gr + t * (int64_t)D, D, lig);
-          // field 1 / 2: the positive / the chosen candidate.  FM: g*(S - item) (= g*u when M == 0); Linear: g*u
-          if (FM && M != 0) {
-#pragma unroll
-            for (int n = 0; n < N; ++n) g.v[n] = gp * (Sp.v[n] - pr.v[n]);
-          } else {
-#pragma unroll
-            for (int n = 0; n < N; ++n) g.v[n] = gp * ur.v[n];
-          }
-          row_store<VEC, G, K>(g, gr + BD + t * (int64_t)D, D, lig);
-          if (FM && M != 0) {
-#pragma unroll
-            for (int n = 0; n < N; ++n) g.v[n] = gn * (Sn.v[n] - ni.v[n]);
-          } else {
-#pragma unroll
-            for (int n = 0; n < N; ++n) g.v[n] = gn * ur.v[n];
-          }
-          row_store<VEC, G, K>(g, gr + 2 * BD + t * (int64_t)D, D, lig);
-          for (int m = 0; m < M; ++m) {
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-              const float gs = s ? gn : gp;
-              const RowReg<VEC, K>& S = s ? Sn : Sp;
-              if (FM) {  // (the slot's metadata row again: L1/L2-hot from the forward part)
-                int64_t mid = a.meta[((int64_t)(s ? 1 + J : 0) * B + t) * M + m];
-                if ((uint64_t)mid >= (uint64_t)T.n_meta[m]) mid = 0;
-                RowReg<VEC, K> mr;
-                row_load<VEC, G, K>(mr, T.meta[m], mid, D, lig);
-#pragma unroll
-                for (int n = 0; n < N; ++n) g.v[n] = gs * (S.v[n] - mr.v[n]);
-              } else {
-#pragma unroll
-                for (int n = 0; n < N; ++n) g.v[n] = gs * ur.v[n];
-              }
-              row_store<VEC, G, K>(g, gr + (int64_t)(3 + 2 * m + s) * BD + t * (int64_t)D, D, lig);
-            }
-          }
-          if (lig == 0) {
-            gl[t] = 0.f;  // the user's 1-wide term enters both z with derivative 1: exactly 0
-            gl[B + t] = gp;
-            gl[2 * B + t] = gn;
-            for (int m = 0; m < M; ++m) {  // Linear has no 1-wide metadata tables: those fields stay 0
-              gl[(int64_t)(3 + 2 * m) * B + t] = FM ? gp : 0.f;
-              gl[(int64_t)(4 + 2 * m) * B + t] = FM ? gn : 0.f;
-            }
-          }
+          // the pair layout (S = 2): the positive, then the chosen candidate, whose ids are slot 1 + J's
+          stage_item_slot<NET, VEC, G, K>(T, M, 2, 0, gp, ur, pr, Sp, slot_meta_ids(a, M, 0, t), gr, gl, B, t, lig);
+          stage_item_slot<NET, VEC, G, K>(T, M, 2, 1, gn, ur, ni, Sn, slot_meta_ids(a, M, 1 + J, t), gr, gl, B, t, lig);
+          if (lig == 0) gl[t] = 0.f;  // the user's 1-wide term enters both z with derivative 1: exactly 0
         }
       }
     }
@@ -613,43 +472,33 @@ __global__ __launch_bounds__(TRS_BLOCK) void warp_kernel(const WarpArgs a) {
     }
   }
 
-  if (a.loss_sum) {  // as score_kernel: lanes -> wave -> block -> one atomic per block
-    __shared__ float s_loss[TRS_BLOCK / TRS_WAVE];
-    __shared__ int s_auc[TRS_BLOCK / TRS_WAVE];
-    const float wl = trs_wave_sum(loss_acc);
-    const int wa = trs_wave_sum_i(auc_acc);
-    if (lane == 0) {
-      s_loss[threadIdx.x >> 6] = wl;
-      s_auc[threadIdx.x >> 6] = wa;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      float L = 0.f;
-      int A = 0;
-#pragma unroll
-      for (int w = 0; w < TRS_BLOCK / TRS_WAVE; ++w) {
-        L += s_loss[w];
-        A += s_auc[w];
-      }
-      if (L != 0.f) atomicAdd(a.loss_sum, L);
-      if (A != 0 && a.auc_count) atomicAdd(a.auc_count, A);
-    }
-  }
+  if (a.loss_sum) block_add_loss_auc(loss_acc, auc_acc, a.loss_sum, a.auc_count);
 }
 
-template <int NET>
-int launch_warp(const WarpArgs& a, hipStream_t s) {
+// One launcher for both candidate kernels: one lane group per row.  kernel_of(V, G, K, META) names the instance.
+template <typename A, typename KernelOf>
+int launch_cand(const char* who, const char* kernel, const A& a, hipStream_t s, KernelOf kernel_of) {
   RowCfg c;
-  TRS_TRY(row_cfg_for("trs_score_warp_fwd_bwd", a.T.D, c));
+  TRS_TRY(row_cfg_for(who, a.T.D, c));
   const int tpw = TRS_WAVE / c.g;
   const int64_t waves = (a.B + tpw - 1) / tpw;
   const dim3 gr(trs_grid(waves, TRS_BLOCK / TRS_WAVE)), bl(TRS_BLOCK);
   return for_row_shape(c, [&](auto V, auto G, auto K) {
-    if (a.T.M > 0) hipLaunchKernelGGL((warp_kernel<NET, V(), G(), K(), true>), gr, bl, 0, s, a);
-    else hipLaunchKernelGGL((warp_kernel<NET, V(), G(), K(), false>), gr, bl, 0, s, a);
-    TRS_CHECK_LAUNCH("warp_kernel");
+    if (a.T.M > 0) hipLaunchKernelGGL(kernel_of(V, G, K, std::true_type{}), gr, bl, 0, s, a);
+    else hipLaunchKernelGGL(kernel_of(V, G, K, std::false_type{}), gr, bl, 0, s, a);
+    TRS_CHECK_LAUNCH(kernel);
     return TRS_OK;
   });
+}
+template <int NET, bool SM>
+int launch_multi(const MultiArgs& a, hipStream_t s) {
+  return launch_cand("trs_score_multi_fwd_bwd", "multineg_kernel", a, s, [](auto V, auto G, auto K, auto META) {
+    return multineg_kernel<NET, V(), G(), K(), SM, META()>; });
+}
+template <int NET>
+int launch_warp(const WarpArgs& a, hipStream_t s) {
+  return launch_cand("trs_score_warp_fwd_bwd", "warp_kernel", a, s, [](auto V, auto G, auto K, auto META) {
+    return warp_kernel<NET, V(), G(), K(), META()>; });
 }
 
 // The argument checks trs_score_multi_fwd_bwd and trs_score_warp_fwd_bwd share (everything but the loss's own

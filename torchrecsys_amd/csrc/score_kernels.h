@@ -194,6 +194,107 @@ __device__ __forceinline__ float pass_forward(const trs_tables& T, const RowReg<
   return NET == TRS_NET_FM ? sigmoidf_(z) : z;
 }
 
+// ------------------------------------------------------------------------- staging: the parts every kernel shares
+// The staged field layout, device side: F = 1 + S (1 + M) fields of (B, D) rows in grad_rows and of (B) 1-wide entries
+// in grad_lin — field 0 the user, then the S item slots, then the S slots of every metadata column.  The host twin is
+// engine.staged_layout(S, M, .); S = 2 (pair, WARP: positive, negative), S = 1 + K (K sampled negatives).
+__host__ __device__ constexpr int staged_item_field(int S, int s) { return 1 + s; }
+__host__ __device__ constexpr int staged_meta_field(int S, int m, int s) { return 1 + S + m * S + s; }
+static_assert(staged_item_field(2, 0) == 1 && staged_item_field(2, 1) == 2, "pair layout: the positive, the negative");
+static_assert(staged_meta_field(2, 0, 0) == 3 && staged_meta_field(2, 0, 1) == 4 && staged_meta_field(2, 3, 1) == 3 + 2 * 3 + 1,
+              "pair layout: column m, slot s is field 3 + 2m + s");
+
+// The staged gradient of ONE item slot s of S with coefficient g = d loss / d z of the slot's pass:
+//   item-row field       FM with metadata: g*(Ssum - it) (= g*u without: Ssum = u + it); Linear: g*u
+//   M metadata fields    FM: g*(Ssum - metadata row), the row re-read (L1/L2-hot from the forward part); Linear: g*u
+//   1-wide entries       g for the item; per column g (FM) or 0 (Linear has no 1-wide metadata tables)
+// mid_of(m) hands back the slot's metadata id of column m (it is checked against the table here); gl may be NULL.
+// ITEM_ROW = false: the metadata fields and their 1-wide entries only (MODE 2: the sorted item update has the rest).
+template <int NET, int VEC, int G, int K, bool ITEM_ROW = true, typename MidOf>
+__device__ __forceinline__ void stage_item_slot(const trs_tables& T, int M, int S, int s, float g,
+                                                const RowReg<VEC, K>& u, const RowReg<VEC, K>& it,
+                                                const RowReg<VEC, K>& Ssum, MidOf&& mid_of, float* gr, float* gl,
+                                                int64_t B, int64_t t, int lig) {
+  constexpr int N = K * VEC;
+  const int D = T.D;
+  const int64_t BD = B * (int64_t)D;
+  RowReg<VEC, K> gv;
+  if (ITEM_ROW) {
+    if (NET == TRS_NET_FM && M != 0) {
+#pragma unroll
+      for (int n = 0; n < N; ++n) gv.v[n] = g * (Ssum.v[n] - it.v[n]);
+    } else {
+#pragma unroll
+      for (int n = 0; n < N; ++n) gv.v[n] = g * u.v[n];
+    }
+    row_store<VEC, G, K>(gv, gr + (int64_t)staged_item_field(S, s) * BD + t * (int64_t)D, D, lig);
+  }
+  for (int m = 0; m < M; ++m) {
+    int64_t mid = mid_of(m);
+    if ((uint64_t)mid >= (uint64_t)T.n_meta[m]) mid = 0;
+    if (NET == TRS_NET_FM) {
+      RowReg<VEC, K> mr;
+      row_load<VEC, G, K>(mr, T.meta[m], mid, D, lig);
+#pragma unroll
+      for (int n = 0; n < N; ++n) gv.v[n] = g * (Ssum.v[n] - mr.v[n]);
+    } else {
+#pragma unroll
+      for (int n = 0; n < N; ++n) gv.v[n] = g * u.v[n];
+    }
+    row_store<VEC, G, K>(gv, gr + (int64_t)staged_meta_field(S, m, s) * BD + t * (int64_t)D, D, lig);
+  }
+  if (lig == 0 && gl) {
+    if (ITEM_ROW) gl[(int64_t)staged_item_field(S, s) * B + t] = g;
+    for (int m = 0; m < M; ++m) gl[(int64_t)staged_meta_field(S, m, s) * B + t] = NET == TRS_NET_FM ? g : 0.f;
+  }
+}
+
+// The user field of a pair (positive gp, negative gn).  FM: gp*(Sp-u) + gn*(Sn-u), without metadata gp*pi + gn*ni
+// (the same value, fewer operations: Ssum = u + item); Linear: gp*Sp + gn*Sn.
+template <int NET, int VEC, int K>
+__device__ __forceinline__ void pair_user_field(RowReg<VEC, K>& g, bool meta, float gp, float gn,
+                                                const RowReg<VEC, K>& u, const RowReg<VEC, K>& pi,
+                                                const RowReg<VEC, K>& ni, const RowReg<VEC, K>& Sp,
+                                                const RowReg<VEC, K>& Sn) {
+  constexpr int N = K * VEC;
+  if (NET == TRS_NET_FM) {
+    if (!meta) {
+#pragma unroll
+      for (int n = 0; n < N; ++n) g.v[n] = gp * pi.v[n] + gn * ni.v[n];
+    } else {
+#pragma unroll
+      for (int n = 0; n < N; ++n) g.v[n] = gp * (Sp.v[n] - u.v[n]) + gn * (Sn.v[n] - u.v[n]);
+    }
+  } else {
+#pragma unroll
+    for (int n = 0; n < N; ++n) g.v[n] = gp * Sp.v[n] + gn * Sn.v[n];
+  }
+}
+
+// The block's loss sum and AUC count: lanes -> wave -> LDS -> one atomic per block.  Every thread of the block calls it.
+__device__ __forceinline__ void block_add_loss_auc(float loss_acc, int auc_acc, float* loss_sum, int32_t* auc_count) {
+  __shared__ float s_loss[TRS_BLOCK / TRS_WAVE];
+  __shared__ int s_auc[TRS_BLOCK / TRS_WAVE];
+  const float wl = trs_wave_sum(loss_acc);
+  const int wa = trs_wave_sum_i(auc_acc);
+  if ((threadIdx.x & 63) == 0) {
+    s_loss[threadIdx.x >> 6] = wl;
+    s_auc[threadIdx.x >> 6] = wa;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float L = 0.f;
+    int A = 0;
+#pragma unroll
+    for (int w = 0; w < TRS_BLOCK / TRS_WAVE; ++w) {
+      L += s_loss[w];
+      A += s_auc[w];
+    }
+    if (L != 0.f) atomicAdd(loss_sum, L);
+    if (A != 0 && auc_count) atomicAdd(auc_count, A);
+  }
+}
+
 // MODE 0: scores only.  MODE 1: scores + hinge/upstream grads -> staged per-triple gradient rows.
 template <int NET, int VEC, int G, int K, int MODE>
 __global__ __launch_bounds__(TRS_BLOCK) void score_kernel(const ScoreArgs a) {
@@ -276,71 +377,14 @@ __global__ __launch_bounds__(TRS_BLOCK) void score_kernel(const ScoreArgs a) {
       }
       if (valid) {
         const int M = T.M;
-        float* gr = a.grad_rows;
-        const int64_t BD = B * (int64_t)D;
         RowReg<VEC, K> g;
-        // field 0: user.  FM: gp*(Sp-u) + gn*(Sn-u) (= gp*i + gn*j when M == 0); Linear: gp*Ip + gn*In
-        if (NET == TRS_NET_FM) {
-          if (M == 0) {
-#pragma unroll
-            for (int n = 0; n < N; ++n) g.v[n] = gp * pi.v[n] + gn * ni.v[n];
-          } else {
-#pragma unroll
-            for (int n = 0; n < N; ++n) g.v[n] = gp * (Sp.v[n] - u.v[n]) + gn * (Sn.v[n] - u.v[n]);
-          }
-        } else {
-#pragma unroll
-          for (int n = 0; n < N; ++n) g.v[n] = gp * Sp.v[n] + gn * Sn.v[n];
-        }
-        row_store<VEC, G, K>(g, gr + 0 * BD + t * (int64_t)D, D, lig);
-        // field 1 / 2: pos / neg item.  FM: g*(S - item) (= g*u when M == 0); Linear: g*u
-        if (NET == TRS_NET_FM && M != 0) {
-#pragma unroll
-          for (int n = 0; n < N; ++n) g.v[n] = gp * (Sp.v[n] - pi.v[n]);
-        } else {
-#pragma unroll
-          for (int n = 0; n < N; ++n) g.v[n] = gp * u.v[n];
-        }
-        row_store<VEC, G, K>(g, gr + 1 * BD + t * (int64_t)D, D, lig);
-        if (NET == TRS_NET_FM && M != 0) {
-#pragma unroll
-          for (int n = 0; n < N; ++n) g.v[n] = gn * (Sn.v[n] - ni.v[n]);
-        } else {
-#pragma unroll
-          for (int n = 0; n < N; ++n) g.v[n] = gn * u.v[n];
-        }
-        row_store<VEC, G, K>(g, gr + 2 * BD + t * (int64_t)D, D, lig);
-        // metadata fields (rows re-read: they are L1/L2-hot from the forward part)
-        for (int m = 0; m < M; ++m) {
-#pragma unroll
-          for (int s = 0; s < 2; ++s) {
-            const float gs = s ? gn : gp;
-            const RowReg<VEC, K>& S = s ? Sn : Sp;
-            if (NET == TRS_NET_FM) {
-              int64_t mid = trs_ld_idx(s ? a.Bt.neg_meta : a.Bt.pos_meta, ib, t * M + m);
-              if ((uint64_t)mid >= (uint64_t)T.n_meta[m]) mid = 0;
-              RowReg<VEC, K> mr;
-              row_load<VEC, G, K>(mr, T.meta[m], mid, D, lig);
-#pragma unroll
-              for (int n = 0; n < N; ++n) g.v[n] = gs * (S.v[n] - mr.v[n]);
-            } else {
-#pragma unroll
-              for (int n = 0; n < N; ++n) g.v[n] = gs * u.v[n];
-            }
-            row_store<VEC, G, K>(g, gr + (int64_t)(3 + 2 * m + s) * BD + t * (int64_t)D, D, lig);
-          }
-        }
-        // 1-wide terms: FM linear_* / Linear biases
-        if (lig == 0 && a.grad_lin) {
-          float* gl = a.grad_lin;
-          gl[0 * B + t] = gp + gn;
-          gl[1 * B + t] = gp;
-          gl[2 * B + t] = gn;
-          for (int m = 0; m < M; ++m) {  // Linear has no 1-wide metadata tables: those fields stay 0
-            gl[(int64_t)(3 + 2 * m) * B + t] = NET == TRS_NET_FM ? gp : 0.f;
-            gl[(int64_t)(4 + 2 * m) * B + t] = NET == TRS_NET_FM ? gn : 0.f;
-          }
-        }
+        pair_user_field<NET>(g, M != 0, gp, gn, u, pi, ni, Sp, Sn);
+        row_store<VEC, G, K>(g, a.grad_rows + t * (int64_t)D, D, lig);
+        const auto pos_mid = [&](int m) { return trs_ld_idx(a.Bt.pos_meta, ib, t * M + m); };
+        const auto neg_mid = [&](int m) { return trs_ld_idx(a.Bt.neg_meta, ib, t * M + m); };
+        stage_item_slot<NET, VEC, G, K>(T, M, 2, 0, gp, u, pi, Sp, pos_mid, a.grad_rows, a.grad_lin, B, t, lig);
+        stage_item_slot<NET, VEC, G, K>(T, M, 2, 1, gn, u, ni, Sn, neg_mid, a.grad_rows, a.grad_lin, B, t, lig);
+        if (lig == 0 && a.grad_lin) a.grad_lin[t] = gp + gn;  // the user's 1-wide term (FM linear_* / Linear bias)
       }
     }
     if (MODE == 2) {
@@ -362,13 +406,10 @@ __global__ __launch_bounds__(TRS_BLOCK) void score_kernel(const ScoreArgs a) {
         if (NET == TRS_NET_FM) {
           row_store<VEC, G, K>(Sp, a.xstage + t * (int64_t)D, D, lig);
           row_store<VEC, G, K>(Sn, a.xstage + BD + t * (int64_t)D, D, lig);
-#pragma unroll
-          for (int n = 0; n < N; ++n) g.v[n] = gp * (Sp.v[n] - u.v[n]) + gn * (Sn.v[n] - u.v[n]);
         } else {
           row_store<VEC, G, K>(u, a.xstage + t * (int64_t)D, D, lig);
-#pragma unroll
-          for (int n = 0; n < N; ++n) g.v[n] = gp * Sp.v[n] + gn * Sn.v[n];
         }
+        pair_user_field<NET>(g, true, gp, gn, u, pi, ni, Sp, Sn);  // (MODE 2 runs with metadata only)
         if (a.udup_pos[t] || !live) {
           row_store<VEC, G, K>(g, a.du + t * (int64_t)D, D, lig);
         } else {
@@ -380,28 +421,18 @@ __global__ __launch_bounds__(TRS_BLOCK) void score_kernel(const ScoreArgs a) {
         }
         // metadata fields: staged gradients (as MODE 1 stages them) + their ids — unless the columns have sorted runs
         // of their own (grad_rows == NULL: they read xstage like the item runs)
-        for (int m = 0; m < (a.grad_rows ? M : 0); ++m) {
+        if (a.grad_rows) {
 #pragma unroll
           for (int s = 0; s < 2; ++s) {
-            const float gs = s ? gn : gp;
-            const RowReg<VEC, K>& S = s ? Sn : Sp;
-            int64_t mid = a.Bt.pos_meta ? trs_ld_idx(s ? a.Bt.neg_meta : a.Bt.pos_meta, ib, t * M + m)
-                                        : (int64_t)a.item_meta_tab[(s ? nid : pid) * M + m];
-            if ((uint64_t)mid >= (uint64_t)T.n_meta[m]) mid = 0;
-            if (NET == TRS_NET_FM) {
-              RowReg<VEC, K> mr;
-              row_load<VEC, G, K>(mr, T.meta[m], mid, D, lig);
-#pragma unroll
-              for (int n = 0; n < N; ++n) g.v[n] = gs * (S.v[n] - mr.v[n]);
-            } else {
-#pragma unroll
-              for (int n = 0; n < N; ++n) g.v[n] = gs * u.v[n];
-            }
-            row_store<VEC, G, K>(g, a.grad_rows + (int64_t)(3 + 2 * m + s) * BD + t * (int64_t)D, D, lig);
-            if (lig == 0) {
-              a.meta_ids_out[((int64_t)s * B + t) * M + m] = (int32_t)mid;  // a dead triple carries zero gradients
-              if (a.grad_lin) a.grad_lin[(int64_t)(3 + 2 * m + s) * B + t] = NET == TRS_NET_FM ? gs : 0.f;
-            }
+            const auto mid_out = [&](int m) {  // the slot's id, also written out for the scatter
+              int64_t mid = a.Bt.pos_meta ? trs_ld_idx(s ? a.Bt.neg_meta : a.Bt.pos_meta, ib, t * M + m)
+                                          : (int64_t)a.item_meta_tab[(s ? nid : pid) * M + m];
+              if ((uint64_t)mid >= (uint64_t)T.n_meta[m]) mid = 0;
+              if (lig == 0) a.meta_ids_out[((int64_t)s * B + t) * M + m] = (int32_t)mid;  // a dead triple carries zero gradients
+              return mid;
+            };
+            stage_item_slot<NET, VEC, G, K, false>(T, M, 2, s, s ? gn : gp, u, s ? ni : pi, s ? Sn : Sp, mid_out,
+                                                   a.grad_rows, a.grad_lin, B, t, lig);
           }
         }
         if (lig == 0) {
@@ -413,28 +444,7 @@ __global__ __launch_bounds__(TRS_BLOCK) void score_kernel(const ScoreArgs a) {
 
   }
 
-  if (MODE != 0 && a.loss_sum) {
-    __shared__ float s_loss[TRS_BLOCK / TRS_WAVE];
-    __shared__ int s_auc[TRS_BLOCK / TRS_WAVE];
-    const float wl = trs_wave_sum(loss_acc);
-    const int wa = trs_wave_sum_i(auc_acc);
-    if (lane == 0) {
-      s_loss[threadIdx.x >> 6] = wl;
-      s_auc[threadIdx.x >> 6] = wa;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      float L = 0.f;
-      int A = 0;
-#pragma unroll
-      for (int w = 0; w < TRS_BLOCK / TRS_WAVE; ++w) {
-        L += s_loss[w];
-        A += s_auc[w];
-      }
-      if (L != 0.f) atomicAdd(a.loss_sum, L);
-      if (A != 0 && a.auc_count) atomicAdd(a.auc_count, A);
-    }
-  }
+  if (MODE != 0 && a.loss_sum) block_add_loss_auc(loss_acc, auc_acc, a.loss_sum, a.auc_count);
 }
 
 // ---------------------------------------------------------------------------------------- dispatch
