@@ -100,7 +100,8 @@ const char* trs_last_error(void);
  *      trs_mask_seen, trs_rank_metrics.  (Entry points added since without touching an existing signature or struct:
  *      the in-batch softmax group, trs_batch_prepare_mined, trs_batch_prepare_multi, trs_score_multi_fwd_bwd,
  *      trs_score_warp_fwd_bwd, TRS_LOSS_WARP, trs_stage_add_l2, trs_neighbour_fold, trs_neighbours_topk,
- *      trs_fold_in_users, trs_item_ranks, trs_item_ranks_workspace_bytes, trs_mmr_rerank, trs_list_ild.) */
+ *      trs_fold_in_users, trs_item_ranks, trs_item_ranks_workspace_bytes, trs_mmr_rerank, trs_list_ild,
+ *      trs_fold_in_items.) */
 #define TRS_ABI_VERSION 6
 #define TRS_SYNC_WORDS 288
 #define TRS_SYNC_REBASE 0x40000000u /* arrivals after which trs_train_steps_sgd zeroes sync_dev and its host count */
@@ -698,6 +699,60 @@ int trs_fold_in_users(int net, const void* fold_dev, int64_t fold_bytes, int64_t
                       const trs_csr* hist, int32_t loss, int32_t epochs, float lr, float l2, uint64_t seed,
                       int32_t shuffle, int32_t reject_seen, int32_t max_tries, float* user_out_dev,
                       float* user_lin_out_dev, float* loss_out_dev, int32_t* err_flag_dev, void* stream);
+
+/* ------------------------------------------------------ item fold-in of unseen items (fold_in_items) */
+/* One new item row per user history, everything else frozen: E epochs of per-visit SGD on the item's own row v and its
+ * 1-wide entry beta.  One launch for all items.  Added without touching an existing signature or struct.
+ * Frozen inputs: the user table U (n_users, D) = tables->user (unpadded, row stride D) with a = tables->user_lin
+ * (n_users); the catalogue's fold (S, c) = fold_dev, a trs_item_fold buffer of (n_items, D); the train interactions
+ * (stream_user, stream_item), n_stream rows, int32, dense ids; seen (optional): the model's seen CSR, user -> sorted
+ * train items.  Of `tables` only user, user_lin, n_users and D are read.
+ * Per new item h: hist row h = its sorted, distinct dense user ids (off int64 (n_new + 1), items int32 hold the users;
+ * n_h = off[h+1] - off[h]); its metadata part T_h in R^Dp and kappa_h = row h of S and c of new_fold_dev, a trs_item_fold
+ * buffer of (n_new, D) written for a table set whose item rows and 1-wide item rows are zero and whose metadata ids are
+ * the new items' (so T = sum_m meta_m, kappa = the c of an item with a zero row; M == 0: both 0).
+ * State per item h: v in R^D = 0, beta = 0, fp32.  With x_d = v_d + T_d (one rounding):
+ *   z_new(u)   = ((sum_d U[u,d] * x_d) + a_u) + c_new,   c_new = beta + kappa (Linear) | (beta + kappa) + sum_d v_d * T_d (FM)
+ *   z_old(u,o) = ((sum_d U[u,d] * S[o,d]) + a_u) + c_o
+ *   s = z (Linear) | sigmoid(z) = 1 / (1 + expf(-z)) (FM);  w(s) = 1 | s (1 - s);  dir_d = U[u,d] | U[u,d] + T_d
+ *   sums       every sum over d is the kernel's: per lane of the item's group of Dp / 4 lanes the four products of
+ *              columns 4l .. 4l+3 added in ascending column order from the first product, then trs_group_sum (the xor
+ *              butterfly of strides Dp/8 .. 1); columns >= D of U read as 0.
+ * For epoch e = 0 .. E-1, visit j = 0 .. n_h * (1 + nu) - 1 (nu = negative_visits), in this order, sequentially:
+ *   order      q = j / (1 + nu), t = j mod (1 + nu); r = q when shuffle == 0, else r = trs_feistel_perm(q, n_h, key_e,
+ *              trs_feistel_half_bits(n_h)), key_e that of "fold-in" above.  ctr = ((uint64)e << 32) | r.
+ *   t == 0     the new item is the positive: u = items[off[h] + r];
+ *              o = trs_sample_neg_opt(seed, ctr, u, pos = n_items, n_items + 1, sampler): the new item stands for row
+ *              n_items of a catalogue one longer, so o is uniform over [0, n_items); with reject_seen and seen != NULL a
+ *              candidate that seen row u holds is redrawn, at most max_tries candidates, the last kept (seen == NULL
+ *              or reject_seen == 0: the first candidate; max_tries == 0 calls trs_sample_one_neg).
+ *              (value, dneg) = trs_pair_loss(loss, s(z_new(u)), s(z_old(u,o)));  g = -dneg * w(s_new).
+ *   t >= 1     the new item is the negative of a train interaction: candidate k = 0, 1, .. is row
+ *              idx_k = mulhi64((y << 32) | x, n_stream) of trs_philox4x32_10(counter = ctr, key = (seed +
+ *              (1 + t) * 0xD1B54A32D192ED03 + k * 0x9E3779B97F4A7C15) mod 2^64); with reject_seen a candidate whose user
+ *              stream_user[idx_k] is in history row h (binary search) is redrawn, at most max_tries candidates, the
+ *              last kept; without, candidate 0.  (u, o) = (stream_user[idx], stream_item[idx]).
+ *              (value, dneg) = trs_pair_loss(loss, s(z_old(u,o)), s(z_new(u)));  g = +dneg * w(s_new).
+ *   update     v_d <- v_d - lr * ((g * dir_d) + l2 * v_d);  beta <- beta - lr * (g + l2 * beta); every product and sum
+ *              rounded to fp32.
+ *   loss_out   loss_out[e][h] = (sum of the epoch's values in visit order) / (float)(n_h * (1 + nu)); 0 for n_h == 0.
+ *   purity     the result for an item depends on its history, T_h, kappa_h, the options and the frozen inputs only, not
+ *              on h or on the other items of the call.  n_h == 0 gives v = 0, beta = 0: the metadata-only item.
+ * A user id outside [0, n_users) or a stream item outside [0, n_items) is never used as an address: that visit is
+ * skipped (no update, nothing added to the loss sum) and bit 0 of *err_flag_dev (may be NULL) is set.
+ * Outputs: item_out (n_new, D), item_lin_out (n_new), loss_out (epochs, n_new) or NULL; each written once.
+ * TRS_E_ARG, nothing launched: what trs_fold_in_users rejects (net, D, n_items, fold buffer, loss, epochs, lr, l2,
+ * max_tries, reject_seen with max_tries == 0, hist NULL, FOLDIN_DEPTH; with n_new > 0 a NULL array of hist or a NULL
+ * output), with D = tables->D, and n_items == 2^31-1 (row n_items must be an int32 too); tables NULL, a NULL user /
+ * user_lin table, n_users outside 1..2^31-1; negative_visits outside 0..8; negative_visits > 0 with n_stream <= 0 or a NULL stream; n_stream < 0; with n_new > 0
+ * new_fold_dev NULL or new_fold_bytes < trs_item_fold_bytes(n_new, D); seen with a NULL array.  n_new == 0: TRS_OK,
+ * nothing launched. */
+int trs_fold_in_items(int net, const trs_tables* tables, const void* fold_dev, int64_t fold_bytes, int64_t n_items,
+                      const void* new_fold_dev, int64_t new_fold_bytes, const trs_csr* hist,
+                      const int32_t* stream_user_dev, const int32_t* stream_item_dev, int64_t n_stream,
+                      const trs_csr* seen, int32_t loss, int32_t epochs, float lr, float l2, int32_t negative_visits,
+                      uint64_t seed, int32_t shuffle, int32_t reject_seen, int32_t max_tries, float* item_out_dev,
+                      float* item_lin_out_dev, float* loss_out_dev, int32_t* err_flag_dev, void* stream);
 
 /* ------------------------------------------------- exact ranks (rank_items / evaluate_ranks) */
 /* Where given items land in a user's full ranking.  Added without touching an existing signature or struct.

@@ -1079,18 +1079,19 @@ class TorchRecSys(torch.nn.Module):
         if reject_seen and int(max_tries) < 1:
             raise ValueError("reject_seen needs max_tries >= 1")
 
-    def _history_csr(self, histories):
+    def _history_csr(self, histories, side='item'):
         """Host side of fold-in: original item ids -> dense rows (IndexError on an unknown id), every history sorted and
         de-duplicated, the users ordered by history length, longest first (the lane groups of a wave then have similar
         trip counts and the long tails start first).  Returns (offsets int64 (n+1,), items int32, rank) as numpy arrays:
-        row rank[r] of the CSR is the caller's history r."""
+        row rank[r] of the CSR is the caller's history r.  side='user' (fold_in_items): the histories hold user ids."""
         hs = [np.asarray(h.tolist() if hasattr(h, "tolist") else list(h), dtype=np.int64).reshape(-1) for h in histories]
         n = len(hs)
         lens = np.array([h.size for h in hs], dtype=np.int64)
         flat = np.concatenate(hs) if n and lens.sum() else np.zeros(0, dtype=np.int64)
-        dense = self._dense_rows(flat, getattr(self.data_processor, "item_index", None), self.n_items, 'item').numpy()
-        key = np.unique(np.repeat(np.arange(n, dtype=np.int64), lens) * int(self.n_items) + dense)
-        rows, items = key // int(self.n_items), key % int(self.n_items)
+        n_side = int(self.n_items if side == 'item' else self.n_users)
+        dense = self._dense_rows(flat, getattr(self.data_processor, side + "_index", None), n_side, side).numpy()
+        key = np.unique(np.repeat(np.arange(n, dtype=np.int64), lens) * n_side + dense)
+        rows, items = key // n_side, key % n_side
         counts = np.bincount(rows, minlength=n).astype(np.int64)
         order = np.argsort(-counts, kind='stable')
         rank = np.empty(n, dtype=np.int64)
@@ -1177,6 +1178,190 @@ class TorchRecSys(torch.nn.Module):
         r = torch.from_numpy(rank)
         ids = self._original_ids(ids.cpu()[r], getattr(self.data_processor, "item_index", None))
         return (ids, scores.cpu()[r]) if return_scores else ids
+
+    # ------------------------------------------------------------------------------------------------ item fold-in
+    def _new_item_metadata(self, what, metadata, n):
+        """The (n, M) int64 numpy metadata ids of n new items, or None for a model without metadata.  ValueError when
+        given without / missing with a metadata model, or of another shape or type; IndexError outside a table."""
+        M = self.net.n_meta_tables()
+        if M == 0:
+            if metadata is not None:
+                raise ValueError(f"{what}: metadata given, but the model uses no metadata")
+            return None
+        if metadata is None:
+            raise ValueError(f"{what}: the model uses {M} metadata column(s): metadata (n, {M}) is required")
+        meta = np.asarray(metadata.tolist() if hasattr(metadata, "tolist") else metadata)
+        if meta.size == 0:
+            meta = meta.reshape(-1, M).astype(np.int64)
+        if meta.dtype.kind not in 'iu' or meta.shape != (n, M):
+            raise ValueError(f"{what}: metadata must be ({n}, {M}) integers, got {meta.dtype} {tuple(meta.shape)}")
+        meta = meta.astype(np.int64)
+        for m, p in enumerate(self.net.table_params()[4:4 + M]):
+            bad = (meta[:, m] < 0) | (meta[:, m] >= p.shape[0])
+            if bad.any():
+                raise IndexError(f"{what}: metadata id {int(meta[bad, m][0])} of column {m} outside [0, {p.shape[0]})")
+        return meta
+
+    def _meta_tables(self):
+        """(metadata tables, their 1-wide tables) of the scorer, as make_tables takes them."""
+        tp, M = self.net.table_params(), self.net.n_meta_tables()
+        return [p.data for p in tp[4:4 + M]], ([p.data for p in tp[4 + M:4 + 2 * M]] if self.net.META_LIN_NAME else [])
+
+    def _new_item_fold(self, meta, n, dev):
+        """Item fold of n items whose own rows are zero and whose metadata ids are `meta` (numpy (n, M) or None): its S
+        rows are the metadata parts T, its c the constants kappa, of the new items (include/trs.h "item fold-in")."""
+        tp = self.net.table_params()
+        metas, meta_lins = self._meta_tables()
+        zero = torch.zeros((n, self.n_factors), dtype=torch.float32, device=dev)
+        zero_lin = torch.zeros((n, 1), dtype=torch.float32, device=dev)
+        T, keep = ops.make_tables(tp[0].data, zero, tp[2].data, zero_lin, metas, meta_lins)
+        ids = None if meta is None else torch.from_numpy(meta).to(torch.int32).to(dev)
+        return ops.item_fold(self.net.NET, T, n, self.n_factors, dev, ids)
+
+    @_host_side
+    def fold_in_items(self, histories, metadata=None, epochs: int = 8, lr: float = 0.05, loss: str = 'hinge',
+                      l2: float = 0.0, negative_visits: int = 1, seed: int = 0, shuffle: bool = True,
+                      reject_seen: bool = True, max_tries: int = 8, return_loss: bool = False):
+        """Rows for items the model has never seen, fitted to the users who interacted with them with everything else
+        frozen: CPU tensors V (n, n_factors) fp32 and b (n,) fp32 — what the item table and item_bias / linear_item
+        would hold — and with return_loss the (epochs, n) fp32 mean pair loss of every epoch.
+        histories: a sequence of sequences / 1-D arrays of original user ids (an unknown id raises IndexError); each is
+        sorted and de-duplicated first.  metadata: the (n, M) integer metadata ids of the new items, as the ingest took
+        them; required exactly when the model uses metadata (ValueError otherwise; IndexError for an id outside its
+        table).  The item is scored as item row + metadata rows, so an empty history gives v = 0, b = 0: the item its
+        metadata alone describes.
+        Per item, `epochs` passes of per-visit SGD over the history (shuffled per epoch when `shuffle`): at each user of
+        the history the new item is the positive against one sampled catalogue item (one the user has in the train
+        split is redrawn, at most max_tries candidates, when reject_seen); then `negative_visits` (0..8) times the new
+        item is the negative of a train interaction drawn uniformly from the train rows this process holds (one whose
+        user is in the history is redrawn when reject_seen) — what fit() does to every item through its sampler, and
+        what keeps b from growing without bound.  loss 'hinge' or 'bpr' on the scorer's outputs, step lr, L2
+        coefficient l2 on v and b; the exact rule is in include/trs.h ("item fold-in").  The result for an item does
+        not depend on the other items of the call.  One kernel launch for all items.
+        Linear and FM only (ValueError for the MLP and for n_factors > TRS_RETRIEVE_DMAX).  The model's parameters are
+        never written; recommend_with_new_items() ranks the catalogue extended by the returned rows."""
+        self._check_fold_in("fold_in_items", epochs, lr, loss, l2, seed, max_tries, reject_seen)
+        if isinstance(negative_visits, bool) or not isinstance(negative_visits, (int, np.integer)) or \
+                not 0 <= int(negative_visits) <= 8:
+            raise ValueError(f"negative_visits must be an integer in 0..8, got {negative_visits!r}")
+        off, users, rank = self._history_csr(histories, side='user')
+        n = rank.size
+        meta = self._new_item_metadata("fold_in_items", metadata, n)
+        if n == 0:
+            V, b = torch.empty((0, self.n_factors), dtype=torch.float32), torch.empty((0,), dtype=torch.float32)
+            return (V, b, torch.empty((int(epochs), 0), dtype=torch.float32)) if return_loss else (V, b)
+        dev = _device()
+        self.net = self.net.eval()
+        st = self._device_stream('train')
+        if int(negative_visits) > 0 and st['user'].numel() == 0:
+            raise ValueError("fold_in_items: negative_visits > 0 needs train interactions, and this process holds none")
+        fold = ops.item_fold(self.net.NET, self.net.tables(), self.n_items, self.n_factors, dev, self._item_meta_dev())
+        order = np.argsort(rank)  # CSR row k is the caller's item order[k]
+        new_fold = self._new_item_fold(None if meta is None else meta[order], n, dev)
+        hist = (torch.from_numpy(off).to(dev), torch.from_numpy(users).to(dev))
+        V, b, ls = ops.fold_in_items(self.net.NET, self.net.tables(), fold, self.n_items, new_fold, hist, st['user'],
+                                     st['pos'], self._seen_csr() if reject_seen else None, loss, int(epochs),
+                                     float(lr), float(l2), int(negative_visits), int(seed), bool(shuffle),
+                                     bool(reject_seen), int(max_tries), want_loss=return_loss)
+        r = torch.from_numpy(rank)
+        V, b = V.cpu()[r], b.cpu()[r]
+        return (V, b, ls.cpu()[:, r]) if return_loss else (V, b)
+
+    @staticmethod
+    def _extended_seen_csr(off, items, hist_off, hist_users, n_items):
+        """The seen CSR (numpy offsets (n_users + 1,), items) with row n_items + j appended to the row of every user of
+        history j (hist_off, hist_users: a CSR of dense, distinct users per new item).  The new rows are larger than
+        every catalogue row and ascend with j, so each user's row stays sorted.  (offsets int64, items int32)."""
+        off, items = np.asarray(off, dtype=np.int64), np.asarray(items, dtype=np.int32)
+        hist_off, hist_users = np.asarray(hist_off, dtype=np.int64), np.asarray(hist_users, dtype=np.int64)
+        n_users = off.size - 1
+        rows = np.repeat(np.arange(hist_off.size - 1, dtype=np.int64), np.diff(hist_off)) + int(n_items)
+        o = np.lexsort((rows, hist_users))  # by user, then by new row
+        au, ar = hist_users[o], rows[o]
+        cnt = np.bincount(au, minlength=n_users).astype(np.int64)
+        shift = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+        new_off = off + shift
+        out = np.empty(items.size + ar.size, dtype=np.int32)
+        old_user = np.repeat(np.arange(n_users, dtype=np.int64), np.diff(off))
+        out[np.arange(items.size, dtype=np.int64) + shift[old_user]] = items
+        within = np.arange(ar.size, dtype=np.int64) - shift[au]
+        out[new_off[au + 1] - cnt[au] + within] = ar
+        return new_off, out
+
+    @_host_side
+    def recommend_with_new_items(self, user_ids, item_ids, V, b, metadata=None, histories=None, top_k: int = 10,
+                                 exclude_seen: bool = True, return_scores: bool = False):
+        """recommend() over the catalogue extended by new items: `item_ids` (original ids, distinct, none of them an item
+        of the model: ValueError otherwise) with the rows V (n, n_factors) and 1-wide entries b (n,) that fold_in_items
+        returned (or any other), and their (n, M) `metadata` ids exactly when the model uses metadata.
+        Output as recommend(): an (n_q, k) int64 CPU tensor of original item ids, k = min(top_k, n_items + n), with
+        return_scores also the (n_q, k) fp32 scores (FM: sigmoid(z), ranked by z); positions beyond the candidates hold
+        id -1 / score -inf; ties by ascending row, the new items taking the rows after the catalogue's in the order
+        given.  exclude_seen drops every user's train items and, with `histories` (one sequence of original user ids
+        per new item, as given to fold_in_items), the new item for the users of its history.
+        Composition of the existing kernels over temporary tables: the item-side tables are copied with the new rows
+        appended, folded (trs_item_fold) and searched (trs_retrieve_topk).  The copy costs one item table per call —
+        512 MB at 1 M items x 128 factors — plus its fold; the model is never written or grown.  Only the fused kernel is
+        offered: top_k > TRS_RETRIEVE_KMAX raises ValueError, as do the MLP and n_factors > TRS_RETRIEVE_DMAX."""
+        what = "recommend_with_new_items"
+        if self.net_type not in ('linear', 'fm'):
+            raise ValueError(f"{what} needs net_type 'linear' or 'fm', not {self.net_type!r} (mlp)")
+        if self.n_factors > ops._lib.RETRIEVE_DMAX:
+            raise ValueError(f"{what} takes n_factors <= {ops._lib.RETRIEVE_DMAX} (TRS_RETRIEVE_DMAX), got "
+                             f"{self.n_factors}")
+        if int(top_k) > ops._lib.RETRIEVE_KMAX:
+            raise ValueError(f"{what} takes top_k <= {ops._lib.RETRIEVE_KMAX} (TRS_RETRIEVE_KMAX), got {top_k}")
+        new_ids = np.asarray(item_ids.tolist() if hasattr(item_ids, "tolist") else list(item_ids), dtype=np.int64)
+        new_ids = new_ids.reshape(-1)
+        n = new_ids.size
+        if np.unique(new_ids).size != n:
+            raise ValueError(f"{what}: item_ids must be distinct")
+        index = getattr(self.data_processor, "item_index", None)
+        known = (new_ids >= 0) & (new_ids < self.n_items) if index is None else \
+            np.isin(new_ids, index.cpu().numpy().astype(np.int64))
+        if known.any():
+            raise ValueError(f"{what}: item id {int(new_ids[known][0])} is an item of the model, not a new one")
+        V = torch.as_tensor(V, dtype=torch.float32).cpu()
+        b = torch.as_tensor(b, dtype=torch.float32).cpu().reshape(-1)
+        if tuple(V.shape) != (n, self.n_factors) or b.numel() != n:
+            raise ValueError(f"{what}: V must be ({n}, {self.n_factors}) and b ({n},), got {tuple(V.shape)} and "
+                             f"{tuple(b.shape)}")
+        meta = self._new_item_metadata(what, metadata, n)
+        if histories is not None:
+            if len(histories) != n:
+                raise ValueError(f"{what}: {len(histories)} histories for {n} new items")
+            hoff, husers, hrank = self._history_csr(histories, side='user')
+        ulist = user_ids.tolist() if hasattr(user_ids, "tolist") else list(user_ids)
+        users = self._dense_users(ulist) if ulist else None
+        n_all = self.n_items + n
+        k = min(int(top_k), n_all)
+        if k <= 0 or not ulist:
+            return self._empty_topk(len(ulist), k, return_scores)
+        dev = _device()
+        self.net = self.net.eval()
+        tp = self.net.table_params()
+        metas, meta_lins = self._meta_tables()
+        item = torch.cat([tp[1].data, V.to(dev)])
+        item_lin = torch.cat([tp[3].data, b.to(dev).view(-1, 1)])
+        T, keep = ops.make_tables(tp[0].data, item, tp[2].data, item_lin, metas, meta_lins)
+        item_meta = None if meta is None else \
+            torch.cat([self._item_meta_dev(), torch.from_numpy(meta).to(torch.int32).to(dev)]).contiguous()
+        fold = ops.item_fold(self.net.NET, T, n_all, self.n_factors, dev, item_meta)
+        seen = self._seen_csr() if exclude_seen else None
+        if seen is not None and histories is not None and husers.size:
+            # the CSR rows are longest first: history row hrank[j] belongs to new item j, catalogue row n_items + j
+            off_j = np.concatenate([[0], np.cumsum(np.diff(hoff)[hrank])]).astype(np.int64)
+            users_j = np.concatenate([husers[hoff[r]:hoff[r + 1]] for r in hrank])
+            eo, ei = self._extended_seen_csr(seen[0].cpu().numpy(), seen[1].cpu().numpy(), off_j, users_j, self.n_items)
+            seen = (torch.from_numpy(eo).to(dev), torch.from_numpy(ei).to(dev))
+        ids, scores, _ = self._chunked(lambda us: ops.retrieve_topk(self.net.NET, T, fold, us, k, seen),
+                                       users.to(dev))
+        ids = ids.cpu()
+        new = ids >= self.n_items
+        new_at = ids[new] - self.n_items
+        ids = self._original_ids(torch.where(new, torch.full_like(ids, -1), ids), index)
+        ids[new] = torch.from_numpy(new_ids)[new_at]
+        return (ids, scores.cpu()) if return_scores else ids
 
     # ------------------------------------------------------------------------------------------------ neighbours
     def _dense_rows(self, ids, index, n_rows, what):

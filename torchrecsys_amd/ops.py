@@ -847,6 +847,43 @@ def fold_in_users(net, fold, n_items, D, hist, loss, epochs, lr, l2, seed, shuff
     return U, b, ls
 
 
+def fold_in_items(net, T, fold, n_items, new_fold, hist, stream_user, stream_item, seen, loss, epochs, lr, l2,
+                  negative_visits, seed, shuffle, reject_seen, max_tries, want_loss=False, err_flag=None):
+    """New item rows fitted to user histories against the frozen user table and item fold (trs_fold_in_items; the
+    update rule is in include/trs.h "item fold-in").  T: the model's tables (the user side is read); fold: its item_fold
+    buffer of (n_items, D); new_fold: an item_fold buffer of (n, D) holding the new items' metadata parts; hist:
+    (offsets int64 (n+1,), users int32) GPU CSR of sorted, distinct dense user rows; stream_user / stream_item: the
+    int32 train interactions (None with negative_visits == 0); seen: the model's seen CSR or None.  Returns GPU tensors
+    (V (n, D) fp32, b (n,) fp32, loss (epochs, n) fp32 or None).  err_flag: optional int32 GPU tensor whose bit 0 is set
+    by a user or stream id outside its table."""
+    lib = _lib.load()
+    off, users = hist
+    _dev(fold, "item fold", torch.uint8)
+    _dev(new_fold, "new-item fold", torch.uint8)
+    _dev(stream_user, "train users", torch.int32)
+    _dev(stream_item, "train items", torch.int32)
+    if (stream_user is None) != (stream_item is None) or \
+            (stream_user is not None and stream_user.numel() != stream_item.numel()):
+        raise ValueError("stream_user and stream_item must be given together, with the same length")
+    dev = fold.device
+    n, D = off.numel() - 1, int(T.D)
+    if users.numel() == 0:  # every history empty: the kernel reads no user, but the CSR may not carry a NULL array
+        users = torch.zeros(1, dtype=torch.int32, device=dev)
+    cs = csr(off, users)
+    sn = csr(*seen) if seen is not None else None
+    V = torch.empty((n, D), dtype=torch.float32, device=dev)
+    b = torch.empty((n,), dtype=torch.float32, device=dev)
+    ls = torch.empty((int(epochs), n), dtype=torch.float32, device=dev) if want_loss else None
+    check(lib.trs_fold_in_items(NET_ID[net], C.byref(T), ptr(fold), fold.numel(), int(n_items), ptr(new_fold),
+                                new_fold.numel(), C.byref(cs), ptr(stream_user), ptr(stream_item),
+                                0 if stream_user is None else stream_user.numel(),
+                                C.byref(sn) if sn is not None else None, _lib.LOSS_ID[loss], int(epochs), float(lr),
+                                float(l2), int(negative_visits), int(seed) & 0xFFFFFFFFFFFFFFFF, int(bool(shuffle)),
+                                int(bool(reject_seen)), int(max_tries), ptr(V), ptr(b), ptr(ls),
+                                ptr(_dev(err_flag, "err_flag", torch.int32)), _stream()), "trs_fold_in_items")
+    return V, b, ls
+
+
 def item_ranks(net, T, fold, users, targets_csr, seen=None, want_values=False):
     """Exact ranks of each query's target items over the catalogue (trs_item_ranks; the definition is in
     include/trs.h "exact ranks").  users: dense int64 GPU tensor; targets_csr: (offsets int64 (n + 1,), items int32) GPU
