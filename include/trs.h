@@ -101,7 +101,7 @@ const char* trs_last_error(void);
  *      the in-batch softmax group, trs_batch_prepare_mined, trs_batch_prepare_multi, trs_score_multi_fwd_bwd,
  *      trs_score_warp_fwd_bwd, TRS_LOSS_WARP, trs_stage_add_l2, trs_neighbour_fold, trs_neighbours_topk,
  *      trs_fold_in_users, trs_item_ranks, trs_item_ranks_workspace_bytes, trs_mmr_rerank, trs_list_ild,
- *      trs_fold_in_items.) */
+ *      trs_fold_in_items, trs_als_gram, trs_als_gram_workspace_bytes, trs_als_solve.) */
 #define TRS_ABI_VERSION 6
 #define TRS_SYNC_WORDS 288
 #define TRS_SYNC_REBASE 0x40000000u /* arrivals after which trs_train_steps_sgd zeroes sync_dev and its host count */
@@ -753,6 +753,54 @@ int trs_fold_in_items(int net, const trs_tables* tables, const void* fold_dev, i
                       const trs_csr* seen, int32_t loss, int32_t epochs, float lr, float l2, int32_t negative_visits,
                       uint64_t seed, int32_t shuffle, int32_t reject_seen, int32_t max_tries, float* item_out_dev,
                       float* item_lin_out_dev, float* loss_out_dev, int32_t* err_flag_dev, void* stream);
+
+/* ------------------------------------------------------------------- implicit ALS (fit_als) */
+/* Weighted alternating least squares on implicit feedback (Hu, Koren, Volinsky, ICDM 2008): preference 1 with confidence
+ * 1 + alpha on the observed pairs, preference 0 with confidence 1 everywhere else.  One half-sweep re-solves every row of
+ * one table with the other table frozen: trs_als_gram once, then trs_als_solve once, for all rows.  Added without
+ * touching an existing signature or struct.
+ *
+ * trs_als_gram: G (D, D) = Y^T Y in fp32 of the first n rows and D columns of rows (row stride ld >= D floats).
+ *   Deterministic: the rows are cut into chunks of R = max(16, ceil(ceil(n / C) / 16) * 16) rows, C = 512 (D <= 128) |
+ *   256 (D > 128); the partial sum of a chunk is one fmaf chain per entry over the chunk's rows in ascending order, from
+ *   0; G[a][b] is the sum of the chunks' partials in ascending chunk order, from 0.  No atomics: the same input gives
+ *   the same bits, and G[a][b] == G[b][a].  workspace: trs_als_gram_workspace_bytes(n, D) = ceil(n / R) * D * D * 4
+ *   bytes.  n == 0 writes G = 0.
+ *   TRS_E_ARG, nothing launched: D outside 1..TRS_RETRIEVE_DMAX; n < 0 (or >= 2^31); ld < D; G_out NULL; with n > 0 a NULL
+ *   rows or workspace.
+ *
+ * trs_als_solve: Y = other_rows (n_other, D, row stride D) frozen, G (D, D, row stride D) as trs_als_gram wrote it for
+ *   Y, nbr the CSR of the n_rows rows to solve (off int64 (n_rows + 1), items int32: sorted, distinct rows of Y),
+ *   rows_inout (n_rows, D, row stride D) the start values, overwritten by the results.  One launch.  Per row h with
+ *   neighbour list N = items[off[h] .. off[h+1]):
+ *     |N| == 0   the row is set to exactly 0.
+ *     otherwise  at most cg_steps steps of conjugate gradient on A x = b from the row's current value x,
+ *                  A = G + lambda I + alpha sum_{i in N} y_i y_i^T,   b = (1 + alpha) sum_{i in N} y_i,
+ *                A never formed (the recurrence of the `implicit` package's GPU solver):
+ *                  A v   = ((G v)_d + lambda * v_d) + alpha * acc_d,  acc = sum_{i in N} (y_i . v) y_i
+ *                  b_d   = (1.0f + alpha) * s_d,  s = sum_{i in N} y_i
+ *                  r = b - A x;  p = r;  rho = r . r;  stop if rho < 1e-20
+ *                  per step:  a = rho / (p . A p);  x += a p;  r -= a A p;  rho' = r . r;  stop if rho' < 1e-20;
+ *                             p = r + (rho' / rho) p;  rho = rho'
+ *   sums       every product and sum is rounded to fp32 on its own (no fused multiply-add).  acc and s run over the
+ *              neighbours in CSR order, from 0.  (G v)_d = sum_e G[e][d] * v_e for e ascending, from 0 (row e of G is
+ *              read).  The order of a sum over d (y . v, r . r, p . A p) is the kernel's: per lane of the row's group of
+ *              Dp / 4 lanes (Dp = D rounded up to a power of two >= 16) the four products of columns 4l .. 4l+3 added in
+ *              ascending column order from the first product, then trs_group_sum (the xor butterfly of strides Dp/8 .. 1);
+ *              columns >= D count as 0.
+ *   purity     a row's result depends on its own list, its start value, Y, G, lambda, alpha and cg_steps only: not on h,
+ *              not on the other rows of the call.
+ * A neighbour id outside [0, n_other) is never used as an address: that neighbour is skipped (in acc and in s) and bit
+ * 0 of *err_flag_dev (may be NULL) is set.
+ * TRS_E_ARG, nothing launched: D outside 1..TRS_RETRIEVE_DMAX; cg_steps outside 1..256; lambda not finite or <= 0; alpha
+ * not finite or < 0; n_rows < 0; with n_rows > 0 n_other outside 1..2^31-1, a NULL other_rows / G / rows_inout, nbr NULL
+ * or with a NULL array, nbr->n_rows != n_rows.  n_rows == 0: TRS_OK, nothing launched. */
+int64_t trs_als_gram_workspace_bytes(int64_t n, int32_t D);
+int trs_als_gram(const float* rows_dev, int64_t n, int32_t D, int64_t ld, float* G_out_dev, void* workspace_dev,
+                 void* stream);
+int trs_als_solve(const float* other_rows_dev, int64_t n_other, int32_t D, const float* G_dev, const trs_csr* nbr,
+                  float lambda, float alpha, int32_t cg_steps, float* rows_inout_dev, int64_t n_rows,
+                  int32_t* err_flag_dev, void* stream);
 
 /* ------------------------------------------------- exact ranks (rank_items / evaluate_ranks) */
 /* Where given items land in a user's full ranking.  Added without touching an existing signature or struct.

@@ -180,6 +180,9 @@ PROTOTYPES = {
     "trs_fold_in_items": (C.c_int, [C.c_int, _T, _vp, _i64, _i64, _vp, _i64, C.POINTER(TrsCsr), _vp, _vp, _i64,
                                     C.POINTER(TrsCsr), _i32, _i32, _f, _f, _i32, _u64, _i32, _i32, _i32, _vp, _vp, _vp,
                                     _vp, _vp]),
+    "trs_als_gram_workspace_bytes": (C.c_int64, [_i64, _i32]),
+    "trs_als_gram": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _vp, _vp]),
+    "trs_als_solve": (C.c_int, [_vp, _i64, _i32, _vp, C.POINTER(TrsCsr), _f, _f, _i32, _vp, _i64, _vp, _vp]),
     "trs_item_ranks_workspace_bytes": (C.c_int64, [_i64, _i64]),
     "trs_item_ranks": (C.c_int, [C.c_int, _T, _vp, _i64, _vp, _i64, C.POINTER(TrsCsr), C.POINTER(TrsCsr), _vp, _vp, _vp,
                                  _i64, _vp]),

@@ -628,6 +628,115 @@ class TorchRecSys(torch.nn.Module):
         bufs = [b for b in self.net.buffers() if b.is_floating_point()]
         tdist.average_tables_([p.data for p in emb] + bufs)
 
+    # ------------------------------------------------------------------------------------------------ ALS
+    def _check_fit_als(self, iterations, regularization, alpha, cg_steps):
+        """Argument checks of fit_als (before any device work)."""
+        if self.net_type not in ('linear', 'fm'):
+            raise ValueError(f"fit_als needs net_type 'linear' or 'fm': with net_type={self.net_type!r} (mlp) a score "
+                             "is not the inner product of a user row and an item row")
+        if self.use_metadata:
+            raise ValueError("fit_als takes a model without metadata columns: with metadata an item is its row plus its "
+                             "metadata rows, and the alternating solves are no longer independent per row")
+        if self.n_factors > ops._lib.RETRIEVE_DMAX:
+            raise ValueError(f"fit_als takes n_factors <= {ops._lib.RETRIEVE_DMAX} (TRS_RETRIEVE_DMAX), got "
+                             f"{self.n_factors}")
+        if tdist.world_info()[1] > 1:
+            raise NotImplementedError("fit_als runs in a single process: under torch.distributed (world > 1) every rank "
+                                      "holds a shard of the interactions, and a row's solve needs all of its pairs")
+
+        def integer(v, name, lo, hi):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+                raise ValueError(f"{name} must be an integer in {lo}..{hi}, got {v!r}")
+
+        def number(v, name, positive):
+            ok = isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and math.isfinite(v)
+            f = float(np.float32(v)) if ok and abs(v) <= 3.4e38 else float("nan")  # the kernel takes it as fp32
+            if not (f > 0 if positive else f >= 0):
+                raise ValueError(f"{name} must be a finite number {'> 0' if positive else '>= 0'}, got {v!r}")
+        integer(iterations, "iterations", 1, 1 << 20)
+        integer(cg_steps, "cg_steps", 1, 256)
+        number(regularization, "regularization", True)
+        number(alpha, "alpha", False)
+
+    def _als_csrs(self):
+        """(user -> sorted items, item -> sorted users) CSRs of the train split's distinct pairs, built once."""
+        seen = self._seen_csr()
+        if 'seen_csr_items' not in self._dev_cache:
+            st = self._device_stream('train')
+            self._dev_cache['seen_csr_items'] = ops.Sampler.seen_csr(st['pos'], st['user'], self.n_items, self.n_users)
+        return seen, self._dev_cache['seen_csr_items']
+
+    def _als_loss(self, X, Y, GX, GY, pairs, lam, alpha):
+        """The ALS objective (fit_als docstring) as a Python float: the Gram term and the norms from the fp32 Gram
+        matrices, the observed term from one fp32 scoring pass over the train pairs (1-wide tables are zero: the Linear
+        score is <x_u, y_i>), everything summed in float64."""
+        dev = X.device
+        users, items = pairs
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        Bt, keep = ops.make_batch(users, items, None, None, None, err)
+        s, _ = ops.score_forward('linear', self.net.tables(), Bt, users.numel(), dev, want_neg=False)
+        check_err_flag(err, "fit_als")
+        s = s.double()
+        observed = ((1.0 + alpha) * (1.0 - s) ** 2 - s ** 2).sum()
+        gx, gy = GX.double(), GY.double()
+        return float((gx * gy).sum() + observed + lam * (torch.diagonal(gx).sum() + torch.diagonal(gy).sum()))
+
+    @_host_side
+    def fit_als(self, iterations: int = 15, regularization: float = 0.1, alpha: float = 10.0, cg_steps: int = 3,
+                return_loss: bool = False):
+        """Implicit-feedback weighted alternating least squares (Hu, Koren, Volinsky 2008; the main model of the
+        `implicit` package) on the train split's distinct (user, item) pairs: preference 1 with confidence 1 + alpha on
+        those pairs, preference 0 with confidence 1 everywhere else, L2 coefficient `regularization` on both tables.  No
+        learning rate, no negative sampler; deterministic.
+
+        One iteration is the user half-sweep, then the item half-sweep.  A half-sweep is two launches: the Gram matrix
+        of the frozen table (trs_als_gram), then every row of the other table takes at most cg_steps conjugate-gradient
+        steps from its current value (trs_als_solve; the exact rule is in include/trs.h "implicit ALS").  A row without
+        a pair becomes 0.  The sweeps start from the model's current user / item tables — the seeded init, or what fit()
+        left — so fit_als(1) called five times equals fit_als(5) bit for bit.
+
+        Writes the two n_factors-wide tables in place and zeroes the 1-wide tables (user_bias / item_bias, or FM's
+        linear_user / linear_item) before the first sweep: the Linear score and FM's logit are then both <x_u, y_i>, and
+        recommend(), rank_items(), similar_items(), recommend_diverse(), evaluate_ranking() and the fold-in calls rank
+        by the ALS score.  Optimiser state is not touched; nothing derived from the tables is cached across calls.
+
+        return_loss: a float64 CPU tensor of iterations + 1 values of
+            L = sum_u x_u^T G_Y x_u + sum_{(u,i) observed} [(1 + alpha)(1 - s_ui)^2 - s_ui^2] + lambda (|X|^2 + |Y|^2),
+        s = <x_u, y_i>, G_Y = Y^T Y, the first taken before the first sweep (after the 1-wide tables are zeroed).  The
+        first term is the Frobenius product of the two Gram matrices; the observed term comes from one scoring pass
+        over the train pairs; sums in float64.  Without return_loss none of this runs.
+
+        net_type 'linear' or 'fm' without metadata columns, n_factors <= TRS_RETRIEVE_DMAX, single process: ValueError /
+        NotImplementedError otherwise, before any device work."""
+        self._check_fit_als(iterations, regularization, alpha, cg_steps)
+        iterations, cg_steps = int(iterations), int(cg_steps)
+        lam, alpha = float(regularization), float(alpha)
+        dev = _device()
+        ps = self.net.table_params()
+        X, Y = ps[0].data, ps[1].data
+        by_user, by_item = self._als_csrs()
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        with torch.no_grad():
+            ps[2].data.zero_()
+            ps[3].data.zero_()
+            losses = []
+            if return_loss:
+                off, items = by_user
+                pairs = (torch.repeat_interleave(torch.arange(self.n_users, dtype=torch.int32, device=dev),
+                                                 off[1:] - off[:-1]), items)
+                GX = ops.als_gram(X)
+            for _ in range(iterations):
+                GY = ops.als_gram(Y)
+                if return_loss:
+                    losses.append(self._als_loss(X, Y, GX, GY, pairs, lam, alpha))
+                ops.als_solve(Y, GY, by_user, lam, alpha, cg_steps, X, err)
+                GX = ops.als_gram(X)
+                ops.als_solve(X, GX, by_item, lam, alpha, cg_steps, Y, err)
+            if return_loss:
+                losses.append(self._als_loss(X, Y, GX, ops.als_gram(Y), pairs, lam, alpha))
+        check_err_flag(err, "fit_als")
+        return torch.tensor(losses, dtype=torch.float64) if return_loss else None
+
     # ------------------------------------------------------------------------------------------------ evaluate
     @_host_side
     def evaluate(self, batch_size=512, eval_metrics=['loss', 'auc']):

@@ -884,6 +884,51 @@ def fold_in_items(net, T, fold, n_items, new_fold, hist, stream_user, stream_ite
     return V, b, ls
 
 
+def als_gram(rows, n=None, D=None):
+    """G (D, D) fp32 = Y^T Y of the first n rows and D columns of the fp32 GPU matrix `rows` (trs_als_gram:
+    deterministic, no atomics; include/trs.h "implicit ALS")."""
+    lib = _lib.load()
+    _dev(rows, "ALS rows", torch.float32)
+    if rows.dim() != 2:
+        raise ValueError(f"rows must be an (n, ld) matrix, got {tuple(rows.shape)}")
+    n = rows.shape[0] if n is None else int(n)
+    D = rows.shape[1] if D is None else int(D)
+    if not 0 <= n <= rows.shape[0] or not 1 <= D <= rows.shape[1]:
+        raise ValueError(f"n={n}, D={D} do not fit rows of shape {tuple(rows.shape)}")
+    G = torch.empty((D, D), dtype=torch.float32, device=rows.device)
+    ws = torch.empty(max(lib.trs_als_gram_workspace_bytes(n, D), 8), dtype=torch.uint8, device=rows.device)
+    check(lib.trs_als_gram(ptr(rows), n, D, rows.shape[1], ptr(G), ptr(ws), _stream()), "trs_als_gram")
+    return G
+
+
+def als_solve(other, G, nbr, regularization, alpha, cg_steps, rows_inout, err_flag=None):
+    """One ALS half-sweep in place (trs_als_solve; the rule is in include/trs.h "implicit ALS"): every row of rows_inout
+    (n_rows, D) takes at most cg_steps conjugate-gradient steps from its current value towards its weighted
+    least-squares solution against the frozen table `other` (n_other, D) with Gram matrix G (D, D) = als_gram(other).
+    nbr: (offsets int64 (n_rows + 1,), ids int32) GPU CSR of sorted, distinct rows of `other`.  err_flag: optional int32
+    GPU tensor whose bit 0 is set by an id outside [0, n_other).  Returns rows_inout."""
+    lib = _lib.load()
+    off, items = nbr
+    _dev(other, "frozen table", torch.float32)
+    _dev(G, "Gram matrix", torch.float32)
+    _dev(rows_inout, "rows to solve", torch.float32)
+    if other.dim() != 2 or rows_inout.dim() != 2 or other.shape[1] != rows_inout.shape[1]:
+        raise ValueError("the frozen table and the rows to solve must be (n, D) with the same D")
+    D = other.shape[1]
+    if tuple(G.shape) != (D, D):
+        raise ValueError(f"G must be ({D}, {D}), got {tuple(G.shape)}")
+    n_rows = rows_inout.shape[0]
+    if off.numel() != n_rows + 1:
+        raise ValueError(f"neighbour CSR has {off.numel() - 1} rows for {n_rows} rows to solve")
+    if items.numel() == 0:  # every list empty: the kernel reads no id, but the CSR may not carry a NULL array
+        items = torch.zeros(1, dtype=torch.int32, device=other.device)
+    cs = csr(off, items)
+    check(lib.trs_als_solve(ptr(other), other.shape[0], D, ptr(G), C.byref(cs), float(regularization), float(alpha),
+                            int(cg_steps), ptr(rows_inout), n_rows, ptr(_dev(err_flag, "err_flag", torch.int32)),
+                            _stream()), "trs_als_solve")
+    return rows_inout
+
+
 def item_ranks(net, T, fold, users, targets_csr, seen=None, want_values=False):
     """Exact ranks of each query's target items over the catalogue (trs_item_ranks; the definition is in
     include/trs.h "exact ranks").  users: dense int64 GPU tensor; targets_csr: (offsets int64 (n + 1,), items int32) GPU
