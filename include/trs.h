@@ -340,6 +340,9 @@ int trs_score_backward(int net, const trs_tables* tables, const trs_batch* batch
  *       remaining references of duplicated rows, by float atomics.  (One all-atomic launch when scratch is NULL.)
  *   K3  user[u] -= lr*du (+ 1-wide user term): plain for rows referenced once in the step, atomics for the others.
  * Same results as trs_score_fwd_bwd + trs_score_sgd_update (to summation order of duplicate rows).
+ * That is the step's "marks" form.  The arguments select one of four forms, resolved once per call: marks; sorted item
+ * references with marks for the users; sorted references with user-duplicate flags (adaptive rules, metadata); both
+ * flag arrays without sorted references (flag mode) — see trs_train_args below and the head of csrc/fast_step.hip.
  * scratch: NULL or trs_train_scratch_bytes(n_users, n_items, batch, D) bytes, zero-initialised once; first_stamp: step counter
  * of the first step, non-zero, strictly increasing over the life of the scratch (re-zero the scratch before it wraps).
  * events: NULL, or 4*n_steps hipEvent_t handles recorded at the K1 | K2a+K2b | K3 boundaries of each step (a step whose handles are NULL is not timed) (bench.py). */
@@ -435,8 +438,10 @@ typedef struct trs_train_args {
   /* presorted two-launch step (trs_epoch_presort / trs_epoch_user_dups outputs, offset to the call's first batch) */
   const void* sorted_keys_dev;
   const void* sorted_vals_dev;
-  int32_t key_bytes;
-  int32_t ukey_bytes;
+  int32_t key_bytes;         /* width of a sorted item key: 4 with sorted_keys_dev (what trs_epoch_presort_sizes reports),
+                                0 without.  The sorted references carry 32-bit keys: 8 is refused (TRS_E_ARG). */
+  int32_t ukey_bytes;        /* the same for sorted_ukeys_dev: 4 with the pairs (trs_epoch_user_dups), 0 without; 8 is
+                                refused */
   const uint8_t* user_dup_flags_dev; /* (n_steps*batch) 1: the triple's user has another reference in its batch */
   const uint8_t* item_dup_flags_dev; /* (n_steps*batch, 2) NULL, or per triple {pos, neg}: 1 = the item row has another
                                         reference in the batch.  Given (plain SGD, no metadata): K1 also applies the
@@ -525,6 +530,8 @@ int trs_epoch_user_dups_sizes(int64_t n_batches, int64_t batch, int64_t n_users,
 int trs_epoch_user_dups(const int32_t* user_dev, int64_t n_batches, int64_t batch, int64_t n_users, void* ukeys_dev,
                         void* uvals_dev, void* temp_dev, int64_t temp_bytes, uint8_t* flags_out_dev,
                         void** sorted_ukeys_out, void** sorted_uvals_out, int32_t* ukey_bytes_out, void* stream);
+/* Buffer sizes of trs_epoch_presort.  *key_bytes_out is always 4: keys are uint32 item rows, the only width
+ * trs_train_steps_sgd takes (trs_train_args.key_bytes). */
 int trs_epoch_presort_sizes(int64_t n_batches, int64_t batch, int64_t n_items, int64_t* key_bytes_out,
                             int64_t* keys_total_bytes_out, int64_t* vals_total_bytes_out, int64_t* temp_bytes_out);
 int trs_epoch_presort(const int32_t* stream_ui_dev, const int32_t* neg_static_dev, int64_t N, uint64_t shuffle_key,

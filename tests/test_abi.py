@@ -195,3 +195,41 @@ def test_staged_gradient_kernels_keep_their_waves_per_simd(tmp_path):
     for n, (vgpr, scratch) in seen.items():
         waves = min(8, 512 // (8 * -(-vgpr // 8)))  # 512 VGPRs per lane and SIMD, allocated in blocks of 8
         assert scratch == 0 and waves >= before[n], (n, vgpr, scratch, waves, before[n])
+
+
+def test_step_kernels_are_the_ones_shipped_before_the_sort_keys_became_32_bit_only(tmp_path):
+    """Register guard for the code objects of csrc/fast_step.hip and csrc/presort.hip (no GPU, no recompilation).
+    tests/step_kernels.json holds (VGPRs, scratch) of their kernels as built before the sorted references lost their
+    key-type template parameter, keyed by the names the kernels have now.  The source of every kernel that is launched
+    did not change, so EQUALITY is required: any difference means a kernel was altered by accident.  Gone for good:
+    every instance with a 64-bit key type and the stand-alone sorted_user_dup_update_kernel (never launched: the fused
+    kernel runs its body) — presort.hip's code object went from 296 kernels to 200."""
+    import json
+    import re
+    found = _shipped_kernel_registers(tmp_path)
+    before = json.load(open(os.path.join(ROOT, "tests", "step_kernels.json")))
+
+    def family(n):  # the kernel's own identifier in its mangled name (None: an identifier with digits, none of ours)
+        m = re.search(r"(?<=\d)([a-z_]+_kernel)", n)
+        return m.group(1) if m else None
+
+    for obj in ("fast_step", "presort"):
+        for n, want in before[obj].items():
+            assert n in found, (obj, n)
+            assert list(found[n]) == want, (obj, n, found[n], want)
+    unchanged = {"fwd_stage_kernel", "flagged_update_kernel", "item_owner_update_kernel", "user_plain_update_kernel",
+                 "user_dup_update_kernel", "item_update_kernel", "user_update_kernel", "meta_stage_kernel",
+                 "pair_scores_kernel", "score_kernel", "sorted_updates_fused_kernel", "cut_rows_apply_kernel",
+                 "batch_flags_kernel", "batch_group_items_kernel", "item_flags_kernel", "meta_refs_kernel"}
+    lost_key_type = {"epoch_refs_kernel", "sorted_item_update_kernel", "sorted_item_update_staged_kernel",
+                     "user_flags_kernel"}
+    fams = {obj: {family(n) for n in before[obj]} for obj in before}
+    assert fams["fast_step"] | fams["presort"] == unchanged | lost_key_type
+    assert fams["presort"] >= lost_key_type
+    # no kernel of these families beyond the fixture's (score_kernel also lives in other code objects: presence only)
+    for obj in before:
+        shipped = {n for n in found if family(n) in fams[obj] - {"score_kernel"}}
+        assert shipped == {n for n in before[obj] if family(n) != "score_kernel"}, (obj, sorted(shipped ^ set(before[obj]))[:5])
+    assert len(before["presort"]) == 200
+    assert not [n for n in found if "sorted_user_dup_update_kernel" in n]
+    assert not [n for n in found if family(n) in lost_key_type and re.search(r"_kernelI[jm]", n)]  # no key-type argument

@@ -364,7 +364,7 @@ PRESORTED_CELLS = [(n, D, True) for n, D in cells("presorted two-launch step", A
 
 @pytest.mark.parametrize("net,D,inline_user", PRESORTED_CELLS)
 def test_presorted_two_launch_step(net, D, inline_user):
-    """trs_epoch_presort + the sorted-run updates (trs_launch_sorted_item_update, _updates_fused, _user_dup_update), one hot
+    """trs_epoch_presort + the sorted-run updates (trs_launch_sorted_item_update, trs_launch_sorted_updates_fused), one hot
     item: 3 batches in one C call == oracle steps, as test_presorted_item_update_matches_oracle."""
     ops = _ops()
     case = two_launch_step_case(net, D)

@@ -1,21 +1,44 @@
-// fast_step.hip — the specialised SGD training step of the Linear / FM scorers without metadata (M = 0), and the
-// C-side step loop (one C call runs many steps: no per-step host work beyond four kernel launches).
+// fast_step.hip — the specialised training step of the Linear / FM scorers and the C-side step loop (one C call runs
+// many steps: no per-step host work beyond the kernel launches).
 //
-// Exact reference semantics (every gradient of a step is taken at the PRE-update tables, reference model.py:188-200)
-// with the least staging that allows it:
-//   K1  fwd_stage    reads u, i, j rows (+1-wide terms) once — software-pipelined: the rows of the group's next triple
-//                    and the ids of the one after are in flight while the current triple is reduced; [optionally]
-//                    derives the batch from the resident interaction stream (Feistel shuffle + Philox sampler,
-//                    = trs_batch_prepare); writes the per-triple score gradients gz+ / gz- (FM: through the sigmoid), the
-//                    user-row gradient du (B,D), the loss sum, and an ownership mark per referenced row.
-//   K2a item_update<1> re-reads the still-unmodified user rows (L2 / Infinity-Cache hot) and applies
-//                    item[i] -= lr*gz+ * u, item[j] -= lr*gz- * u (+ 1-wide terms) for the references that OWN their
-//                    row (their K1 mark survived: exactly one per distinct row) with plain whole-row read-modify-writes;
-//                    stamps user rows that have several references (marks and stamps carry the step number: no resets).
-//   K2b item_update<2> the other references of duplicated item rows add with float atomics (one 256-B wave-instruction
-//                    per row segment).  K2a/K2b touch only item tables.
-//   K3  user_update  user[u] -= lr*du (+ 1-wide term) from the staged rows: plain for rows referenced once, atomics for
-//                    stamped rows.  Touches only user tables.
+// Exact reference semantics: every gradient of a step is taken at the PRE-update tables (reference model.py:188-200),
+// so a kernel may only write a row that no other reference of the batch will still read.  K1 reads the u, i, j rows
+// (+1-wide terms) once — software-pipelined: the rows of the group's next triple and the ids of the one after are in
+// flight while the current triple is reduced — and writes the per-triple score gradients gz+ / gz- (FM: through the
+// sigmoid), the loss sum, and what the updates behind it need.  trs_train_steps_sgd resolves its arguments once per
+// call (resolve_step_plan) into one of FOUR FORMS; the plan alone decides what a step launches:
+//
+//   marks          No sorted references and not both flag arrays.  Ids derived by K1 from the resident interaction stream
+//                  (Feistel shuffle + Philox sampler, = trs_batch_prepare) or given.  K1 = fwd_stage_kernel<INL 0>
+//                  stages the user-row gradient du (B,D) and an ownership mark per referenced row (marks and stamps
+//                  carry the step number: no resets).  Then launch_updates: item_owner_update_kernel (the references
+//                  that OWN their row — their K1 mark survived, exactly one per distinct row — with plain whole-row
+//                  read-modify-writes; stamps user rows that have several references), item_update_kernel<2> (the other
+//                  references of duplicated item rows: float atomics), user_plain_update_kernel (plain for rows
+//                  referenced once, atomics for stamped rows).  Without scratch: item_update_kernel<0> +
+//                  user_update_kernel, every update atomic.
+//                  Reached by: engine.fast_stream_steps (the presort buffers do not fit), engine.fast_array_steps,
+//                  engine.step() (the epoch's last partial batch, the mined per-step loop).
+//   sorted, marks  Sorted item references (trs_epoch_presort), no user flags.  K1 = <INL 0> marking users only;
+//                  sorted_item_update_kernel (presort.hip: one plain read-modify-write per run of equal item rows, user
+//                  rows read from the still-unmodified table), then user_plain_update_kernel.
+//                  Reached by: callers of ops.train_steps_sgd that pass sorted references without user_dup (the kernel
+//                  tests); the engine always has the flags.
+//   sorted         Sorted item references + per-position user-duplicate flags (the dense regime, every adaptive rule,
+//                  every metadata scorer).  K1 applies the user update itself for users referenced once and stages the
+//                  OLD user row: <INL 1>, <INL 1, OPT> for SparseAdam / Adagrad, <INL 2> with item flags (K1 also
+//                  takes the item references that are alone on their row); meta_stage_kernel or score_kernel<MODE 2>
+//                  with metadata.  Then ONE launch, sorted_updates_fused_kernel (item runs + duplicated users: sorted
+//                  (batch,user) pairs, or float atomics for the flagged users when the pairs are omitted), and for
+//                  metadata one sorted-run launch per column or an atomic scatter of the staged fields.
+//                  Reached by: engine.fast_sorted_steps with an ops.EpochPresort.
+//   flags          Both flag arrays (trs_epoch_flags), no sorted references: the sparse regime.  K1 updates every
+//                  unflagged row in place.  <INL 3> = the whole step in one launch, when an arrival counter is given,
+//                  the batch takes at most DEFER_ITERS iterations and the grid is resident at once
+//                  (launch_fwd_stage asks); else <INL 2> + flagged_update_kernel (float atomics for the flagged
+//                  references).
+//                  Reached by: engine.fast_sorted_steps with an ops.EpochFlags (ops.FlagStepCall).
+//
 // Float atomics run at ~1.3 TB/s chip-wide against ~6 TB/s for plain stores (MI355X_MICROARCH.md "Global float
 // atomics"), so every reference that is provably alone on its row takes the plain path.
 #include "score_kernels.h"
@@ -1465,9 +1488,27 @@ static int64_t defer_resident_cap(KernelT kernel) {
   return per_cu > 0 ? (int64_t)per_cu * cus : 0;
 }
 
+// What one call of trs_train_steps_sgd launches per step: resolved ONCE from its arguments (resolve_step_plan).  The
+// step loop, the four step_* functions and launch_fwd_stage decide by these fields and by nothing else.
+enum StepForm { STEP_MARKS, STEP_SORTED_MARKS, STEP_SORTED, STEP_FLAGS };  // (the file header describes them)
+struct StepPlan {
+  StepForm form;
+  int src;           // K1's ids: 0 given, 1 resident stream + dynamic sampler, 2 resident stream + static negatives
+  int inl;           // fwd_stage_kernel's INL; 3: one launch where the grid is resident (launch_fwd_stage asks), else INL 2
+  int item_bits;     // sorted forms: bits of an item row in a key
+  bool owners;       // marks: scratch given — owner / plain update kernels (false: every update is atomic)
+  bool adaptive;     // sorted: SparseAdam / Adagrad
+  bool user_pairs;   // sorted: the slice's sorted (batch,user) pairs are given (false: flagged users take float atomics)
+  bool meta;         // sorted: K1 is a metadata scorer ...
+  bool meta_ids;     //   ... that reads the slice's metadata ids by position,
+  bool meta_sorted;  //   ... and whose columns go through sorted runs (false: atomic scatter of the fields K1 staged)
+  bool sync;         // flags: an arrival counter is given (inl == 3)
+  bool nflag;        // flags: flagged-first batches with their counts
+};
+
 template <int NET>
-static int launch_fwd_stage(const FastArgs& a, hipStream_t s, uint32_t* deferred = nullptr) {
-  if (deferred) *deferred = 0;  // > 0: INL 3 was launched with that many workgroups (= arrivals on a.sync)
+static int launch_fwd_stage(const FastArgs& a, const StepPlan& p, hipStream_t s, uint32_t* deferred) {
+  *deferred = 0;  // > 0: INL 3 was launched with that many workgroups (= arrivals on a.sync)
   RowCfg c;
   TRS_TRY(row_cfg_for("launch_fwd_stage", a.T.D, c));
   const int tpw = TRS_WAVE / c.g;
@@ -1482,7 +1523,6 @@ static int launch_fwd_stage(const FastArgs& a, hipStream_t s, uint32_t* deferred
   int64_t grid = ((a.B + tpw - 1) / tpw + 4 * iters - 1) / (4 * iters);
   if (grid < 1) grid = 1;
   if (grid > 4096) grid = 4096;
-  const int src = !a.from_stream ? 0 : (a.neg_static ? 2 : 1);
   // one-launch flag mode: user rows loaded AND stored nontemporally when the user table is far beyond the Infinity Cache
   // (as in the scoring pass, trs_launch_pair_scores): c4, 1 024-step windows, 37.0-37.4 -> 36.2-36.3 us per step (loads
   // alone: no change).  TRS_K1_NT = 0 | 1 | 3 forces a setting.
@@ -1493,11 +1533,13 @@ static int launch_fwd_stage(const FastArgs& a, hipStream_t s, uint32_t* deferred
     constexpr int VV = V(), GG = G(), KK = K();
     auto launch = [&](auto FULL) {
       constexpr bool FU = FULL();
-      if (src == 0 && a.udup_pos && a.o.kind == OPT_ADAM)
+      if (p.inl == 1 && a.o.kind == OPT_ADAM)
         hipLaunchKernelGGL((fwd_stage_kernel<NET, VV, GG, KK, 0, FU, 1, OPT_ADAM>), gr, bl, 0, s, a);
-      else if (src == 0 && a.udup_pos && a.o.kind == OPT_ADAGRAD)
+      else if (p.inl == 1 && a.o.kind == OPT_ADAGRAD)
         hipLaunchKernelGGL((fwd_stage_kernel<NET, VV, GG, KK, 0, FU, 1, OPT_ADAGRAD>), gr, bl, 0, s, a);
-      else if (src == 0 && a.udup_pos && a.idup_pos && a.sync && deferred && iters <= DEFER_ITERS) {
+      else if (p.inl == 1)
+        hipLaunchKernelGGL((fwd_stage_kernel<NET, VV, GG, KK, 0, FU, 1>), gr, bl, 0, s, a);
+      else if (p.inl == 3 && iters <= DEFER_ITERS) {
         // one value per instantiation (NET, shape, FULL): the residency of THIS kernel, asked once
         static const int64_t cap = defer_resident_cap(fwd_stage_kernel<NET, VV, GG, KK, 0, FU, 3>);
         if (grid <= cap) {
@@ -1514,12 +1556,10 @@ static int launch_fwd_stage(const FastArgs& a, hipStream_t s, uint32_t* deferred
           *deferred = (uint32_t)grid;
         } else
           hipLaunchKernelGGL((fwd_stage_kernel<NET, VV, GG, KK, 0, FU, 2>), gr, bl, 0, s, a);
-      } else if (src == 0 && a.udup_pos && a.idup_pos)
+      } else if (p.inl >= 2)
         hipLaunchKernelGGL((fwd_stage_kernel<NET, VV, GG, KK, 0, FU, 2>), gr, bl, 0, s, a);
-      else if (src == 0 && a.udup_pos)
-        hipLaunchKernelGGL((fwd_stage_kernel<NET, VV, GG, KK, 0, FU, 1>), gr, bl, 0, s, a);
-      else if (src == 0) hipLaunchKernelGGL((fwd_stage_kernel<NET, VV, GG, KK, 0, FU, 0>), gr, bl, 0, s, a);
-      else if (src == 1) hipLaunchKernelGGL((fwd_stage_kernel<NET, VV, GG, KK, 1, FU, 0>), gr, bl, 0, s, a);
+      else if (p.src == 0) hipLaunchKernelGGL((fwd_stage_kernel<NET, VV, GG, KK, 0, FU, 0>), gr, bl, 0, s, a);
+      else if (p.src == 1) hipLaunchKernelGGL((fwd_stage_kernel<NET, VV, GG, KK, 1, FU, 0>), gr, bl, 0, s, a);
       else hipLaunchKernelGGL((fwd_stage_kernel<NET, VV, GG, KK, 2, FU, 0>), gr, bl, 0, s, a);
     };
     if (VV * GG * KK == a.T.D) launch(std::true_type{});
@@ -1561,9 +1601,11 @@ static int launch_plain(const FastArgs& a, hipStream_t s) {
   });
 }
 
-static int launch_updates(const FastArgs& a, hipStream_t s, hipEvent_t ev_k3) {
+// The marks form behind K1.  owners: item_owner_update (plain, the owning references), item_update<2> (atomics, the
+// others), user_plain_update; else item_update<0> + user_update, all atomic.  ev_k3 sits between items and users.
+static int launch_updates(const FastArgs& a, bool owners, hipStream_t s, hipEvent_t ev_k3) {
   const int D = a.T.D;
-  if (a.uown) {
+  if (owners) {
     int rc = launch_plain<0>(a, s);  // K2a: owners, plain
     if (rc) return rc;
   }
@@ -1571,7 +1613,7 @@ static int launch_updates(const FastArgs& a, hipStream_t s, hipEvent_t ev_k3) {
   {                                                                                                  \
     constexpr int PER = (TRS_WAVE / L) * U;                                                          \
     const dim3 gr(trs_grid((a.B + PER - 1) / PER, TRS_BLOCK / TRS_WAVE)), bl(TRS_BLOCK);             \
-    if (a.uown) {                                                                                    \
+    if (owners) {                                                                                    \
       hipLaunchKernelGGL((item_update_kernel<L, KD, U, 2>), gr, bl, 0, s, a);                        \
       if (ev_k3) (void)hipEventRecord(ev_k3, s);                                                     \
     } else {                                                                                         \
@@ -1591,7 +1633,7 @@ static int launch_updates(const FastArgs& a, hipStream_t s, hipEvent_t ev_k3) {
   else TRS_UPD(1, 1, 1)
 #undef TRS_UPD
   TRS_CHECK_LAUNCH("item/user_update_kernel");
-  if (a.uown) return launch_plain<1>(a, s);  // K3: users, plain (atomics for the few duplicated rows)
+  if (owners) return launch_plain<1>(a, s);  // K3: users, plain (atomics for the few duplicated rows)
   return TRS_OK;
 }
 
@@ -1600,10 +1642,9 @@ static int launch_updates(const FastArgs& a, hipStream_t s, hipEvent_t ev_k3) {
 using namespace trs;
 
 // presort.hip
-int trs_launch_sorted_item_update(const trs_tables* tables, const void* keys_step, const void* vals_step, int key_bytes,
-                                  int64_t batch, int64_t item_bits, const float* gz, float lr, uint64_t* uown,
-                                  uint32_t* udup, uint32_t stamp, const float* ustage, const int32_t* user_ids,
-                                  hipStream_t s);
+int trs_launch_sorted_item_update(const trs_tables* tables, const void* keys_step, const void* vals_step, int64_t batch,
+                                  int64_t item_bits, const float* gz, float lr, uint64_t* uown, uint32_t* udup,
+                                  uint32_t stamp, const int32_t* user_ids, hipStream_t s);
 int trs_item_bits_for(int64_t n_items);
 int trs_launch_sorted_updates_fused(const trs_tables* tables, const void* keys_step, const void* vals_step,
                                     int64_t batch, int64_t item_bits, const float* gz, float lr, const float* ustage,
@@ -1616,9 +1657,6 @@ int trs_launch_sorted_meta_update(const trs_tables* tables, int m, float* lin_or
 // rows.hip
 int trs_launch_sgd_fields(int net, const trs_tables* tables, const trs_batch* batch, const float* grad_rows_dev,
                           const float* grad_lin_dev, float lr, int f_begin, void* stream);
-int trs_launch_sorted_user_dup_update(const trs_tables* tables, const void* ukeys_step, const void* uvals_step,
-                                      int key_bytes, int64_t batch, int64_t q0, const float* du, const float* gz,
-                                      float lr, hipStream_t s);
 
 // > 0: shape not handled (caller uses score_kernel<MODE 0>)
 int trs_launch_pair_scores(int net, const ScoreArgs* ap, hipStream_t s) {
@@ -1666,67 +1704,51 @@ extern "C" int64_t trs_train_scratch_bytes(int64_t n_users, int64_t n_items, int
   return 12 * (n_users + n_items);  // uown, iown (8 B per row) + udup, idup (4 B per row)
 }
 
-extern "C" int trs_train_steps_sgd(const trs_train_args* args, void* stream) {
+
+// Every argument check of trs_train_steps_sgd, and the plan the arguments resolve to.  Host only, no allocation.
+static int resolve_step_plan(const trs_train_args* args, StepPlan& p) {
   TRS_REQUIRE(args != nullptr, "trs_train_steps_sgd: NULL arguments");
-  const int net = args->net;
   const trs_tables* tables = args->tables;
-  const int32_t* stream_ui_dev = args->stream_ui_dev;
-  const int32_t* neg_static_dev = args->neg_static_dev;
-  const int64_t N = args->N;
-  const uint64_t shuffle_key = args->shuffle_key, sample_seed = args->sample_seed;
-  const int64_t first_pos = args->first_pos, batch = args->batch;
-  const int32_t n_steps = args->n_steps;
-  const float lr = args->lr;
-  int32_t *user_buf_dev = args->user_buf_dev, *pos_buf_dev = args->pos_buf_dev, *neg_buf_dev = args->neg_buf_dev;
-  float *gz_buf_dev = args->gz_buf_dev, *du_buf_dev = args->du_buf_dev, *loss_sums_dev = args->loss_sums_dev;
-  int32_t* err_flag_dev = args->err_flag_dev;
-  void* scratch_dev = args->scratch_dev;
-  const uint32_t first_stamp = args->first_stamp;
-  const void *sorted_keys_dev = args->sorted_keys_dev, *sorted_vals_dev = args->sorted_vals_dev;
-  const int32_t key_bytes = args->key_bytes, ukey_bytes = args->ukey_bytes;
-  const uint8_t* user_dup_flags_dev = args->user_dup_flags_dev;
-  float* ustage_buf_dev = args->ustage_buf_dev;
-  const void *sorted_ukeys_dev = args->sorted_ukeys_dev, *sorted_uvals_dev = args->sorted_uvals_dev;
-  const int64_t slice_pos0 = args->slice_pos0;
   const trs_opt* opt = args->opt;
   const trs_meta_stage* meta = args->meta;
-  void** events = args->events;
-  TRS_TRY(trs_check_net("trs_train_steps_sgd", net, tables));
+  const int64_t batch = args->batch;
+  const int32_t n_steps = args->n_steps;
+  TRS_TRY(trs_check_net("trs_train_steps_sgd", args->net, tables));
   TRS_REQUIRE((tables->M > 0) == (meta != nullptr), "trs_train_steps_sgd: metadata tables need the metadata staging");
   TRS_REQUIRE(tables->user && tables->item && tables->user_lin && tables->item_lin, "trs_train_steps_sgd: NULL table");
   TRS_REQUIRE(batch > 0 && batch < ((int64_t)1 << 30) && n_steps >= 0, "trs_train_steps_sgd: bad batch / n_steps");
-  TRS_REQUIRE(user_buf_dev && pos_buf_dev && neg_buf_dev && gz_buf_dev && du_buf_dev && loss_sums_dev,
+  TRS_REQUIRE(args->user_buf_dev && args->pos_buf_dev && args->neg_buf_dev && args->gz_buf_dev && args->du_buf_dev &&
+                  args->loss_sums_dev,
               "trs_train_steps_sgd: NULL buffer");
-  TRS_REQUIRE(!scratch_dev || (first_stamp != 0 && (uint64_t)first_stamp + (uint64_t)n_steps < 0xFFFFFFFFull),
+  TRS_REQUIRE(!args->scratch_dev ||
+                  (args->first_stamp != 0 && (uint64_t)args->first_stamp + (uint64_t)n_steps < 0xFFFFFFFFull),
               "trs_train_steps_sgd: stamps must be non-zero and must not wrap (zero the scratch and restart at 1)");
-  const bool from_stream = stream_ui_dev != nullptr;
-  const bool sorted = sorted_keys_dev != nullptr;
-  const bool inl = sorted && user_dup_flags_dev != nullptr;
+  TRS_REQUIRE(args->key_bytes != 8 && args->ukey_bytes != 8,
+              "trs_train_steps_sgd: the sorted references carry 32-bit keys (key_bytes / ukey_bytes must be 4, or 0 "
+              "without the arrays)");
+  const bool from_stream = args->stream_ui_dev != nullptr;
+  const bool sorted = args->sorted_keys_dev != nullptr;
+  const bool uflags = args->user_dup_flags_dev != nullptr, iflags = args->item_dup_flags_dev != nullptr;
+  const bool user_pairs = args->sorted_ukeys_dev != nullptr;
+  const bool adaptive = opt && opt->kind != TRS_OPT_SGD;
   if (sorted) {
-    TRS_REQUIRE(!from_stream && scratch_dev && sorted_vals_dev && (key_bytes == 4 || key_bytes == 8),
+    TRS_REQUIRE(!from_stream && args->scratch_dev && args->sorted_vals_dev && args->key_bytes == 4,
                 "trs_train_steps_sgd: the presorted mode needs the epoch's id arrays, scratch and sorted references");
-    TRS_REQUIRE(!inl || (ustage_buf_dev && ((sorted_ukeys_dev && sorted_uvals_dev && (ukey_bytes == 4 || ukey_bytes == 8)) ||
-                                            (!sorted_ukeys_dev && !(opt && opt->kind != TRS_OPT_SGD) && !meta && key_bytes == 4))),
+    TRS_REQUIRE(!uflags || (args->ustage_buf_dev && (user_pairs ? args->sorted_uvals_dev && args->ukey_bytes == 4
+                                                                 : !adaptive && !meta)),
                 "trs_train_steps_sgd: user-duplicate flags need the staging buffer and the slice's sorted (batch,user) "
                 "pairs (plain SGD without metadata may omit the pairs: flagged users then take float atomics)");
   }
-  const bool adaptive = opt && opt->kind != TRS_OPT_SGD;
-  // K1 takes the item references that are alone on their row: plain SGD without metadata on the fused two-launch step
-  // flag mode (sparse regime): both flag arrays, no sorted references — K1 takes every reference that is alone on its
-  // row, the flagged ones follow in flagged_update_kernel
-  const bool flgm = !sorted && user_dup_flags_dev && args->item_dup_flags_dev;
-  if (flgm)
-    TRS_REQUIRE(!from_stream && !adaptive && !meta && ustage_buf_dev,
+  const bool flags_form = !sorted && uflags && iflags;
+  if (flags_form)
+    TRS_REQUIRE(!from_stream && !adaptive && !meta && args->ustage_buf_dev,
                 "trs_train_steps_sgd: the flag mode takes given ids, both flag arrays and the (batch,D) staging buffer "
                 "(plain SGD, no metadata, no sorted references)");
-  const bool item_inl = args->item_dup_flags_dev && inl && !adaptive && !meta && key_bytes == 4 &&
-                        (ukey_bytes == 4 || !sorted_ukeys_dev);
-  TRS_REQUIRE(!args->item_dup_flags_dev || item_inl || flgm,
+  TRS_REQUIRE(!iflags || flags_form || (sorted && uflags && !adaptive && !meta),
               "trs_train_steps_sgd: item-duplicate flags need the presorted plain-SGD step without metadata");
+  const bool meta_sorted = meta && meta->sorted_keys[0] != nullptr;
   if (meta) {
-    TRS_REQUIRE(sorted_keys_dev && user_dup_flags_dev && key_bytes == 4 && ukey_bytes == 4,
-                "trs_train_steps_sgd: metadata scorers run on the presorted step");
-    const bool meta_sorted = meta->sorted_keys[0] != nullptr;
+    TRS_REQUIRE(sorted && uflags && args->ukey_bytes == 4, "trs_train_steps_sgd: metadata scorers run on the presorted step");
     if (adaptive) {
       const int D = tables->D;
       TRS_REQUIRE(meta_sorted && meta->pos_meta_ids && meta->neg_meta_ids && tables->M <= 3 &&
@@ -1743,15 +1765,15 @@ extern "C" int trs_train_steps_sgd(const trs_train_args* args, void* stream) {
     TRS_REQUIRE(meta_sorted || (meta->grad_rows && meta->grad_lin && meta->meta_ids),
                 "trs_train_steps_sgd: metadata gradient staging is NULL");
     for (int m = 0; m < tables->M && meta_sorted; ++m)
-      TRS_REQUIRE(meta->sorted_keys[m] && meta->sorted_vals[m] && (net == TRS_NET_FM || meta->lin_scratch),
+      TRS_REQUIRE(meta->sorted_keys[m] && meta->sorted_vals[m] && (args->net == TRS_NET_FM || meta->lin_scratch),
                   "trs_train_steps_sgd: sorted references of metadata column %d are NULL", m);
     for (int m = 0; m < tables->M; ++m)
-      TRS_REQUIRE(tables->meta[m] && (net != TRS_NET_FM || tables->meta_lin[m]),
+      TRS_REQUIRE(tables->meta[m] && (args->net != TRS_NET_FM || tables->meta_lin[m]),
                   "trs_train_steps_sgd: metadata table %d is NULL", m);
   }
   if (adaptive) {
     TRS_REQUIRE(opt->kind == TRS_OPT_SPARSE_ADAM || opt->kind == TRS_OPT_ADAGRAD, "trs_train_steps_sgd: bad opt->kind");
-    TRS_REQUIRE(inl && key_bytes == 4 && ukey_bytes == 4,
+    TRS_REQUIRE(sorted && uflags && args->ukey_bytes == 4,
                 "trs_train_steps_sgd: the adaptive rules need the presorted mode with user-duplicate flags");
     TRS_REQUIRE(opt->user_s1 && opt->item_s1 && opt->user_lin_s1 && opt->item_lin_s1 && opt->gacc && opt->gacc_lin &&
                     opt->cut_rows && opt->cut_count && opt->cut_capacity > 0 && opt->step0 >= 0,
@@ -1761,201 +1783,270 @@ extern "C" int trs_train_steps_sgd(const trs_train_args* args, void* stream) {
                 "trs_train_steps_sgd: SparseAdam needs exp_avg_sq tables");
   }
   if (from_stream) {
-    TRS_REQUIRE(N > 0 && first_pos >= 0 && first_pos + (int64_t)n_steps * batch <= N,
-                "trs_train_steps_sgd: steps [%lld, %lld) outside the stream of %lld rows", (long long)first_pos,
-                (long long)(first_pos + (int64_t)n_steps * batch), (long long)N);
-    TRS_REQUIRE(neg_static_dev || tables->n_items >= 2, "trs_train_steps_sgd: dynamic sampling needs n_items >= 2");
+    TRS_REQUIRE(args->N > 0 && args->first_pos >= 0 && args->first_pos + (int64_t)n_steps * batch <= args->N,
+                "trs_train_steps_sgd: steps [%lld, %lld) outside the stream of %lld rows", (long long)args->first_pos,
+                (long long)(args->first_pos + (int64_t)n_steps * batch), (long long)args->N);
+    TRS_REQUIRE(args->neg_static_dev || tables->n_items >= 2, "trs_train_steps_sgd: dynamic sampling needs n_items >= 2");
   }  // without a stream the id buffers hold n_steps consecutive batches (one epoch slice prepared by the host)
+  TRS_REQUIRE(args->loss == TRS_LOSS_HINGE || args->loss == TRS_LOSS_BPR, "trs_train_steps_sgd: bad loss kind");
+  p = StepPlan{};
+  p.form = sorted ? (uflags ? STEP_SORTED : STEP_SORTED_MARKS) : (flags_form ? STEP_FLAGS : STEP_MARKS);
+  p.src = !from_stream ? 0 : (args->neg_static_dev ? 2 : 1);
+  p.item_bits = trs_item_bits_for(tables->n_items);
+  p.owners = args->scratch_dev != nullptr;
+  if (p.form == STEP_SORTED) {
+    p.inl = iflags ? 2 : 1;  // (item flags: plain SGD without metadata only, checked above)
+    p.adaptive = adaptive;
+    p.user_pairs = user_pairs;
+    p.meta = meta != nullptr;
+    p.meta_ids = meta && meta->pos_meta_ids && meta->neg_meta_ids;
+    p.meta_sorted = meta_sorted;
+  } else if (p.form == STEP_FLAGS) {
+    p.sync = args->sync_count_host && args->sync_dev;
+    p.inl = p.sync ? 3 : 2;
+    p.nflag = args->n_flagged_dev != nullptr;
+  }
+  return TRS_OK;
+}
+
+// K1 = fwd_stage_kernel in the form the plan names
+static int launch_k1(int net, const FastArgs& a, const StepPlan& p, hipStream_t s, uint32_t* deferred) {
+  return net == TRS_NET_FM ? launch_fwd_stage<TRS_NET_FM>(a, p, s, deferred)
+                           : launch_fwd_stage<TRS_NET_LINEAR>(a, p, s, deferred);
+}
+
+// K1 of a metadata scorer: meta_stage_kernel, or the generic scorer in its staging mode (score_kernels.h MODE 2) for the
+// shapes meta_stage_kernel does not take.  first: the step's first triple in the call's arrays.
+static int launch_meta_k1(const trs_train_args* args, const StepPlan& p, const FastArgs& a, int64_t first, hipStream_t s) {
+  const trs_meta_stage* meta = args->meta;
+  const int net = args->net;
+  ScoreArgs sa = {};
+  sa.T = a.T;
+  sa.Bt.user = a.user; sa.Bt.pos = a.pos; sa.Bt.neg = a.neg;
+  sa.Bt.B = a.B; sa.Bt.idx_bytes = 4; sa.Bt.err_flag_dev = a.err;
+  if (p.meta_ids) {
+    sa.Bt.pos_meta = (void*)(meta->pos_meta_ids + first * a.T.M);
+    sa.Bt.neg_meta = (void*)(meta->neg_meta_ids + first * a.T.M);
+  }
+  sa.inv_B = a.inv_B;
+  sa.loss = a.loss;
+  sa.loss_sum = a.loss_sum;
+  sa.grad_rows = p.meta_sorted ? nullptr : meta->grad_rows;
+  sa.grad_lin = p.meta_sorted ? nullptr : meta->grad_lin;
+  sa.iota_user = -1;
+  sa.item_meta_tab = meta->item_meta_tab;
+  sa.gz = a.gz; sa.du = a.du; sa.xstage = meta->xstage;
+  sa.udup_pos = a.udup_pos;
+  sa.lr = a.lr;
+  sa.meta_ids_out = meta->meta_ids;
+  if (p.adaptive) sa.o = a.o;
+  int rc = net == TRS_NET_FM ? launch_meta_stage<TRS_NET_FM>(sa, s) : launch_meta_stage<TRS_NET_LINEAR>(sa, s);
+  if (rc > 0 && p.adaptive) {
+    trs_set_error("trs_train_steps_sgd: no adaptive metadata kernel for this shape");
+    return TRS_E_ARG;
+  }
+  if (rc > 0)  // more than 3 columns / odd D / no id arrays: the generic scorer's staging mode
+    rc = net == TRS_NET_FM ? launch_score<TRS_NET_FM, 2>(sa, s) : launch_score<TRS_NET_LINEAR, 2>(sa, s);
+  return rc;
+}
+
+// ---- one function per form: what a step launches.  ev: the step's four event handles (K1 | item update | user update
+// boundaries) or NULL; the forms whose updates are one launch record the last two back to back.
+static int step_marks(const trs_train_args* args, const StepPlan& p, const FastArgs& a, hipEvent_t* ev, hipStream_t s) {
+  uint32_t deferred;
+  if (ev) (void)hipEventRecord(ev[0], s);
+  TRS_TRY(launch_k1(args->net, a, p, s, &deferred));
+  if (ev) (void)hipEventRecord(ev[1], s);
+  TRS_TRY(launch_updates(a, p.owners, s, ev ? ev[2] : nullptr));
+  if (ev) (void)hipEventRecord(ev[3], s);
+  return TRS_OK;
+}
+
+// this step's parts of the sorted arrays; first = its first triple in the call's arrays, q0 = in the slice
+struct SortedSlices {
+  const char *keys, *vals, *ukeys, *uvals;
+  int64_t first, q0;
+};
+
+static int step_sorted_marks(const trs_train_args* args, const StepPlan& p, const FastArgs& a, const SortedSlices& sl,
+                             hipEvent_t* ev, hipStream_t s) {
+  uint32_t deferred;
+  if (ev) (void)hipEventRecord(ev[0], s);
+  TRS_TRY(launch_k1(args->net, a, p, s, &deferred));
+  if (ev) (void)hipEventRecord(ev[1], s);
+  TRS_TRY(trs_launch_sorted_item_update(args->tables, sl.keys, sl.vals, a.B, p.item_bits, a.gz, a.lr, a.uown, a.udup,
+                                        a.stamp, a.user, s));
+  if (ev) (void)hipEventRecord(ev[2], s);
+  TRS_TRY(launch_plain<1>(a, s));
+  if (ev) (void)hipEventRecord(ev[3], s);
+  return TRS_OK;
+}
+
+static int step_sorted(const trs_train_args* args, const StepPlan& p, const FastArgs& a, const SortedSlices& sl,
+                       hipEvent_t* ev, hipStream_t s) {
+  const trs_tables* tables = args->tables;
+  const trs_meta_stage* meta = args->meta;
+  const trs_opt* opt = args->opt;
+  const int64_t batch = a.B;
+  uint32_t deferred;
+  if (ev) (void)hipEventRecord(ev[0], s);
+  TRS_TRY(p.meta ? launch_meta_k1(args, p, a, sl.first, s) : launch_k1(args->net, a, p, s, &deferred));
+  if (ev) (void)hipEventRecord(ev[1], s);
+  // item + duplicated-user updates in one launch
+  const bool fm_meta = p.meta && args->net == TRS_NET_FM;
+  TRS_TRY(trs_launch_sorted_updates_fused(tables, sl.keys, sl.vals, batch, p.item_bits, a.gz, a.lr,
+                                          p.meta ? meta->xstage : a.ustage, sl.ukeys, sl.uvals, sl.q0, a.du,
+                                          p.adaptive ? &a.o : nullptr, (int)(a.stamp & 1u), fm_meta ? batch : 0,
+                                          fm_meta ? 1 : 0, p.inl == 2 ? 1 : 0, a.udup_pos, a.user, s));
+  if (p.meta_sorted) {  // one sorted-run launch per metadata column
+    for (int m = 0; m < tables->M; ++m) {
+      const char* mk = (const char*)meta->sorted_keys[m] + sl.first * 2 * 4;
+      const char* mv = (const char*)meta->sorted_vals[m] + sl.first * 2 * 4;
+      OptArgs mo = a.o;  // this column's state, accumulators and cut-run list in the item slots
+      if (p.adaptive) {
+        mo.item_s1 = opt->meta_s1[m]; mo.item_s2 = opt->meta_s2[m];
+        mo.item_lin_s1 = opt->meta_lin_s1[m]; mo.item_lin_s2 = opt->meta_lin_s2[m];
+        mo.gacc = opt->meta_gacc[m]; mo.gacc_lin = opt->meta_gacc_lin[m];
+        mo.cut_rows = opt->meta_cut_rows[m]; mo.cut_count = opt->meta_cut_count[m];
+      }
+      TRS_TRY(trs_launch_sorted_meta_update(tables, m, args->net == TRS_NET_FM ? tables->meta_lin[m] : meta->lin_scratch,
+                                            mk, mv, batch, a.gz, a.lr, meta->xstage, fm_meta ? batch : 0, fm_meta ? 1 : 0,
+                                            p.adaptive ? &mo : nullptr, (int)(a.stamp & 1u), s));
+    }
+  } else if (p.meta) {  // the metadata fields staged by K1: atomic scatter into their (small) tables
+    trs_batch mb = {};
+    mb.user = a.user; mb.pos = a.pos; mb.neg = a.neg;
+    mb.pos_meta = meta->meta_ids;
+    mb.neg_meta = meta->meta_ids + batch * tables->M;
+    mb.B = batch; mb.idx_bytes = 4; mb.err_flag_dev = a.err;
+    TRS_TRY(trs_launch_sgd_fields(args->net, tables, &mb, meta->grad_rows, meta->grad_lin, a.lr, 3, s));
+  }
+  if (ev) {
+    (void)hipEventRecord(ev[2], s);
+    (void)hipEventRecord(ev[3], s);
+  }
+  return TRS_OK;
+}
+
+static int step_flags(const trs_train_args* args, const StepPlan& p, const FastArgs& a, hipEvent_t* ev, hipStream_t s) {
+  uint32_t deferred;
+  if (ev) (void)hipEventRecord(ev[0], s);
+  TRS_TRY(launch_k1(args->net, a, p, s, &deferred));
+  if (ev) (void)hipEventRecord(ev[1], s);
+  // the flagged references: float atomics into the tables (every read of the step is behind us)
+  if (deferred) *args->sync_count_host += deferred;  // K1's own workgroups did it after their grid-wide wait
+  else TRS_TRY(launch_flagged_update(a, s));
+  if (ev) {
+    (void)hipEventRecord(ev[2], s);
+    (void)hipEventRecord(ev[3], s);
+  }
+  return TRS_OK;
+}
+
+extern "C" int trs_train_steps_sgd(const trs_train_args* args, void* stream) {
+  StepPlan p;
+  TRS_TRY(resolve_step_plan(args, p));
   hipStream_t s = (hipStream_t)stream;
+  const trs_tables* tables = args->tables;
+  const trs_opt* opt = args->opt;
+  const int64_t batch = args->batch;
+  // ---- what every step of the call shares
   FastArgs a = {};
   a.T = *tables;
-  a.user = user_buf_dev;
-  a.pos = pos_buf_dev;
-  a.neg = neg_buf_dev;
+  a.user = args->user_buf_dev;
+  a.pos = args->pos_buf_dev;
+  a.neg = args->neg_buf_dev;
   a.B = batch;
-  a.err = err_flag_dev;
-  a.from_stream = from_stream ? 1 : 0;
-  a.sui = (const int2*)stream_ui_dev;
-  a.neg_static = neg_static_dev;
-  a.N = N;
-  a.shuffle_key = shuffle_key;
-  a.hb = from_stream ? trs_feistel_half_bits(N) : 0;
-  a.sample_seed = sample_seed;
-  a.gz = gz_buf_dev;
-  a.du = du_buf_dev;
+  a.err = args->err_flag_dev;
+  a.from_stream = p.src != 0;
+  a.sui = (const int2*)args->stream_ui_dev;
+  a.neg_static = args->neg_static_dev;
+  a.N = args->N;
+  a.shuffle_key = args->shuffle_key;
+  a.hb = p.src != 0 ? trs_feistel_half_bits(args->N) : 0;
+  a.sample_seed = args->sample_seed;
+  a.gz = args->gz_buf_dev;
+  a.du = args->du_buf_dev;
   a.inv_B = 1.0f / (float)batch;
-  a.lr = lr;
+  a.lr = args->lr;
   a.loss = args->loss;
-  TRS_REQUIRE(args->loss == TRS_LOSS_HINGE || args->loss == TRS_LOSS_BPR, "trs_train_steps_sgd: bad loss kind");
-  if (scratch_dev) {
-    a.uown = (uint64_t*)scratch_dev;
+  if (p.owners) {
+    a.uown = (uint64_t*)args->scratch_dev;
     a.iown = a.uown + tables->n_users;
     a.udup = (uint32_t*)(a.iown + tables->n_items);
     a.idup = a.udup + tables->n_users;
-    if (sorted) a.iown = nullptr;  // K1 marks users only
+    if (p.form == STEP_SORTED_MARKS || p.form == STEP_SORTED) a.iown = nullptr;  // K1 marks users only
   }
-  const int item_bits = trs_item_bits_for(tables->n_items);
+  if (p.form == STEP_SORTED || p.form == STEP_FLAGS) a.ustage = args->ustage_buf_dev;
+  if (p.sync) a.sync = args->sync_dev;
   // the rule's hyper-parameters as the doubles torch.optim holds (trs_common.h)
-  const double lr_w = adaptive ? trs_as_written(opt->lr) : 0.0, decay_w = adaptive ? trs_as_written(opt->lr_decay) : 0.0;
-  const double b1_w = adaptive ? trs_as_written(opt->beta1) : 0.0, b2_w = adaptive ? trs_as_written(opt->beta2) : 0.0;
-  for (int32_t st = 0; st < n_steps; ++st) {
-    a.t0 = first_pos + (int64_t)st * batch;
+  double lr_w = 0.0, decay_w = 0.0, b1_w = 0.0, b2_w = 0.0;
+  if (p.adaptive) {
+    lr_w = trs_as_written(opt->lr); decay_w = trs_as_written(opt->lr_decay);
+    b1_w = trs_as_written(opt->beta1); b2_w = trs_as_written(opt->beta2);
+    OptArgs& o = a.o;
+    o.kind = opt->kind == TRS_OPT_SPARSE_ADAM ? OPT_ADAM : OPT_ADAGRAD;
+    o.omb1 = (float)(1.0 - b1_w); o.omb2 = (float)(1.0 - b2_w); o.eps = opt->eps;
+    o.user_s1 = opt->user_s1; o.user_s2 = opt->user_s2; o.item_s1 = opt->item_s1; o.item_s2 = opt->item_s2;
+    o.user_lin_s1 = opt->user_lin_s1; o.user_lin_s2 = opt->user_lin_s2;
+    o.item_lin_s1 = opt->item_lin_s1; o.item_lin_s2 = opt->item_lin_s2;
+    o.gacc = opt->gacc; o.gacc_lin = opt->gacc_lin;
+    o.cut_rows = opt->cut_rows; o.cut_count = opt->cut_count; o.cut_capacity = opt->cut_capacity;
+  }
+  // ---- the step loop: only what differs from step to step is set here; what is launched is the form's business
+  for (int32_t st = 0; st < args->n_steps; ++st) {
+    const int64_t first = (int64_t)st * batch;  // the step's first triple in the call's arrays
+    a.t0 = args->first_pos + first;
     a.sample_offset = (uint64_t)a.t0;
-    if (inl) {
-      a.udup_pos = user_dup_flags_dev + (int64_t)st * batch;
-      a.ustage = ustage_buf_dev;
-      if (item_inl) a.idup_pos = args->item_dup_flags_dev + (int64_t)st * 2 * batch;
+    if (p.src == 0) {  // step st reads its ids at [st*batch, (st+1)*batch) of the given arrays
+      a.user = args->user_buf_dev + first;
+      a.pos = args->pos_buf_dev + first;
+      a.neg = args->neg_buf_dev + first;
     }
-    if (flgm) {
-      a.udup_pos = user_dup_flags_dev + (int64_t)st * batch;
-      a.idup_pos = args->item_dup_flags_dev + (int64_t)st * 2 * batch;
-      a.ustage = ustage_buf_dev;
-      a.sync = args->sync_count_host ? args->sync_dev : nullptr;
+    a.loss_sum = args->loss_sums_dev + st;
+    a.stamp = args->first_stamp + (uint32_t)st;
+    if (p.form == STEP_SORTED || p.form == STEP_FLAGS) a.udup_pos = args->user_dup_flags_dev + first;
+    if (p.inl >= 2) a.idup_pos = args->item_dup_flags_dev + 2 * first;
+    if (p.adaptive) {  // this step's effective learning rate, in double like the Python floats of torch.optim
+      const double t = (double)(opt->step0 + st + 1);
+      a.o.lr_eff = a.o.kind == OPT_ADAM ? (float)(lr_w * sqrt(1.0 - pow(b2_w, t)) / (1.0 - pow(b1_w, t)))
+                                        : (float)(lr_w / (1.0 + (t - 1.0) * decay_w));
+    }
+    if (p.sync) {
       // Rebase: launches that count in early never write the flag lines, so after 2^31 arrivals of them a launch that
       // polls its line would read a stale value as "ahead" and not wait.  Long before that, zero counter and lines
       // behind every earlier launch of the stream: all values stay within TRS_SYNC_REBASE + one grid of each other.
-      if (a.sync && *args->sync_count_host >= TRS_SYNC_REBASE) {
+      if (*args->sync_count_host >= TRS_SYNC_REBASE) {
         if (hipMemsetAsync(args->sync_dev, 0, TRS_SYNC_WORDS * sizeof(uint32_t), s) != hipSuccess) {
           trs_set_error("trs_train_steps_sgd: clearing the arrival counter failed");
           return TRS_E_LAUNCH;
         }
         *args->sync_count_host = 0;
       }
-      a.sync_base = a.sync ? *args->sync_count_host : 0u;
-      a.nflag = args->n_flagged_dev ? args->n_flagged_dev + st : nullptr;
+      a.sync_base = *args->sync_count_host;
     }
-    if (adaptive) {  // this step's effective learning rate, in double like the Python floats of torch.optim
-      OptArgs& o = a.o;
-      const double t = (double)(opt->step0 + st + 1);
-      o.kind = opt->kind == TRS_OPT_SPARSE_ADAM ? OPT_ADAM : OPT_ADAGRAD;
-      o.omb1 = (float)(1.0 - b1_w); o.omb2 = (float)(1.0 - b2_w); o.eps = opt->eps;
-      o.lr_eff = o.kind == OPT_ADAM
-                     ? (float)(lr_w * sqrt(1.0 - pow(b2_w, t)) / (1.0 - pow(b1_w, t)))
-                     : (float)(lr_w / (1.0 + (t - 1.0) * decay_w));
-      o.user_s1 = opt->user_s1; o.user_s2 = opt->user_s2; o.item_s1 = opt->item_s1; o.item_s2 = opt->item_s2;
-      o.user_lin_s1 = opt->user_lin_s1; o.user_lin_s2 = opt->user_lin_s2;
-      o.item_lin_s1 = opt->item_lin_s1; o.item_lin_s2 = opt->item_lin_s2;
-      o.gacc = opt->gacc; o.gacc_lin = opt->gacc_lin;
-      o.cut_rows = opt->cut_rows; o.cut_count = opt->cut_count; o.cut_capacity = opt->cut_capacity;
+    if (p.nflag) a.nflag = args->n_flagged_dev + st;
+    SortedSlices sl = {};
+    if (p.form == STEP_SORTED || p.form == STEP_SORTED_MARKS) {
+      sl.keys = (const char*)args->sorted_keys_dev + first * 2 * 4;
+      sl.vals = (const char*)args->sorted_vals_dev + first * 2 * 4;
+      if (p.user_pairs) {
+        sl.ukeys = (const char*)args->sorted_ukeys_dev + first * 4;
+        sl.uvals = (const char*)args->sorted_uvals_dev + first * 4;
+      }
+      sl.first = first;
+      sl.q0 = args->slice_pos0 + first;
     }
-    if (!from_stream) {  // step st reads its ids at [st*batch, (st+1)*batch) of the given arrays
-      a.user = user_buf_dev + (int64_t)st * batch;
-      a.pos = pos_buf_dev + (int64_t)st * batch;
-      a.neg = neg_buf_dev + (int64_t)st * batch;
-    }
-    a.loss_sum = loss_sums_dev + st;
-    a.stamp = first_stamp + (uint32_t)st;
-    hipEvent_t* ev = events ? (hipEvent_t*)events + 4 * (int64_t)st : nullptr;  // K1 | K2a+K2b | K3 boundaries
+    hipEvent_t* ev = args->events ? (hipEvent_t*)args->events + 4 * (int64_t)st : nullptr;
     if (ev && !ev[0]) ev = nullptr;  // a step whose four handles are NULL is not timed (sampled timing)
-    if (ev) (void)hipEventRecord(ev[0], s);
-    int rc;
-    uint32_t deferred = 0;
-    if (meta) {  // K1 = the generic scorer in its staging mode (score_kernels.h MODE 2)
-      ScoreArgs sa = {};
-      sa.T = *tables;
-      sa.Bt.user = a.user; sa.Bt.pos = a.pos; sa.Bt.neg = a.neg;
-      sa.Bt.B = batch; sa.Bt.idx_bytes = 4; sa.Bt.err_flag_dev = err_flag_dev;
-      if (meta->pos_meta_ids && meta->neg_meta_ids) {
-        sa.Bt.pos_meta = (void*)(meta->pos_meta_ids + (int64_t)st * batch * tables->M);
-        sa.Bt.neg_meta = (void*)(meta->neg_meta_ids + (int64_t)st * batch * tables->M);
-      }
-      sa.inv_B = a.inv_B;
-      sa.loss = a.loss;
-      sa.loss_sum = a.loss_sum;
-      const bool meta_sorted = meta->sorted_keys[0] != nullptr;
-      sa.grad_rows = meta_sorted ? nullptr : meta->grad_rows;
-      sa.grad_lin = meta_sorted ? nullptr : meta->grad_lin;
-      sa.iota_user = -1;
-      sa.item_meta_tab = meta->item_meta_tab;
-      sa.gz = a.gz; sa.du = a.du; sa.xstage = meta->xstage;
-      sa.udup_pos = a.udup_pos;
-      sa.lr = a.lr;
-      sa.meta_ids_out = meta->meta_ids;
-      if (adaptive) sa.o = a.o;
-      rc = net == TRS_NET_FM ? launch_meta_stage<TRS_NET_FM>(sa, s) : launch_meta_stage<TRS_NET_LINEAR>(sa, s);
-      if (rc > 0 && adaptive) {
-        trs_set_error("trs_train_steps_sgd: no adaptive metadata kernel for this shape");
-        return TRS_E_ARG;
-      }
-      if (rc > 0)  // more than 3 columns / odd D / no id arrays: the generic scorer's staging mode
-        rc = net == TRS_NET_FM ? launch_score<TRS_NET_FM, 2>(sa, s) : launch_score<TRS_NET_LINEAR, 2>(sa, s);
-    } else {
-      rc = net == TRS_NET_FM ? launch_fwd_stage<TRS_NET_FM>(a, s, &deferred)
-                             : launch_fwd_stage<TRS_NET_LINEAR>(a, s, &deferred);
+    int rc = TRS_OK;
+    switch (p.form) {
+      case STEP_MARKS: rc = step_marks(args, p, a, ev, s); break;
+      case STEP_SORTED_MARKS: rc = step_sorted_marks(args, p, a, sl, ev, s); break;
+      case STEP_SORTED: rc = step_sorted(args, p, a, sl, ev, s); break;
+      case STEP_FLAGS: rc = step_flags(args, p, a, ev, s); break;
     }
     if (rc) return rc;
-    if (ev) (void)hipEventRecord(ev[1], s);
-    if (flgm) {  // the flagged references: float atomics into the tables (every read of the step is behind us)
-      if (deferred) *args->sync_count_host += deferred;  // K1's own workgroups did it after their grid-wide wait
-      else rc = launch_flagged_update(a, s);
-      if (rc) return rc;
-      if (ev) {
-        (void)hipEventRecord(ev[2], s);
-        (void)hipEventRecord(ev[3], s);
-      }
-      continue;
-    }
-    if (sorted) {  // K2: per-run owner update from the presorted references, then K3
-      const char* ks = (const char*)sorted_keys_dev + (int64_t)st * 2 * batch * key_bytes;
-      const char* vs = (const char*)sorted_vals_dev + (int64_t)st * 2 * batch * 4;
-      if (inl && key_bytes == 4 && (ukey_bytes == 4 || !sorted_ukeys_dev)) {  // item + duplicated-user updates in one launch
-        const char* uk = sorted_ukeys_dev ? (const char*)sorted_ukeys_dev + (int64_t)st * batch * 4 : nullptr;
-        const char* uv = sorted_ukeys_dev ? (const char*)sorted_uvals_dev + (int64_t)st * batch * 4 : nullptr;
-        const bool fm_meta = meta && net == TRS_NET_FM;
-        rc = trs_launch_sorted_updates_fused(tables, ks, vs, batch, item_bits, a.gz, a.lr,
-                                             meta ? meta->xstage : a.ustage, uk, uv,
-                                             slice_pos0 + (int64_t)st * batch, a.du, adaptive ? &a.o : nullptr,
-                                             (int)(a.stamp & 1u), fm_meta ? batch : 0, fm_meta ? 1 : 0,
-                                             item_inl ? 1 : 0, a.udup_pos, a.user, s);
-        if (rc) return rc;
-        if (meta && meta->sorted_keys[0]) {  // one sorted-run launch per metadata column
-          for (int m = 0; m < tables->M; ++m) {
-            const char* mk = (const char*)meta->sorted_keys[m] + (int64_t)st * 2 * batch * 4;
-            const char* mv = (const char*)meta->sorted_vals[m] + (int64_t)st * 2 * batch * 4;
-            OptArgs mo = a.o;  // this column's state, accumulators and cut-run list in the item slots
-            if (adaptive) {
-              mo.item_s1 = opt->meta_s1[m]; mo.item_s2 = opt->meta_s2[m];
-              mo.item_lin_s1 = opt->meta_lin_s1[m]; mo.item_lin_s2 = opt->meta_lin_s2[m];
-              mo.gacc = opt->meta_gacc[m]; mo.gacc_lin = opt->meta_gacc_lin[m];
-              mo.cut_rows = opt->meta_cut_rows[m]; mo.cut_count = opt->meta_cut_count[m];
-            }
-            rc = trs_launch_sorted_meta_update(tables, m, net == TRS_NET_FM ? tables->meta_lin[m] : meta->lin_scratch, mk,
-                                               mv, batch, a.gz, a.lr, meta->xstage, fm_meta ? batch : 0, fm_meta ? 1 : 0,
-                                               adaptive ? &mo : nullptr, (int)(a.stamp & 1u), s);
-            if (rc) return rc;
-          }
-        } else if (meta) {  // the metadata fields staged by K1: atomic scatter into their (small) tables
-          trs_batch mb = {};
-          mb.user = a.user; mb.pos = a.pos; mb.neg = a.neg;
-          mb.pos_meta = meta->meta_ids;
-          mb.neg_meta = meta->meta_ids + batch * tables->M;
-          mb.B = batch; mb.idx_bytes = 4; mb.err_flag_dev = err_flag_dev;
-          rc = trs_launch_sgd_fields(net, tables, &mb, meta->grad_rows, meta->grad_lin, a.lr, 3, s);
-          if (rc) return rc;
-        }
-        if (ev) {
-          (void)hipEventRecord(ev[2], s);
-          (void)hipEventRecord(ev[3], s);
-        }
-        continue;
-      }
-      rc = trs_launch_sorted_item_update(tables, ks, vs, key_bytes, batch, item_bits, a.gz, a.lr,
-                                         inl ? nullptr : a.uown, a.udup, a.stamp, inl ? a.ustage : nullptr, a.user, s);
-      if (rc) return rc;
-      if (ev) (void)hipEventRecord(ev[2], s);
-      if (inl) {
-        const char* uk = (const char*)sorted_ukeys_dev + (int64_t)st * batch * ukey_bytes;
-        const char* uv = (const char*)sorted_uvals_dev + (int64_t)st * batch * 4;
-        rc = trs_launch_sorted_user_dup_update(tables, uk, uv, ukey_bytes, batch, slice_pos0 + (int64_t)st * batch,
-                                               a.du, a.gz, a.lr, s);
-      } else {
-        rc = launch_plain<1>(a, s);
-      }
-    } else {
-      rc = launch_updates(a, s, ev ? ev[2] : nullptr);
-    }
-    if (rc) return rc;
-    if (ev) (void)hipEventRecord(ev[3], s);
   }
   return TRS_OK;
 }

@@ -46,16 +46,16 @@ struct EpochArgs {
   int32_t* user;  // (n_pos) in/out
   int32_t* pos;
   int32_t* neg;
-  void* keys;  // (2*n_pos) uint32 or uint64
+  uint32_t* keys;  // (2*n_pos) item rows, or NULL
   RefPayload* vals;
   int32_t* err;
   TrsSampler S;  // sampler options (max_tries == 0: the reference's sampler); k_neg: the epoch has N * k_neg positions
 };
 
-template <typename KeyT, int SRC>
+template <int SRC>
 __global__ __launch_bounds__(TRS_BLOCK) void epoch_refs_kernel(const EpochArgs a) {
   const int64_t stride = (int64_t)gridDim.x * TRS_BLOCK;
-  KeyT* keys = reinterpret_cast<KeyT*>(a.keys);
+  uint32_t* keys = a.keys;
   for (int64_t q = (int64_t)blockIdx.x * TRS_BLOCK + threadIdx.x; q < a.n_pos; q += stride) {
     int64_t u, i, j;
     if (SRC != 0) {
@@ -84,8 +84,8 @@ __global__ __launch_bounds__(TRS_BLOCK) void epoch_refs_kernel(const EpochArgs a
       a.neg[q] = (int32_t)j;
     }
     if (keys) {  // (NULL: ids only — the sparse regime's flags need no sort keys)
-      keys[2 * q] = (KeyT)i;
-      keys[2 * q + 1] = (KeyT)j;
+      keys[2 * q] = (uint32_t)i;
+      keys[2 * q + 1] = (uint32_t)j;
     }
   }
 }
@@ -499,17 +499,17 @@ __global__ __launch_bounds__(GRP_THREADS) void batch_group_items_kernel(const in
 // ---------------------------------------------------------------------------------------------- per-step update
 struct SortedArgs {
   trs_tables T;
-  const void* keys;         // this step's 2B sorted keys
+  const uint32_t* keys;     // this step's 2B sorted keys (item rows)
   const RefPayload* vals;   // this step's 2B sorted payloads
   const int32_t* user_ids;  // this step's B user ids (position t -> user): the unstaged form reads the user table
   int64_t B;
   int item_bits;
   const float* gz;          // (2,B)
   float lr;
-  uint64_t* uown;       // NULL: the user-duplicate stamps are not needed (flags were precomputed)
+  uint64_t* uown;       // unstaged form: K1's user marks (the staged forms got precomputed flags and leave it NULL)
   uint32_t* udup;
   uint32_t stamp;
-  const float* ustage;  // (B,D) pre-update user rows staged by K1 (indexed by t), or NULL: read the user table
+  const float* ustage;  // staged forms: (B,D) pre-update user rows staged by K1 (indexed by t)
   OptArgs o;            // staged form: update rule (OPT_SGD: lr above); adaptive rules coalesce whole runs first
   int parity;           // step parity: which cut-run counter this step appends to
   // metadata scorers (staged form, SGD): the staged rows are X(t, which) = ustage[which * xpass + t]; FM with metadata
@@ -527,17 +527,17 @@ struct SortedArgs {
 
 constexpr int RUN_CHUNK = 64;  // runs are cut at multiples of this many references
 
-// STAGED: user rows come from K1's staging buffer (row t of the batch; K1 has already updated the table rows of users
-// referenced once) and no duplicate stamping is needed.
-template <typename KeyT, int VEC, int G, int K, bool FULL, bool STAGED>
+// The unstaged form (the sorted-marks step: K1 marked the users only): user rows are read from the still-unmodified user
+// table, and the positive reference of every triple stamps its user row for K3 if it has other references in the step.
+template <int VEC, int G, int K, bool FULL>
 __global__ __launch_bounds__(TRS_BLOCK) void sorted_item_update_kernel(const SortedArgs a) {
   constexpr int N = K * VEC;
   constexpr int TPW = TRS_WAVE / G;
   const trs_tables& T = a.T;
   const int D = T.D;
   const int64_t n = 2 * a.B;
-  const KeyT* keys = reinterpret_cast<const KeyT*>(a.keys);
-  const KeyT row_mask = (KeyT)(((uint64_t)1 << a.item_bits) - 1);
+  const uint32_t* keys = a.keys;
+  const uint32_t row_mask = (uint32_t)(((uint64_t)1 << a.item_bits) - 1);
   const int lane = threadIdx.x & 63;
   const int lig = lane % G;
   const int64_t wave = ((int64_t)blockIdx.x * TRS_BLOCK + threadIdx.x) >> 6;
@@ -550,23 +550,21 @@ __global__ __launch_bounds__(TRS_BLOCK) void sorted_item_update_kernel(const Sor
     const int64_t ic = valid ? i : n - 1;
     // everything the first element of a run needs is requested up front, unconditionally (a conditional block that
     // contains a load would end in s_waitcnt vmcnt(0)); groups that turn out not to lead a run read row 0 instead
-    const KeyT key = keys[ic];
-    const KeyT prev = keys[ic > 0 ? ic - 1 : 0];
+    const uint32_t key = keys[ic];
+    const uint32_t prev = keys[ic > 0 ? ic - 1 : 0];
     const RefPayload me = a.vals[ic];
-    const int64_t me_user = STAGED ? 0 : (int64_t)a.user_ids[me.tw >> 1];
+    const int64_t me_user = (int64_t)a.user_ids[me.tw >> 1];
     const bool head = ic == 0 || prev != key;
     const bool leader = valid && (head || (ic % RUN_CHUNK) == 0);
-    uint64_t own = 0;
-    if (!STAGED) own = a.uown[me_user];
-    const float* ubase = STAGED ? a.ustage : T.user;
+    const uint64_t own = a.uown[me_user];
     const float c0 = -a.lr * a.gz[(int64_t)(me.tw & 1u) * a.B + (me.tw >> 1)];
     const int64_t row = (int64_t)(key & row_mask);
     RowReg<VEC, K> u0, w;
-    row_load<VEC, G, K, FULL>(u0, ubase, leader ? (STAGED ? (int64_t)(me.tw >> 1) : me_user) : 0, D, lig);
+    row_load<VEC, G, K, FULL>(u0, T.user, leader ? me_user : 0, D, lig);
     row_load<VEC, G, K, FULL>(w, T.item, leader ? row : 0, D, lig);
     const float wl = T.item_lin[leader ? row : 0];
     // the positive reference of a triple also checks whether its user row has other references in this step (K3)
-    if (!STAGED && valid && (me.tw & 1u) == 0 && lig == 0 && own != (hi | (uint64_t)(me.tw >> 1)))
+    if (valid && (me.tw & 1u) == 0 && lig == 0 && own != (hi | (uint64_t)(me.tw >> 1)))
       a.udup[me_user] = a.stamp;
     if (!leader) continue;
     const int64_t chunk_end = (ic / RUN_CHUNK + 1) * RUN_CHUNK < n ? (ic / RUN_CHUNK + 1) * RUN_CHUNK : n;
@@ -579,7 +577,7 @@ __global__ __launch_bounds__(TRS_BLOCK) void sorted_item_update_kernel(const Sor
       const RefPayload pl = a.vals[j];
       const float c = -a.lr * a.gz[(int64_t)(pl.tw & 1u) * a.B + (pl.tw >> 1)];
       RowReg<VEC, K> u;
-      row_load<VEC, G, K, FULL>(u, ubase, STAGED ? (int64_t)(pl.tw >> 1) : (int64_t)a.user_ids[pl.tw >> 1], D, lig);
+      row_load<VEC, G, K, FULL>(u, T.user, (int64_t)a.user_ids[pl.tw >> 1], D, lig);
 #pragma unroll
       for (int q = 0; q < N; ++q) acc.v[q] += c * u.v[q];
       lin += c;
@@ -606,7 +604,7 @@ __global__ __launch_bounds__(TRS_BLOCK) void sorted_item_update_kernel(const Sor
   }
 }
 
-// STAGED form, wave-cooperative: a 256-thread workgroup owns one 64-reference chunk (= RUN_CHUNK, so a run never leaves
+// Staged form (user rows come from K1's staging buffer, row t of the batch), wave-cooperative: a 256-thread workgroup owns one 64-reference chunk (= RUN_CHUNK, so a run never leaves
 // the chunk).  Every wave detects the run leaders with ONE lane per reference (coalesced keys / payloads, then the
 // reference's coefficient c = -lr*gz), ranks them (ballot + popcount) and publishes rank -> lane through LDS; the
 // leaders are then dealt round-robin to the lane groups of the four waves.  A group knows its run's members from the
@@ -614,7 +612,7 @@ __global__ __launch_bounds__(TRS_BLOCK) void sorted_item_update_kernel(const Sor
 // member rows for SLOTS runs at once — no load sits under a branch and no load depends on a loop-carried compare.
 constexpr int SI_SLOTS = 3, SI_MEMB = 3;
 
-template <typename KeyT, int VEC, int G, int K, bool FULL, int OPT = OPT_SGD>
+template <int VEC, int G, int K, bool FULL, int OPT = OPT_SGD>
 __device__ __forceinline__ void sorted_item_update_staged_body(const SortedArgs& a, int block_id, int n_blocks) {
   constexpr int N = K * VEC;
   constexpr int TPW = TRS_WAVE / G;
@@ -625,8 +623,8 @@ __device__ __forceinline__ void sorted_item_update_staged_body(const SortedArgs&
   float* const tab = a.tab ? a.tab : T.item;
   float* const tab_lin = a.tab ? a.tab_lin : T.item_lin;
   const int64_t n = 2 * a.B;
-  const KeyT* keys = reinterpret_cast<const KeyT*>(a.keys);
-  const KeyT row_mask = (KeyT)(((uint64_t)1 << a.item_bits) - 1);
+  const uint32_t* keys = a.keys;
+  const uint32_t row_mask = (uint32_t)(((uint64_t)1 << a.item_bits) - 1);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int lig = lane % G, gi = lane / G;
   const int64_t nchunk = (n + RUN_CHUNK - 1) / RUN_CHUNK;
@@ -635,9 +633,9 @@ __device__ __forceinline__ void sorted_item_update_staged_body(const SortedArgs&
     const int64_t i = base + lane;
     const bool valid = i < n;
     const int64_t il = valid ? i : n - 1;
-    const KeyT k0 = keys[il];
-    const KeyT kp = keys[il > 0 ? il - 1 : 0];
-    const KeyT knext = keys[base + RUN_CHUNK < n ? base + RUN_CHUNK : n - 1];  // first key of the next chunk
+    const uint32_t k0 = keys[il];
+    const uint32_t kp = keys[il > 0 ? il - 1 : 0];
+    const uint32_t knext = keys[base + RUN_CHUNK < n ? base + RUN_CHUNK : n - 1];  // first key of the next chunk
     const RefPayload me = a.vals[il];
     const int t = (int)(me.tw >> 1);
     const int xrow = t + (int)(me.tw & 1u) * (int)a.xpass;  // row of the staged image this reference multiplies
@@ -648,7 +646,7 @@ __device__ __forceinline__ void sorted_item_update_staged_body(const SortedArgs&
     const bool head = il == 0 || kp != k0;                // first reference of the row in this step
     const bool cont = valid && lane > 0 && !head;         // continues the run of the lane before it
     // a reference alone on its row (same test as item_flags_kernel): K1 has updated that row already
-    const KeyT kn1 = keys[il + 1 < n ? il + 1 : il];
+    const uint32_t kn1 = keys[il + 1 < n ? il + 1 : il];
     const bool single = head && !(il + 1 < n && kn1 == k0);
     const bool lead = valid && !cont && !(a.skip_single != 0 && single);
     const uint64_t lmask = __ballot(lead), cmask = __ballot(cont);
@@ -657,11 +655,10 @@ __device__ __forceinline__ void sorted_item_update_staged_body(const SortedArgs&
     if (lead) lead_lane[wv][rank] = (unsigned char)lane;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    const uint32_t klo = (uint32_t)(k0 & (KeyT)0xffffffffu), khi = (uint32_t)((uint64_t)k0 >> 32);
     // rounds of TPW leaders; round r belongs to wave r % NW; SLOTS rounds per pass
     for (int r0 = wv; r0 * TPW < nlead; r0 += NW * SI_SLOTS) {
       int l[SI_SLOTS], len[SI_SLOTS], hd[SI_SLOTS];
-      KeyT keyv[SI_SLOTS];
+      uint32_t keyv[SI_SLOTS];
       bool has[SI_SLOTS];
       int64_t row[SI_SLOTS];
       RowReg<VEC, K> w[SI_SLOTS], u[SI_SLOTS][SI_MEMB];
@@ -674,10 +671,9 @@ __device__ __forceinline__ void sorted_item_update_staged_body(const SortedArgs&
         l[s] = has[s] ? (int)lead_lane[wv][want] : 0;
         const uint64_t after = l[s] < 63 ? (cmask >> (l[s] + 1)) : 0ull;
         len[s] = 1 + (int)__ffsll((unsigned long long)~after) - 1;
-        const uint64_t key = ((uint64_t)(uint32_t)__shfl((int)khi, l[s], 64) << 32) | (uint32_t)__shfl((int)klo, l[s], 64);
-        keyv[s] = (KeyT)key;
+        keyv[s] = (uint32_t)__shfl((int)k0, l[s], 64);
         hd[s] = __shfl((int)head, l[s], 64);
-        row[s] = has[s] ? (int64_t)((KeyT)key & row_mask) : 0;
+        row[s] = has[s] ? (int64_t)(keyv[s] & row_mask) : 0;
         row_load<VEC, G, K, FULL>(w[s], tab, row[s], D, lig);
         wl[s] = tab_lin[row[s]];
         ls1[s] = ls2[s] = 0.f;
@@ -805,13 +801,12 @@ __device__ __forceinline__ void sorted_item_update_staged_body(const SortedArgs&
 // ---------------------------------------------------------------------------------------------- user duplicates
 // flags[q] = 1 iff the user of position q is referenced by another triple of the same batch (static for the epoch):
 // per-batch grouping of (user, q) by user, then compare neighbours inside the batch.
-template <typename KeyT>
-__global__ __launch_bounds__(TRS_BLOCK) void user_flags_kernel(const KeyT* __restrict__ keys,
+__global__ __launch_bounds__(TRS_BLOCK) void user_flags_kernel(const uint32_t* __restrict__ keys,
                                                               const uint32_t* __restrict__ vals, int64_t n_pos,
                                                               int64_t batch, uint8_t* __restrict__ flags) {
   const int64_t stride = (int64_t)gridDim.x * TRS_BLOCK;
   for (int64_t s = (int64_t)blockIdx.x * TRS_BLOCK + threadIdx.x; s < n_pos; s += stride) {
-    const KeyT k = keys[s];
+    const uint32_t k = keys[s];
     const int64_t in_seg = s % batch;
     const bool dup = (in_seg > 0 && keys[s - 1] == k) || (in_seg + 1 < batch && keys[s + 1] == k);
     if (dup) flags[vals[s]] = 1;  // the array was zeroed: only the (few) duplicated positions take a scattered byte store
@@ -837,7 +832,7 @@ __global__ __launch_bounds__(TRS_BLOCK) void item_flags_kernel(const uint32_t* _
 // plain read-modify-write (K1 already updated every user referenced once).  No atomics: the step is reproducible.
 struct UserDupArgs {
   trs_tables T;
-  const void* ukeys;      // this step's B sorted user ids
+  const uint32_t* ukeys;  // this step's B sorted user ids
   const uint32_t* uvals;  // this step's B sorted positions (slice-relative q)
   int64_t B;
   int64_t q0;             // slice-relative position of the step's first triple
@@ -899,15 +894,15 @@ __device__ __forceinline__ void flagged_user_update_body(const UserDupArgs& a, i
   }
 }
 
-template <typename KeyT, int VEC, int G, int K, bool FULL, int OPT = OPT_SGD>
+template <int VEC, int G, int K, bool FULL, int OPT = OPT_SGD>
 __device__ __forceinline__ void sorted_user_dup_update_body(const UserDupArgs& a, int block_id, int n_blocks) {
   constexpr int N = K * VEC;
   constexpr int TPW = TRS_WAVE / G;
   const trs_tables& T = a.T;
   const int D = T.D;
   const int64_t n = a.B;
-  const KeyT* keys = reinterpret_cast<const KeyT*>(a.ukeys);
-  const KeyT user_mask = (KeyT)(((uint64_t)1 << a.user_bits) - 1);
+  const uint32_t* keys = a.ukeys;
+  const uint32_t user_mask = (uint32_t)(((uint64_t)1 << a.user_bits) - 1);
   const int lane = threadIdx.x & 63;
   const int lig = lane % G;
   const int64_t wave = ((int64_t)block_id * TRS_BLOCK + threadIdx.x) >> 6;
@@ -921,9 +916,9 @@ __device__ __forceinline__ void sorted_user_dup_update_body(const UserDupArgs& a
     const int64_t i = it * TRS_WAVE + lane;
     const bool valid = i < n;
     const int64_t il = valid ? i : n - 1;
-    const KeyT k0 = keys[il];
-    const KeyT kp = keys[il > 0 ? il - 1 : 0];
-    const KeyT kn = keys[il + 1 < n ? il + 1 : il];
+    const uint32_t k0 = keys[il];
+    const uint32_t kp = keys[il > 0 ? il - 1 : 0];
+    const uint32_t kn = keys[il + 1 < n ? il + 1 : il];
     const int uv = (int)((int64_t)a.uvals[il] - a.q0);
     const bool cont = valid && il > 0 && kp == k0;
     const bool lead = valid && !cont && (il + 1 < n && kn == k0);
@@ -945,7 +940,7 @@ __device__ __forceinline__ void sorted_user_dup_update_body(const UserDupArgs& a
         const int other = __shfl_xor(most, o, 64);
         most = other > most ? other : most;
       }
-      const int64_t key_lo = __shfl((int)(uint32_t)(k0 & (KeyT)0xffffffffu), l, 64);
+      const int64_t key_lo = __shfl((int)k0, l, 64);
       const int64_t user = (int64_t)((uint32_t)key_lo) & (int64_t)user_mask;
       RowReg<VEC, K> w, acc, s1, s2;
       row_load<VEC, G, K, FULL>(w, T.user, user, D, lig);
@@ -975,7 +970,7 @@ __device__ __forceinline__ void sorted_user_dup_update_body(const UserDupArgs& a
       }
       if (!has) continue;
       if (l + in_wave == TRS_WAVE) {  // rare: the run goes on in the next 64 entries
-        const KeyT key = keys[it * TRS_WAVE + l];
+        const uint32_t key = keys[it * TRS_WAVE + l];
         for (int64_t j = (it + 1) * TRS_WAVE; j < n && keys[j] == key; ++j) {
           const int64_t t = (int64_t)a.uvals[j] - a.q0;
           RowReg<VEC, K> g;
@@ -1050,21 +1045,16 @@ __global__ __launch_bounds__(TRS_BLOCK) void cut_rows_apply_kernel(const trs_tab
   }
 }
 
-template <typename KeyT, int VEC, int G, int K, bool FULL, int OPT = OPT_SGD>
+template <int VEC, int G, int K, bool FULL, int OPT = OPT_SGD>
 __global__ __launch_bounds__(TRS_BLOCK)
-__attribute__((amdgpu_waves_per_eu(OPT == OPT_SGD && VEC == 4 && K == 1 && FULL && sizeof(KeyT) == 4 ? K2_WAVES : 1)))
+__attribute__((amdgpu_waves_per_eu(OPT == OPT_SGD && VEC == 4 && K == 1 && FULL ? K2_WAVES : 1)))
 void sorted_item_update_staged_kernel(const SortedArgs a) {
-  sorted_item_update_staged_body<KeyT, VEC, G, K, FULL, OPT>(a, blockIdx.x, gridDim.x);
-}
-
-template <typename KeyT, int VEC, int G, int K, bool FULL>
-__global__ __launch_bounds__(TRS_BLOCK) void sorted_user_dup_update_kernel(const UserDupArgs a) {
-  sorted_user_dup_update_body<KeyT, VEC, G, K, FULL>(a, blockIdx.x, gridDim.x);
+  sorted_item_update_staged_body<VEC, G, K, FULL, OPT>(a, blockIdx.x, gridDim.x);
 }
 
 // Both updates of a presorted step in ONE launch (they touch different tables and only depend on K1): the first
 // n_user_blocks workgroups walk the duplicated-user runs, the rest the item chunks.  Saves a kernel boundary and hides
-// the short, latency-bound user pass under the item pass.  32-bit keys on both sides (the common case).
+// the short, latency-bound user pass under the item pass.
 template <int VEC, int G, int K, bool FULL, int OPT = OPT_SGD>
 __global__ __launch_bounds__(TRS_BLOCK)
 __attribute__((amdgpu_waves_per_eu(OPT == OPT_SGD && VEC == 4 && K == 1 && FULL ? K2_WAVES : 1)))
@@ -1072,9 +1062,9 @@ void sorted_updates_fused_kernel(const SortedArgs ia, const UserDupArgs ua,
                                                                         int n_user_blocks) {
   if ((int)blockIdx.x < n_user_blocks) {
     if (OPT == OPT_SGD && ua.ukeys == nullptr) flagged_user_update_body(ua, blockIdx.x, n_user_blocks);
-    else sorted_user_dup_update_body<uint32_t, VEC, G, K, FULL, OPT>(ua, blockIdx.x, n_user_blocks);
+    else sorted_user_dup_update_body<VEC, G, K, FULL, OPT>(ua, blockIdx.x, n_user_blocks);
   } else
-    sorted_item_update_staged_body<uint32_t, VEC, G, K, FULL, OPT>(ia, (int)blockIdx.x - n_user_blocks,
+    sorted_item_update_staged_body<VEC, G, K, FULL, OPT>(ia, (int)blockIdx.x - n_user_blocks,
                                                                    (int)gridDim.x - n_user_blocks);
 }
 
@@ -1142,6 +1132,7 @@ using namespace trs;
 
 // Sizes (bytes) a caller must provide for an epoch slice of n_batches whole batches:
 //   ids: 3 x n_pos int32 (user, pos, neg)   keys: 2 x (2 n_pos) keys   vals: 2 x (2 n_pos) x 8   temp: 256 bytes, unused
+// *key_bytes_out is always 4: the sorted references carry uint32 keys (item rows), the only width trs_train_steps_sgd takes.
 extern "C" int trs_epoch_presort_sizes(int64_t n_batches, int64_t batch, int64_t n_items, int64_t* key_bytes_out,
                                        int64_t* keys_total_bytes_out, int64_t* vals_total_bytes_out,
                                        int64_t* temp_bytes_out) {
@@ -1193,7 +1184,6 @@ extern "C" int trs_epoch_presort(const int32_t* stream_ui_dev, const int32_t* ne
   a.user = user_dev;
   a.pos = pos_dev;
   a.neg = neg_dev;
-  a.keys = keys_dev;
   a.vals = (RefPayload*)vals_dev;
   a.err = err_flag_dev;
   const int bits = a.item_bits;
@@ -1203,9 +1193,9 @@ extern "C" int trs_epoch_presort(const int32_t* stream_ui_dev, const int32_t* ne
   const dim3 gr(presort_grid(n_pos)), bl(TRS_BLOCK);
   const int pay_bits = bits_for(2 * batch);
   a.keys = nullptr;  // the grouping kernel reads pos / neg themselves
-  if (src == 0) hipLaunchKernelGGL((epoch_refs_kernel<uint32_t, 0>), gr, bl, 0, s, a);
-  else if (src == 1) hipLaunchKernelGGL((epoch_refs_kernel<uint32_t, 1>), gr, bl, 0, s, a);
-  else hipLaunchKernelGGL((epoch_refs_kernel<uint32_t, 2>), gr, bl, 0, s, a);
+  if (src == 0) hipLaunchKernelGGL((epoch_refs_kernel<0>), gr, bl, 0, s, a);
+  else if (src == 1) hipLaunchKernelGGL((epoch_refs_kernel<1>), gr, bl, 0, s, a);
+  else hipLaunchKernelGGL((epoch_refs_kernel<2>), gr, bl, 0, s, a);
   TRS_CHECK_LAUNCH("epoch_refs_kernel");
   const size_t n = (size_t)(2 * n_pos);
   (void)temp_bytes;
@@ -1332,8 +1322,8 @@ extern "C" int trs_epoch_flags_ordered(const int32_t* stream_ui_dev, const int32
     e.S = trs_sampler_args(sampler);
     e.hb = trs_feistel_half_bits(N * kn);
     const dim3 ge(presort_grid(e.n_pos)), be(TRS_BLOCK);
-    if (src == 1) hipLaunchKernelGGL((epoch_refs_kernel<uint32_t, 1>), ge, be, 0, s, e);
-    else hipLaunchKernelGGL((epoch_refs_kernel<uint32_t, 2>), ge, be, 0, s, e);
+    if (src == 1) hipLaunchKernelGGL((epoch_refs_kernel<1>), ge, be, 0, s, e);
+    else hipLaunchKernelGGL((epoch_refs_kernel<2>), ge, be, 0, s, e);
     TRS_CHECK_LAUNCH("epoch_refs_kernel");
     src = 0;  // the ids now exist (validated and clamped): the flags kernel takes them as given
   }
@@ -1412,7 +1402,7 @@ extern "C" int trs_epoch_user_dups(const int32_t* user_dev, int64_t n_batches, i
                                  kin + n_pos, (RefPayload*)(vin + n_pos), s, "trs_epoch_user_dups");
   if (rc) return rc;
   (void)hipMemsetAsync(flags_out_dev, 0, (size_t)n_pos, s);
-  hipLaunchKernelGGL((user_flags_kernel<uint32_t>), gr, bl, 0, s, kin + n_pos, vin + n_pos, n_pos, batch, flags_out_dev);
+  hipLaunchKernelGGL(user_flags_kernel, gr, bl, 0, s, kin + n_pos, vin + n_pos, n_pos, batch, flags_out_dev);
   if (sorted_ukeys_out) *sorted_ukeys_out = (void*)(kin + n_pos);
   if (ukey_bytes_out) *ukey_bytes_out = 4;
   if (sorted_uvals_out) *sorted_uvals_out = (void*)(vin + n_pos);
@@ -1473,43 +1463,31 @@ extern "C" int trs_epoch_presort_meta(const int32_t* pos_dev, const int32_t* neg
                          kin + n, vin + n, s, "trs_epoch_presort_meta");
 }
 
-// One launch of the sorted item update for a step (used by trs_train_steps_sgd's sorted mode).
-int trs_launch_sorted_item_update(const trs_tables* tables, const void* keys_step, const void* vals_step, int key_bytes,
-                                  int64_t batch, int64_t n_batches_bits_items, const float* gz, float lr,
-                                  uint64_t* uown, uint32_t* udup, uint32_t stamp, const float* ustage,
-                                  const int32_t* user_ids, hipStream_t s) {
+// The sorted-marks step's item update (trs_train_steps_sgd): sorted_item_update_kernel, one launch.
+int trs_launch_sorted_item_update(const trs_tables* tables, const void* keys_step, const void* vals_step, int64_t batch,
+                                  int64_t item_bits, const float* gz, float lr, uint64_t* uown, uint32_t* udup,
+                                  uint32_t stamp, const int32_t* user_ids, hipStream_t s) {
   SortedArgs a = {};
   a.T = *tables;
-  a.keys = keys_step;
+  a.keys = (const uint32_t*)keys_step;
   a.vals = (const RefPayload*)vals_step;
   a.user_ids = user_ids;
   a.B = batch;
-  a.item_bits = (int)n_batches_bits_items;
+  a.item_bits = (int)item_bits;
   a.gz = gz;
   a.lr = lr;
   a.uown = uown;
   a.udup = udup;
   a.stamp = stamp;
-  a.ustage = ustage;
   RowCfg c;
   TRS_TRY(row_cfg_for("trs_launch_sorted_item_update", tables->D, c));
   const int tpw = TRS_WAVE / c.g;
   const dim3 gr(trs_grid((2 * batch + tpw - 1) / tpw, TRS_BLOCK / TRS_WAVE)), bl(TRS_BLOCK);
-  const dim3 gs(trs_grid((2 * batch + RUN_CHUNK - 1) / RUN_CHUNK, 1));  // staged form: one 64-reference chunk per workgroup
   return for_row_shape(c, [&](auto V, auto G, auto K) {
-    constexpr int VV = V(), GG = G(), KK = K();
-    auto launch = [&](auto FULL) {
-      if (key_bytes == 4 && ustage)
-        hipLaunchKernelGGL((sorted_item_update_staged_kernel<uint32_t, VV, GG, KK, FULL()>), gs, bl, 0, s, a);
-      else if (key_bytes == 4)
-        hipLaunchKernelGGL((sorted_item_update_kernel<uint32_t, VV, GG, KK, FULL(), false>), gr, bl, 0, s, a);
-      else if (ustage)
-        hipLaunchKernelGGL((sorted_item_update_staged_kernel<uint64_t, VV, GG, KK, FULL()>), gs, bl, 0, s, a);
-      else
-        hipLaunchKernelGGL((sorted_item_update_kernel<uint64_t, VV, GG, KK, FULL(), false>), gr, bl, 0, s, a);
-    };
-    if (VV * GG * KK == tables->D) launch(std::true_type{});
-    else launch(std::false_type{});
+    if (V() * G() * K() == tables->D)
+      hipLaunchKernelGGL((sorted_item_update_kernel<V(), G(), K(), true>), gr, bl, 0, s, a);
+    else
+      hipLaunchKernelGGL((sorted_item_update_kernel<V(), G(), K(), false>), gr, bl, 0, s, a);
     TRS_CHECK_LAUNCH("sorted_item_update_kernel");
     return TRS_OK;
   });
@@ -1525,7 +1503,7 @@ int trs_launch_sorted_meta_update(const trs_tables* tables, int m, float* lin_or
                                   int64_t xpass, int fmsub, const OptArgs* opt, int parity, hipStream_t s) {
   SortedArgs a = {};
   a.T = *tables;
-  a.keys = keys_step;
+  a.keys = (const uint32_t*)keys_step;
   a.vals = (const RefPayload*)vals_step;
   a.B = batch;
   a.item_bits = bits_for(tables->n_meta[m]);
@@ -1548,11 +1526,11 @@ int trs_launch_sorted_meta_update(const trs_tables* tables, int m, float* lin_or
       constexpr int VV = V(), GG = G(), KK = K();
       if (VV * GG != tables->D) return 1;
       if (kind == OPT_ADAM) {
-        hipLaunchKernelGGL((sorted_item_update_staged_kernel<uint32_t, VV, GG, KK, true, OPT_ADAM>), gs, bl, 0, s, a);
+        hipLaunchKernelGGL((sorted_item_update_staged_kernel<VV, GG, KK, true, OPT_ADAM>), gs, bl, 0, s, a);
         hipLaunchKernelGGL((cut_rows_apply_kernel<VV, GG, KK, true, OPT_ADAM>), gc, bl, 0, s, T, a.o, a.parity, a.tab,
                            a.tab_lin);
       } else {
-        hipLaunchKernelGGL((sorted_item_update_staged_kernel<uint32_t, VV, GG, KK, true, OPT_ADAGRAD>), gs, bl, 0, s,
+        hipLaunchKernelGGL((sorted_item_update_staged_kernel<VV, GG, KK, true, OPT_ADAGRAD>), gs, bl, 0, s,
                            a);
         hipLaunchKernelGGL((cut_rows_apply_kernel<VV, GG, KK, true, OPT_ADAGRAD>), gc, bl, 0, s, T, a.o, a.parity,
                            a.tab, a.tab_lin);
@@ -1566,15 +1544,15 @@ int trs_launch_sorted_meta_update(const trs_tables* tables, int m, float* lin_or
   }
   return for_row_shape(c, [&](auto V, auto G, auto K) {
     if (V() * G() * K() == tables->D)
-      hipLaunchKernelGGL((sorted_item_update_staged_kernel<uint32_t, V(), G(), K(), true>), gs, bl, 0, s, a);
+      hipLaunchKernelGGL((sorted_item_update_staged_kernel<V(), G(), K(), true>), gs, bl, 0, s, a);
     else
-      hipLaunchKernelGGL((sorted_item_update_staged_kernel<uint32_t, V(), G(), K(), false>), gs, bl, 0, s, a);
+      hipLaunchKernelGGL((sorted_item_update_staged_kernel<V(), G(), K(), false>), gs, bl, 0, s, a);
     TRS_CHECK_LAUNCH("sorted_item_update_staged_kernel");
     return TRS_OK;
   });
 }
 
-// Fused launch of the staged item update and the duplicated-user update (both with 32-bit keys).
+// Fused launch of the staged item update and the duplicated-user update.
 int trs_launch_sorted_updates_fused(const trs_tables* tables, const void* keys_step, const void* vals_step,
                                     int64_t batch, int64_t item_bits, const float* gz, float lr, const float* ustage,
                                     const void* ukeys_step, const void* uvals_step, int64_t q0, const float* du,
@@ -1583,7 +1561,7 @@ int trs_launch_sorted_updates_fused(const trs_tables* tables, const void* keys_s
   SortedArgs ia = {};
   ia.skip_single = skip_single;
   ia.T = *tables;
-  ia.keys = keys_step;
+  ia.keys = (const uint32_t*)keys_step;
   ia.vals = (const RefPayload*)vals_step;
   ia.B = batch;
   ia.item_bits = (int)item_bits;
@@ -1592,7 +1570,7 @@ int trs_launch_sorted_updates_fused(const trs_tables* tables, const void* keys_s
   ia.ustage = ustage;
   UserDupArgs ua = {};
   ua.T = *tables;
-  ua.ukeys = ukeys_step;
+  ua.ukeys = (const uint32_t*)ukeys_step;
   ua.uvals = (const uint32_t*)uvals_step;
   ua.B = batch;
   ua.q0 = q0;
@@ -1634,37 +1612,6 @@ int trs_launch_sorted_updates_fused(const trs_tables* tables, const void* keys_s
     if (VV * GG * KK == tables->D) launch(std::true_type{});
     else launch(std::false_type{});
     TRS_CHECK_LAUNCH("sorted_updates_fused_kernel");
-    return TRS_OK;
-  });
-}
-
-int trs_launch_sorted_user_dup_update(const trs_tables* tables, const void* ukeys_step, const void* uvals_step,
-                                      int key_bytes, int64_t batch, int64_t q0, const float* du, const float* gz,
-                                      float lr, hipStream_t s) {
-  UserDupArgs a = {};
-  a.T = *tables;
-  a.ukeys = ukeys_step;
-  a.uvals = (const uint32_t*)uvals_step;
-  a.B = batch;
-  a.q0 = q0;
-  a.user_bits = bits_for(tables->n_users);
-  a.du = du;
-  a.gz = gz;
-  a.lr = lr;
-  RowCfg c;
-  TRS_TRY(row_cfg_for("trs_launch_sorted_user_dup_update", tables->D, c));
-  const dim3 gr(trs_grid((batch + TRS_WAVE - 1) / TRS_WAVE, TRS_BLOCK / TRS_WAVE)), bl(TRS_BLOCK);
-  return for_row_shape(c, [&](auto V, auto G, auto K) {
-    constexpr int VV = V(), GG = G(), KK = K();
-    auto launch = [&](auto FULL) {
-      if (key_bytes == 4)
-        hipLaunchKernelGGL((sorted_user_dup_update_kernel<uint32_t, VV, GG, KK, FULL()>), gr, bl, 0, s, a);
-      else
-        hipLaunchKernelGGL((sorted_user_dup_update_kernel<uint64_t, VV, GG, KK, FULL()>), gr, bl, 0, s, a);
-    };
-    if (VV * GG * KK == tables->D) launch(std::true_type{});
-    else launch(std::false_type{});
-    TRS_CHECK_LAUNCH("sorted_user_dup_update_kernel");
     return TRS_OK;
   });
 }

@@ -416,11 +416,9 @@ class SparseScorerTrainer:
                             self.gz, self.du, loss_sums, self.err, self.scratch, self._stamps(n_steps), evs, sk, sv,
                             ps.key_bytes, udup, self.ustage, usorted, opt, meta, idup, loss=self.loss_id)
         if te is not None:
-            # 32-bit keys: item and duplicated-user updates are ONE launch, and the last two events are recorded back to
-            # back — that interval is the cost of an event record itself
-            fused = ps.key_bytes == 4 and ps.ukey_bytes in (0, 4)
-            self._collect_events(te, ns, ("fwd_stage_kernel", "sorted_updates_fused_kernel", "event_overhead") if fused
-                                 else ("fwd_stage_kernel", "sorted_item_update_kernel", "sorted_user_dup_update_kernel"))
+            # item and duplicated-user updates are ONE launch, and the last two events are recorded back to back — that
+            # interval is the cost of an event record itself
+            self._collect_events(te, ns, ("fwd_stage_kernel", "sorted_updates_fused_kernel", "event_overhead"))
 
     def _adaptive_rule(self, n_steps):
         """_lib.TrsOpt of the next n_steps SparseAdam / Adagrad steps; moments live in optimizer.state[p] under torch's

@@ -204,7 +204,8 @@ def _samp(sampler):
 
 class EpochPresort:
     """Buffers + result of trs_epoch_presort for n_batches whole batches: id arrays and the item references of every
-    batch sorted by row.  `step_args(b)` gives what trs_train_steps_sgd needs to start at batch b of the slice."""
+    batch sorted by row (uint32 keys: key_bytes and, with the user sort, ukey_bytes are always 4).  `step_args(b)` gives
+    what trs_train_steps_sgd needs to start at batch b of the slice."""
 
     def __init__(self, n_batches, batch, n_users, n_items, device, item_meta=None, n_meta=(), user_sort=True,
                  item_flags=True):
@@ -374,7 +375,9 @@ def train_steps_sgd(net, T, stream_ui, neg_static, shuffle_key, sample_seed, fir
                     events=None, sorted_keys=None, sorted_vals=None, key_bytes=0, user_dup=None, ustage=None,
                     user_sorted=None, opt=None, meta=None, item_dup=None, loss=0, sync=None, n_flagged=None):
     """n_steps fused steps driven from C (trs_train_steps_sgd).  stream_ui None: the steps' ids are already in
-    user/pos/neg_buf.  events: optional flat list of 4*n_steps raw hipEvent_t handles.  opt: None (SGD with lr) or a
+    user/pos/neg_buf.  events: optional flat list of 4*n_steps raw hipEvent_t handles.  sorted_keys / user_sorted: the
+    sorted references of an EpochPresort; their keys are 4 bytes wide (key_bytes = 4, and 4 in user_sorted; 0 without
+    the arrays; the library refuses 8).  opt: None (SGD with lr) or a
     _lib.TrsOpt (SparseAdam / Adagrad on the presorted path; keep the tensors it points to alive).  item_dup: the
     presort's item-duplicate flags (plain SGD without metadata): K1 also updates item rows referenced once.  Flag mode
     (sparse regime): user_dup + item_dup from an EpochFlags, ustage, and no sorted references; sync = (zeroed int32
