@@ -101,14 +101,15 @@ const char* trs_last_error(void);
  *      the in-batch softmax group, trs_batch_prepare_mined, trs_batch_prepare_multi, trs_score_multi_fwd_bwd,
  *      trs_score_warp_fwd_bwd, TRS_LOSS_WARP, trs_stage_add_l2, trs_neighbour_fold, trs_neighbours_topk,
  *      trs_fold_in_users, trs_item_ranks, trs_item_ranks_workspace_bytes, trs_mmr_rerank, trs_list_ild,
- *      trs_fold_in_items, trs_als_gram, trs_als_gram_workspace_bytes, trs_als_solve.) */
+ *      trs_fold_in_items, trs_als_gram, trs_als_gram_workspace_bytes, trs_als_solve, trs_ease_gram, trs_ease_invert,
+ *      trs_ease_invert_workspace_bytes, trs_ease_weights, trs_ease_scores.) */
 #define TRS_ABI_VERSION 6
 #define TRS_SYNC_WORDS 288
 #define TRS_SYNC_REBASE 0x40000000u /* arrivals after which trs_train_steps_sgd zeroes sync_dev and its host count */
 int trs_abi_version(void);
 /* Tuning / A-B knobs of the launch paths (kernel selection, launch shapes): GRID_CAP, PASS_GRID_CAP, K1_ITERS,
  * PASS_ITERS, PRESORT_GRID_CAP, PASS_NT, K1_NT, K1_WGS_PER_CU, K1_APPLY_IN_LOOP, K1_APPLY_STATS, GEMM32_NO_GLDS,
- * GEMM16_TN_WIDE, GEMM16_TILE, GEMM16_NO_GLDS, BN_FINAL_TWO_SWEEPS, FOLDIN_DEPTH, RANKS_STAGES (meanings:
+ * GEMM16_TN_WIDE, GEMM16_TILE, GEMM16_NO_GLDS, BN_FINAL_TWO_SWEEPS, FOLDIN_DEPTH, RANKS_STAGES, EASE_STAGES (meanings:
  * csrc/trs_common.h TrsTuning).  The library reads TRS_<name> from the environment ONCE, at its first use; this entry
  * point changes a knob afterwards (tests, tools): unset != 0 restores the default.  The defaults are the measured best. */
 int trs_tuning_set(const char* name, int64_t value, int32_t unset);
@@ -808,6 +809,56 @@ int trs_als_gram(const float* rows_dev, int64_t n, int32_t D, int64_t ld, float*
 int trs_als_solve(const float* other_rows_dev, int64_t n_other, int32_t D, const float* G_dev, const trs_csr* nbr,
                   float lambda, float alpha, int32_t cg_steps, float* rows_inout_dev, int64_t n_rows,
                   int32_t* err_flag_dev, void* stream);
+
+/* ------------------------------------------------------------------- EASE (fit_ease) */
+/* Embarrassingly shallow autoencoder (Steck, WWW 2019): an item-item model with a closed form.  Added without touching
+ * an existing signature or struct.
+ *
+ *   X       the binary n_users x n items matrix of the DISTINCT (user, item) pairs of a CSR (repeated interactions
+ *           count once: Steck's definition; a sparse matrix built by summing duplicates would differ on such data)
+ *   A       = X^T X + lambda I, lambda > 0: symmetric positive definite, eigenvalues >= lambda
+ *   P       = A^-1
+ *   B[i][j] = -P[i][j] / P[j][j] for i != j, B[i][i] = 0 (column j divided by its own diagonal entry: not symmetric)
+ *   score(u, i) = sum_{j in hist(u)} B[j][i]: the score row of a user is the sum of the B rows of the user's items
+ *
+ * fp64 matrices are (nbar, nbar) row-major with row stride nbar = n rounded up to a multiple of TRS_EASE_NB.
+ *
+ * trs_ease_gram: A from the user -> items CSR hist (rows: sorted, distinct item ids).  A[i][j] = the number of users
+ *   holding both i and j, formed by fp64 atomic adds of 1.0 (integers below 2^53: exact in any order, so the result
+ *   does not depend on the launch), then A[i][i] += lambda with one rounding.  Padding (index >= n): 1 on the diagonal,
+ *   0 elsewhere, so the padded matrix is SPD and its inverse is P beside an identity block.  An item id outside [0, n)
+ *   is never used as an address: the pair is skipped and bit 0 of *err_flag_dev (may be NULL) is set.
+ * trs_ease_invert: P = A^-1 in place, with one workspace of trs_ease_invert_workspace_bytes(n) = nbar * nbar * 8 bytes.
+ *   Only the lower triangle of A is read.  Blocked Cholesky route, block size NB = TRS_EASE_NB, every launch on
+ *   `stream`, no host synchronisation:
+ *     1. right-looking factorisation: per block column k the diagonal block A_kk = L_kk L_kk^T and W_kk = L_kk^-1 (one
+ *        workgroup, in LDS), the panel L_ik = A_ik W_kk^T, the trailing update A_ij -= L_ik L_jk^T for i >= j > k;
+ *     2. M = L^-1 by block forward substitution: M_kk = W_kk, M_ik = -W_ii sum_{j=k}^{i-1} L_ij M_jk;
+ *     3. P = M^T M (lower tiles, then the mirror image: P is exactly symmetric).
+ *   Every product runs on one fp64 matrix-core GEMM kernel with a fixed K order: the same input gives the same bits.
+ *   A pivot that is not positive and finite sets bit 0 of *err_flag_dev (required) and is replaced by 1.
+ *   Knob EASE_STAGES (timing only): bits 0 / 1 / 2 run phase 1 / 2 / 3; three calls with 1, 2 and 4 on the same
+ *   matrix and workspace are one inversion.
+ * trs_ease_weights: B (n, n) fp32 row-major, row stride n, from P: the division in fp64, rounded to fp32 once; the
+ *   diagonal exactly 0.
+ * trs_ease_scores: out (n_rows, n) fp32; out[r] = sum of B[j] over the items j of row rows[r] of hist, in fp32, in
+ *   ascending CSR position from 0, one add per item (no fused multiply-add, never split across threads): a sequential
+ *   float32 loop reproduces it bit for bit.  An empty history gives a row of zeros.  rows may repeat.  A row index
+ *   outside the CSR counts as an empty history and an item id outside [0, n) is skipped; both set bit 0 of
+ *   *err_flag_dev (may be NULL).
+ * TRS_E_ARG, nothing launched: n outside 1..TRS_EASE_NMAX; lambda not finite or <= 0; a NULL matrix, workspace, CSR or
+ *   CSR array; hist->n_rows != n_users (trs_ease_gram); a workspace that is too small; a NULL err_flag
+ *   (trs_ease_invert).  trs_ease_scores with n_rows == 0: TRS_OK, nothing launched. */
+#define TRS_EASE_NB 64      /* block size of trs_ease_invert; fp64 matrices are padded to a multiple of it */
+#define TRS_EASE_NMAX 32768 /* largest catalogue: 2 x 8.6 GB fp64 plus 4.3 GB fp32 */
+int trs_ease_gram(const trs_csr* hist, int64_t n_users, int64_t n, double lambda, double* A_out_dev,
+                  int32_t* err_flag_dev, void* stream);
+int64_t trs_ease_invert_workspace_bytes(int64_t n);
+int trs_ease_invert(double* A_inout_dev, int64_t n, void* workspace_dev, int64_t workspace_bytes, int32_t* err_flag_dev,
+                    void* stream);
+int trs_ease_weights(const double* P_dev, int64_t n, float* B_out_dev, void* stream);
+int trs_ease_scores(const float* B_dev, int64_t n, const trs_csr* hist, const int64_t* rows_dev, int64_t n_rows,
+                    float* out_dev, int32_t* err_flag_dev, void* stream);
 
 /* ------------------------------------------------- exact ranks (rank_items / evaluate_ranks) */
 /* Where given items land in a user's full ranking.  Added without touching an existing signature or struct.

@@ -15,6 +15,8 @@ LOSS_SAMPLED_SOFTMAX = 2  # TRS_LOSS_SAMPLED_SOFTMAX (trs_score_multi_fwd_bwd on
 LOSS_WARP = 3  # TRS_LOSS_WARP (trs_score_warp_fwd_bwd only: not a pair loss)
 RETRIEVE_KMAX = 128  # TRS_RETRIEVE_KMAX: largest k of the fused retrieval kernel
 RETRIEVE_DMAX = 256  # TRS_RETRIEVE_DMAX: largest D of the fused retrieval kernel
+EASE_NB = 64  # TRS_EASE_NB: fp64 matrices of the EASE solver are padded to a multiple of it
+EASE_NMAX = 32768  # TRS_EASE_NMAX: largest catalogue of fit_ease
 ABI_VERSION = 6  # == TRS_ABI_VERSION of include/trs.h (tests/test_abi.py)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -183,6 +185,11 @@ PROTOTYPES = {
     "trs_als_gram_workspace_bytes": (C.c_int64, [_i64, _i32]),
     "trs_als_gram": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _vp, _vp]),
     "trs_als_solve": (C.c_int, [_vp, _i64, _i32, _vp, C.POINTER(TrsCsr), _f, _f, _i32, _vp, _i64, _vp, _vp]),
+    "trs_ease_gram": (C.c_int, [C.POINTER(TrsCsr), _i64, _i64, C.c_double, _vp, _vp, _vp]),
+    "trs_ease_invert_workspace_bytes": (C.c_int64, [_i64]),
+    "trs_ease_invert": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
+    "trs_ease_weights": (C.c_int, [_vp, _i64, _vp, _vp]),
+    "trs_ease_scores": (C.c_int, [_vp, _i64, C.POINTER(TrsCsr), _vp, _i64, _vp, _vp, _vp]),
     "trs_item_ranks_workspace_bytes": (C.c_int64, [_i64, _i64]),
     "trs_item_ranks": (C.c_int, [C.c_int, _T, _vp, _i64, _vp, _i64, C.POINTER(TrsCsr), C.POINTER(TrsCsr), _vp, _vp, _vp,
                                  _i64, _vp]),

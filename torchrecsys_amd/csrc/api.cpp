@@ -43,6 +43,7 @@ const Knob KNOBS[] = {
     {"BN_FINAL_TWO_SWEEPS", nullptr, &TrsTuning::bn_final_two_sweeps, 0},
     {"FOLDIN_DEPTH", nullptr, &TrsTuning::foldin_depth, 4},
     {"RANKS_STAGES", nullptr, &TrsTuning::ranks_stages, 3},
+    {"EASE_STAGES", nullptr, &TrsTuning::ease_stages, 7},
 };
 TrsTuning g_tuning;
 std::once_flag g_tuning_once;

@@ -75,6 +75,7 @@ struct TrsTuning {
   int bn_final_two_sweeps;  // TRS_BN_FINAL_TWO_SWEEPS  1: the two-sweep finalise kernels
   int foldin_depth;       // TRS_FOLDIN_DEPTH    visits whose rows trs_fold_in_users keeps requested: 1 | 2 | 4 | 8 (4)
   int ranks_stages;       // TRS_RANKS_STAGES    launches of trs_item_ranks, for timing one alone: bit 0 keys, bit 1 counting (3)
+  int ease_stages;        // TRS_EASE_STAGES     phases of trs_ease_invert, for timing one alone: bit 0 factor, bit 1 triangular inverse, bit 2 product (7)
 };
 TrsTuning& trs_tuning();
 

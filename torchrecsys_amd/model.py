@@ -222,7 +222,7 @@ class TorchRecSys(torch.nn.Module):
 
     # ------------------------------------------------------------------------------------------------ net
     def _init_net(self, net_type='linear'):
-        assert net_type in ('linear', 'mlp', 'neucf', 'fm', 'lstm'), \
+        assert net_type in ('linear', 'mlp', 'neucf', 'fm', 'lstm', 'ease'), \
             'Net type must be one of "linear", "mlp", "neu", "ease" or "lstm"'
         kw = dict(n_users=self.n_users, n_items=self.n_items, n_metadata=self.metadata_size,
                   n_factors=self.n_factors, use_metadata=self.use_metadata, use_cuda=self.use_cuda)
@@ -237,6 +237,14 @@ class TorchRecSys(torch.nn.Module):
         elif net_type == 'fm':
             print('Factorization Machine')
             self.net = FM(**kw)
+        elif net_type == 'ease':
+            print('Embarrassingly Shallow Autoencoder')
+            if self.use_metadata:
+                raise ValueError("net_type='ease' takes no metadata columns: the model is an item-item weight matrix "
+                                 "over the interactions alone")
+            from .collaborative.ease import EASE
+            self.net = EASE(n_users=self.n_users, n_items=self.n_items)  # n_factors is ignored
+            self.net.bind_history(self._seen_csr)
         else:  # the reference silently leaves self.net undefined here (model.py:162-166)
             raise NotImplementedError(f'{net_type} is not implemented (nor is it in the reference)')
         # parameters are created on the host from torch's CPU generator (bit-identical init), then live in HBM
@@ -388,7 +396,14 @@ class TorchRecSys(torch.nn.Module):
             self._dev_cache['item_meta'] = torch.from_numpy(tab).to(torch.int32).to(_device())
         return self._dev_cache['item_meta']
 
+    def _refuse_ease(self, what, instead, exc=NotImplementedError):
+        """net_type='ease' has no embedding rows, no gradient steps and no pairwise loss: say what to call instead."""
+        if self.net_type == 'ease':
+            raise exc(f"{what} does not apply to net_type='ease' (a closed-form item-item model without embedding "
+                      f"rows): {instead}")
+
     def _make_trainer(self, optimizer, batch_size):
+        self._refuse_ease("fit() / make_runner()", "call fit_ease()")
         if self.net_type == 'mlp':
             from .mlp_engine import MLPTrainer
             return MLPTrainer(self.net, optimizer, batch_size)
@@ -494,6 +509,7 @@ class TorchRecSys(torch.nn.Module):
         # loss: 'hinge' = the reference's only loss (helper/loss.py:5-9, model.py:282); 'bpr' = -log sigmoid(pos - neg),
         # the alternative BASELINE.json's north_star names (evaluate() then reports that loss too); 'softmax' = the
         # in-batch softmax (engine.SparseScorerTrainer.softmax_step; not a pair loss, so not in LOSS_ID)
+        self._refuse_ease("fit()", "call fit_ease(), which needs no optimiser")
         from ._lib import LOSS_ID, LOSS_SAMPLED_SOFTMAX
         if loss not in LOSS_ID and loss not in ('softmax', 'sampled_softmax', 'warp'):
             raise ValueError(f"loss must be one of {sorted(list(LOSS_ID) + ['softmax', 'sampled_softmax', 'warp'])}")
@@ -631,6 +647,7 @@ class TorchRecSys(torch.nn.Module):
     # ------------------------------------------------------------------------------------------------ ALS
     def _check_fit_als(self, iterations, regularization, alpha, cg_steps):
         """Argument checks of fit_als (before any device work)."""
+        self._refuse_ease("fit_als()", "call fit_ease()", ValueError)
         if self.net_type not in ('linear', 'fm'):
             raise ValueError(f"fit_als needs net_type 'linear' or 'fm': with net_type={self.net_type!r} (mlp) a score "
                              "is not the inner product of a user row and an item row")
@@ -737,12 +754,122 @@ class TorchRecSys(torch.nn.Module):
         check_err_flag(err, "fit_als")
         return torch.tensor(losses, dtype=torch.float64) if return_loss else None
 
+    # ------------------------------------------------------------------------------------------------ EASE
+    @_host_side
+    def fit_ease(self, regularization: float = 0.5):
+        """Closed-form EASE (Steck 2019; reference collaborative/ease.py) on the train split's distinct (user, item)
+        pairs X:  P = (X^T X + regularization I)^-1,  B[i][j] = -P[i][j] / P[j][j],  B[i][i] = 0;  a user's scores are
+        the sum of the B rows of the user's train items.  No learning rate, no sampler, deterministic: two calls give
+        the same B bit for bit.  regularization defaults to the reference's lambda_ = 0.5, which suits toy data; real
+        data usually wants hundreds (Steck reports 500 for ML-20M, 1000 for Netflix).
+        X is binary: a pair that occurs several times counts once (Steck's definition; the reference's sparse matrix adds
+        repeats up, and agrees on data without them).
+        Device work: trs_ease_gram (fp64 atomics of exact integer counts), trs_ease_invert (blocked Cholesky, triangular
+        inverse and product on the fp64 matrix cores), trs_ease_weights (fp32 B); the rule is in include/trs.h "EASE".
+        Memory: two fp64 matrices and the fp32 B, 20 bytes per entry of the catalogue squared (padded to a multiple of
+        64) — 5.4 GB at 16 384 items, 21.5 GB at TRS_EASE_NMAX = 32 768; the fp64 matrices are freed on return and B
+        (4 n_items^2 bytes) stays as a buffer of the net, in state_dict().
+        Afterwards predict(), predict_many(), recommend(), rank_items(), evaluate_ranking(), evaluate_ranks(),
+        recommend_for_histories() and item_weights() answer from B.
+        Before any device work: ValueError for another net_type, a regularization that is not a finite number > 0 or
+        n_items > TRS_EASE_NMAX; NotImplementedError under torch.distributed with more than one rank (the seen CSR is
+        this rank's shard); RuntimeError when the device reports less free memory than the 20 bytes per entry."""
+        if self.net_type != 'ease':
+            raise ValueError(f"fit_ease needs net_type='ease', not {self.net_type!r}: call fit() or fit_als()")
+        lam = regularization
+        ok = isinstance(lam, (int, float, np.integer, np.floating)) and not isinstance(lam, bool) and math.isfinite(lam)
+        if not ok or not lam > 0:
+            raise ValueError(f"regularization must be a finite number > 0, got {regularization!r}")
+        nmax = ops._lib.EASE_NMAX
+        if self.n_items > nmax:
+            raise ValueError(f"fit_ease takes n_items <= {nmax} (TRS_EASE_NMAX), got {self.n_items}: the dense weight "
+                             f"matrix and the two fp64 work matrices need 20 * n_items^2 bytes of device memory, "
+                             f"{20 * self.n_items ** 2 / 1e9:.1f} GB here")
+        if tdist.world_info()[1] > 1:
+            raise NotImplementedError("fit_ease runs in a single process: under torch.distributed (world > 1) the seen "
+                                      "CSR is this rank's shard of the interactions, and X^T X needs all of them")
+        _device()
+        nbar = ops.ease_padded(self.n_items)
+        need = 20 * nbar * nbar
+        free = int(torch.cuda.mem_get_info()[0])
+        if free < need:
+            raise RuntimeError(f"fit_ease needs {need / 1e9:.2f} GB of free device memory for {self.n_items} items (two "
+                               f"fp64 matrices and the fp32 weights), the device reports {free / 1e9:.2f} GB free")
+        seen = self._seen_csr()
+        err = torch.zeros(2, dtype=torch.int32, device=seen[0].device)
+        A = ops.ease_gram(seen, self.n_items, float(lam), err[0:1])
+        ops.ease_invert(A, err[1:2])
+        B = ops.ease_weights(A, self.n_items)
+        del A
+        check_err_flag(err[0:1], "fit_ease")
+        if int(err[1].item()):
+            raise RuntimeError("fit_ease: X^T X + regularization I is not numerically positive definite (a pivot of the "
+                               "Cholesky factorisation was not positive and finite); raise regularization")
+        self.net.set_weights(B, seen)
+
+    def _ease_recommend_for_histories(self, histories, top_k, exclude_seen, return_scores):
+        """recommend_for_histories on an EASE model: score rows of the histories' own CSR, mask, top-k, ids back."""
+        off, items, rank = self._history_csr(histories)
+        n = rank.size
+        k = min(int(top_k), self.n_items)
+        if k <= 0 or n == 0:
+            return self._empty_topk(n, k, return_scores)
+        B = self.net.weights()
+        dev = B.device
+        hist = (torch.from_numpy(off).to(dev), torch.from_numpy(items).to(dev))
+        mask = bool(exclude_seen) and items.size > 0  # every history empty: nothing to exclude
+        ids = torch.empty((n, k), dtype=torch.int64, device=dev)
+        scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+        for s in range(0, n, self.GENERIC_CHUNK):
+            us = torch.arange(s, min(s + self.GENERIC_CHUNK, n), dtype=torch.int64, device=dev)
+            rows = ops.ease_scores(B, hist, us)
+            if mask:
+                ops.mask_seen(rows, us, hist)
+                n_seen = hist[0][us + 1] - hist[0][us]
+            else:
+                n_seen = torch.zeros_like(us)
+            ids[s:s + us.numel()], scores[s:s + us.numel()] = self._topk_rows(rows, rows, k, self.n_items - n_seen)
+        r = torch.from_numpy(rank)
+        ids = self._original_ids(ids.cpu()[r], getattr(self.data_processor, "item_index", None))
+        return (ids, scores.cpu()[r]) if return_scores else ids
+
+    @_host_side
+    def item_weights(self, item_ids, top_k: int = 10, return_scores: bool = False):
+        """The top_k largest weights of row B[i, :] for each of several items (the reference's EASE.get_similarity): an
+        (n, k) int64 CPU tensor of original item ids, k = min(top_k, n_items); with return_scores also the (n, k) fp32
+        weights.  Order: weight descending, ties by ascending item row; the item itself is never returned, so the
+        positions beyond the n_items - 1 other items hold id -1 and weight -inf.  B[i, j] is what having item i adds to
+        the score of item j.  An unknown id raises IndexError; another net_type ValueError."""
+        if self.net_type != 'ease':
+            raise ValueError(f"item_weights needs net_type='ease', not {self.net_type!r}: call similar_items()")
+        index = getattr(self.data_processor, "item_index", None)
+        qlist = item_ids.tolist() if hasattr(item_ids, "tolist") else list(item_ids)
+        k = min(int(top_k), self.n_items)
+        if k <= 0 or not qlist:
+            return self._empty_topk(len(qlist), k, return_scores)
+        B = self.net.weights()
+        dev = B.device
+        queries = self._dense_rows(qlist, index, self.n_items, 'item').to(dev)
+        n = queries.numel()
+        ids = torch.empty((n, k), dtype=torch.int64, device=dev)
+        scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+        for s in range(0, n, self.GENERIC_CHUNK):
+            qs = queries[s:s + self.GENERIC_CHUNK]
+            g = qs.numel()
+            rows = B[qs].contiguous()
+            rows[torch.arange(g, device=dev), qs] = float('-inf')
+            ids[s:s + g], scores[s:s + g] = self._topk_rows(rows, rows, k, torch.full((g,), self.n_items - 1, device=dev))
+        ids = self._original_ids(ids.cpu(), index)
+        return (ids, scores.cpu()) if return_scores else ids
+
     # ------------------------------------------------------------------------------------------------ evaluate
     @_host_side
     def evaluate(self, batch_size=512, eval_metrics=['loss', 'auc']):
         """reference model.py:292-338: eval-mode scores of the test split, hinge loss and pairwise AUC per batch,
         unweighted means over batches, printed; returns None.  The printed values are kept at full precision in
         `self.eval_results` ({'loss': ..., 'auc': ...}, this rank's view of the means)."""
+        self._refuse_ease("evaluate() (a pairwise loss over sampled negatives)",
+                          "call evaluate_ranking() or evaluate_ranks()")
         self.net = self.net.eval()
         if self.data_processor.test_data.get('user_id', torch.empty(0)).numel() == 0:
             print("|--- No test data to evaluate.")
@@ -950,6 +1077,9 @@ class TorchRecSys(torch.nn.Module):
     def _generic_rows(self, us, meta, form):
         """Score rows of the dense users `us` (a GENERIC_CHUNK of them): (rows ranked by, rows in output units)."""
         dev = us.device
+        if hasattr(self.net, 'score_rows'):  # EASE: the chunk's rows in one launch
+            rows = self.net.score_rows(us)
+            return rows, rows
         if form is None:
             rows = torch.stack([self.net.score_all_items(int(u), meta) for u in us.tolist()])
             return rows, rows
@@ -1163,6 +1293,7 @@ class TorchRecSys(torch.nn.Module):
     # ------------------------------------------------------------------------------------------------ fold-in
     def _check_fold_in(self, what, epochs, lr, loss, l2, seed, max_tries, reject_seen):
         """Argument checks of fold_in_users / recommend_for_histories (before any device work)."""
+        self._refuse_ease(f"{what}()", "call recommend_for_histories(), which needs no fitting with EASE", ValueError)
         if self.net_type not in ('linear', 'fm'):
             raise ValueError(f"{what} needs net_type 'linear' or 'fm': with net_type={self.net_type!r} (mlp) a user is "
                              "not an inner-product row against a folded item matrix")
@@ -1260,6 +1391,12 @@ class TorchRecSys(torch.nn.Module):
         beyond the candidates hold id -1 / score -inf; ties by ascending item row.
         Only the fused kernel is offered: top_k > TRS_RETRIEVE_KMAX raises ValueError (the generic path of recommend()
         for larger k is out of scope here), as do the MLP and n_factors > TRS_RETRIEVE_DMAX."""
+        if self.net_type == 'ease':
+            if fold_in_options:
+                raise ValueError(f"recommend_for_histories with net_type='ease' takes no fold-in options (nothing is "
+                                 f"fitted: a history's scores are the sum of its items' rows of B), got "
+                                 f"{sorted(fold_in_options)}")
+            return self._ease_recommend_for_histories(histories, top_k, exclude_seen, return_scores)
         unknown = set(fold_in_options) - {'epochs', 'lr', 'loss', 'l2', 'seed', 'shuffle', 'reject_seen', 'max_tries'}
         if unknown:
             raise ValueError(f"unknown fold-in options {sorted(unknown)}")
@@ -1413,6 +1550,7 @@ class TorchRecSys(torch.nn.Module):
         512 MB at 1 M items x 128 factors — plus its fold; the model is never written or grown.  Only the fused kernel is
         offered: top_k > TRS_RETRIEVE_KMAX raises ValueError, as do the MLP and n_factors > TRS_RETRIEVE_DMAX."""
         what = "recommend_with_new_items"
+        self._refuse_ease(f"{what}()", "a new item needs a new fit_ease() over interactions that hold it", ValueError)
         if self.net_type not in ('linear', 'fm'):
             raise ValueError(f"{what} needs net_type 'linear' or 'fm', not {self.net_type!r} (mlp)")
         if self.n_factors > ops._lib.RETRIEVE_DMAX:
@@ -1491,6 +1629,7 @@ class TorchRecSys(torch.nn.Module):
 
     def _similar(self, what, query_ids, top_k, metric, return_scores):
         """similar_items / similar_users: argument checks (before any device work), id mapping, the search, ids back."""
+        self._refuse_ease(f"similar_{what}s()", "call item_weights() for an item's strongest weights", ValueError)
         if metric not in ('cosine', 'dot'):
             raise ValueError(f"metric must be 'cosine' or 'dot', got {metric!r}")
         if self.net_type not in ('linear', 'fm'):
@@ -1605,6 +1744,7 @@ class TorchRecSys(torch.nn.Module):
         pool > TRS_RETRIEVE_KMAX, a diversity outside [0, 1], an unknown metric.  Per call one item fold, one
         normalised copy of it and one selection launch per 65 536 users; under torch.distributed every rank answers
         from its own replica."""
+        self._refuse_ease("recommend_diverse()", "call recommend()", ValueError)
         k, pool = diversity_eval.check('recommend_diverse', self.net_type, self.n_factors, self.n_items, top_k,
                                        diversity, pool, metric, ops._lib.RETRIEVE_KMAX, ops._lib.RETRIEVE_DMAX)
         self.net = self.net.eval()
@@ -1695,6 +1835,7 @@ class TorchRecSys(torch.nn.Module):
           hit_rate@k, recall@k, ndcg@k   evaluate_ranking()'s formulas on the re-ranked lists
         Per-user values in float64, averaged over the evaluated users in ascending user order (evaluate/diversity.py).
         Under torch.distributed with more than one rank: ValueError (coverage needs the union over all ranks)."""
+        self._refuse_ease("evaluate_diversity()", "call evaluate_ranking() or evaluate_ranks()", ValueError)
         kk, pool = diversity_eval.check('evaluate_diversity', self.net_type, self.n_factors, self.n_items, k,
                                         diversity, pool, metric, ops._lib.RETRIEVE_KMAX, ops._lib.RETRIEVE_DMAX)
         rank, world = tdist.world_info()

@@ -932,6 +932,86 @@ def als_solve(other, G, nbr, regularization, alpha, cg_steps, rows_inout, err_fl
     return rows_inout
 
 
+def ease_padded(n):
+    """Row count and row stride of the fp64 matrices of the EASE solver: n rounded up to a multiple of TRS_EASE_NB."""
+    return -(-int(n) // _lib.EASE_NB) * _lib.EASE_NB
+
+
+def _csr_nonnull(off, items):
+    if items.numel() == 0:  # every list empty: the kernels read no id, but the CSR may not carry a NULL array
+        items = torch.zeros(1, dtype=torch.int32, device=off.device)
+    return csr(off, items), items
+
+
+def ease_gram(seen_csr, n_items, lam, err_flag=None):
+    """A = X^T X + lam I in fp64, (nbar, nbar) with nbar = ease_padded(n_items) and the padding an identity block
+    (trs_ease_gram; include/trs.h "EASE").  seen_csr: (offsets int64 (n_users + 1,), items int32) GPU CSR of sorted,
+    distinct item ids per user.  Exact: every entry is a count of users, plus lam on the diagonal."""
+    off, items = seen_csr
+    _dev(off, "CSR offsets", torch.int64)
+    _dev(items, "CSR items", torch.int32)
+    n, nbar = int(n_items), ease_padded(n_items)
+    if not 1 <= n <= _lib.EASE_NMAX:
+        raise ValueError(f"n_items={n} outside 1..{_lib.EASE_NMAX} (TRS_EASE_NMAX)")
+    A = torch.empty((nbar, nbar), dtype=torch.float64, device=off.device)
+    cs, keep = _csr_nonnull(off, items)
+    check(_lib.load().trs_ease_gram(C.byref(cs), off.numel() - 1, n, float(lam), ptr(A),
+                                    ptr(_dev(err_flag, "err_flag", torch.int32)), _stream()), "trs_ease_gram")
+    return A
+
+
+def ease_invert(A, err, workspace=None):
+    """P = A^-1 in place (trs_ease_invert: blocked Cholesky on the fp64 matrix cores) of the padded fp64 matrix
+    ease_gram returned; err: int32 GPU tensor whose bit 0 a pivot that is not positive and finite sets.  workspace: a
+    uint8 GPU tensor of trs_ease_invert_workspace_bytes to keep between calls (tools/ease_bench.py).  Returns A."""
+    lib = _lib.load()
+    _dev(A, "A", torch.float64)
+    _dev(err, "err_flag", torch.int32)
+    if err is None:
+        raise ValueError("ease_invert needs an err_flag tensor")
+    if A.dim() != 2 or A.shape[0] != A.shape[1] or A.shape[0] % _lib.EASE_NB or A.shape[0] == 0:
+        raise ValueError(f"A must be square with a multiple of {_lib.EASE_NB} rows (ease_gram's output), got "
+                         f"{tuple(A.shape)}")
+    n = A.shape[0]
+    ws_bytes = lib.trs_ease_invert_workspace_bytes(n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=A.device) if workspace is None else \
+        _dev(workspace, "workspace", torch.uint8)
+    check(lib.trs_ease_invert(ptr(A), n, ptr(ws), ws.numel(), ptr(err), _stream()), "trs_ease_invert")
+    return A
+
+
+def ease_weights(P, n):
+    """B (n, n) fp32 from the padded fp64 P = ease_invert(...): B[i][j] = -P[i][j] / P[j][j], B[i][i] = 0
+    (trs_ease_weights)."""
+    _dev(P, "P", torch.float64)
+    n = int(n)
+    if P.dim() != 2 or P.shape[0] != P.shape[1] or P.shape[0] != ease_padded(n) or n < 1:
+        raise ValueError(f"P must be ({ease_padded(n)}, {ease_padded(n)}) for n={n}, got {tuple(P.shape)}")
+    B = torch.empty((n, n), dtype=torch.float32, device=P.device)
+    check(_lib.load().trs_ease_weights(ptr(P), n, ptr(B), _stream()), "trs_ease_weights")
+    return B
+
+
+def ease_scores(B, hist_csr, rows, err_flag=None):
+    """Score rows (len(rows), n) fp32: row r = the sum of the rows of B that row rows[r] of hist_csr lists, in CSR order
+    (trs_ease_scores).  B (n, n) fp32; hist_csr (offsets int64, items int32) GPU CSR; rows int64 GPU tensor."""
+    _dev(B, "B", torch.float32)
+    _dev(rows, "rows", torch.int64)
+    off, items = hist_csr
+    _dev(off, "CSR offsets", torch.int64)
+    _dev(items, "CSR items", torch.int32)
+    if B.dim() != 2 or B.shape[0] != B.shape[1]:
+        raise ValueError(f"B must be square, got {tuple(B.shape)}")
+    n = B.shape[0]
+    out = torch.empty((rows.numel(), n), dtype=torch.float32, device=B.device)
+    if rows.numel() == 0:
+        return out
+    cs, keep = _csr_nonnull(off, items)
+    check(_lib.load().trs_ease_scores(ptr(B), n, C.byref(cs), ptr(rows), rows.numel(), ptr(out),
+                                      ptr(_dev(err_flag, "err_flag", torch.int32)), _stream()), "trs_ease_scores")
+    return out
+
+
 def item_ranks(net, T, fold, users, targets_csr, seen=None, want_values=False):
     """Exact ranks of each query's target items over the catalogue (trs_item_ranks; the definition is in
     include/trs.h "exact ranks").  users: dense int64 GPU tensor; targets_csr: (offsets int64 (n + 1,), items int32) GPU
