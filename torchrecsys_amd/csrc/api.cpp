@@ -36,6 +36,7 @@ const Knob KNOBS[] = {
     {"K1_WGS_PER_CU", nullptr, &TrsTuning::k1_wgs_per_cu, 2},
     {"K1_APPLY_IN_LOOP", nullptr, &TrsTuning::k1_apply_in_loop, 1},
     {"K1_APPLY_STATS", nullptr, &TrsTuning::k1_apply_stats, 0},
+    {"K1_FLAG_KERNEL", nullptr, &TrsTuning::k1_flag_kernel, 1},
     {"GEMM32_NO_GLDS", nullptr, &TrsTuning::gemm32_no_glds, 0},
     {"GEMM16_TN_WIDE", nullptr, &TrsTuning::gemm16_tn_wide, -1},
     {"GEMM16_TILE", nullptr, &TrsTuning::gemm16_tile, 0},

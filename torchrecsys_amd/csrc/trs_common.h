@@ -68,6 +68,7 @@ struct TrsTuning {
   int k1_wgs_per_cu;      // TRS_K1_WGS_PER_CU   workgroups per CU the one-launch step may count on being resident (2)
   int k1_apply_in_loop;   // TRS_K1_APPLY_IN_LOOP  one-launch step, flagged-first batches: flagged references applied inside the loop (1)
   int k1_apply_stats;     // TRS_K1_APPLY_STATS  1: count the references applied in the loop / in the tail into the last two words of sync_dev (0: tests only)
+  int k1_flag_kernel;     // TRS_K1_FLAG_KERNEL  one-launch step, flagged-first batches, whole rows: flag_step_kernel (1); 0: fwd_stage_kernel
   int gemm32_no_glds;     // TRS_GEMM32_NO_GLDS  1: fp32 NT GEMMs on the register-staged 128 x 128 kernel
   int gemm16_tn_wide;     // TRS_GEMM16_TN_WIDE  0 | 1: weight-gradient GEMMs on 256 x 256 tiles (-1)
   int gemm16_tile;        // TRS_GEMM16_TILE     128 | 256 | 512: force the bf16-resident tile (0)
