@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import large_tables
 import step_sensitivity as sens
 from conftest import rel_err
 from oracle import loader as oloader
@@ -1121,7 +1122,9 @@ def test_flag_mode_matches_oracle(net, D, skew, n_users, one_launch, tune):
     """The sparse regime's step (trs_epoch_flags + K1 taking every lone reference + flagged_update_kernel): rows
     referenced once in the batch updated in place by K1, the flagged references added with float atomics afterwards — 3
     batches in one C call == oracle SGD steps.  n_users = 3M: more rows than bitmap bits, so the user flags are
-    hashed (conservative) — flagged lone rows must still be exact.  Flags: exact where the table fits the bitmap.
+    hashed (conservative) — flagged lone rows must still be exact; the 3M-row user tables hold random values outside the
+    300 rows that occur, and every row no triple names must come back bit-identical.  Flags: exact where the table fits
+    the bitmap.
     one_launch: the same step as ONE launch (trs_train_args.sync_dev): K1's workgroups count themselves in on the
     arrival counter after their last row read, wait for the whole grid and apply the flagged references themselves;
     the library reports the arrivals it scheduled (3 launches x grid), and a second call continues the counter.
@@ -1132,10 +1135,13 @@ def test_flag_mode_matches_oracle(net, D, skew, n_users, one_launch, tune):
 
 
 @functools.lru_cache(maxsize=4)
-def flag_mode_case(net, D, skew, n_users, big=False, lr=None):
+def flag_mode_case(net, D, skew, n_users, big=False, lr=None, bands=False):
     """The input of check_flag_mode (no GPU): 3 batches of 512 on 300 users that occur (at their places in a table of
     n_users rows) and 57 or 5000 items, one hot item under skew.  big (the ordered form on the 3M-row table): mostly lone
-    references, 16 000 users and 20 000 items for batches of 2 048 — about 40 % of the triples carry a flag."""
+    references, 16 000 users and 20 000 items for batches of 2 048 — about 40 % of the triples carry a flag.
+    bands (tests/test_gpu_large_offsets.py): the users that occur sit at large_tables.band_rows of the n_users-row table
+    — every offset band and both sides of every boundary — and everything else (tables, triples, step size, and with
+    them the conditioning and the written-down seed bump) is the 3M-row case's."""
     def build(bump):
         rs = np.random.RandomState(D + skew + 1000 * bump)
         NU, NI, B, nb = n_users, 57 if n_users == 300 else 5000, 512, 3
@@ -1143,8 +1149,13 @@ def flag_mode_case(net, D, skew, n_users, big=False, lr=None):
         if big:
             NUS, NI, B = 16000, 20000, 2048
         p, _, _ = make_case(net, D, 0, 8, NU=NUS, NI=NI, seed=2)
-        urows = np.sort(rs.choice(NU, NUS, replace=False)) if NU > 300 else np.arange(300)  # the users that occur
+        if bands:
+            rs.choice(3_000_000, NUS, replace=False)  # (drawn and dropped: the triples below stay the 3M-row case's)
+        else:
+            urows = np.sort(rs.choice(NU, NUS, replace=False)) if NU > 300 else np.arange(300)  # the users that occur
         u_small = rs.randint(0, NUS, nb * B)
+        if bands:  # (users drawn by a triple take the boundary rows: the ids then name every band and boundary)
+            urows = large_tables.band_places(u_small, NUS, NU, D, seed=D)
         i = rs.randint(0, NI, nb * B)
         j = rs.randint(0, NI, nb * B)
         if skew:
@@ -1157,23 +1168,27 @@ def flag_mode_case(net, D, skew, n_users, big=False, lr=None):
                             bump=BIG_FLAG_MODE_BUMP.get((net, D, skew), 0) if big and lr is None else None)
 
 
-def check_flag_mode(net, D, skew, n_users, one_launch, tune, first_stamp=1, prepare_scratch=None):
+def check_flag_mode(net, D, skew, n_users, one_launch, tune, first_stamp=1, prepare_scratch=None, bands=False):
     ops = _ops()
     big = one_launch == "ordered" and n_users > 300
     if big:  # four iterations per wave: the workgroups count themselves in after iteration 2 of 4 (mid-loop)
         tune(K1_ITERS=4)
-    case = flag_mode_case(net, D, skew, n_users, big)
+    case = flag_mode_case(net, D, skew, n_users, big, bands=bands)
     p, NU, NI, NUS, B, nb, lr = case.p, case.NU, case.NI, case.NUS, case.B, case.nb, case.lr
     urows, u_small, i, j = case.urows, case.u_small, case.i, case.j
     u = urows[u_small]
     lin = ("user_bias.weight", "item_bias.weight") if net == "linear" else ("linear_user.weight", "linear_item.weight")
     t = {k: torch.from_numpy(v.copy()).to(DEV) for k, v in p.items()}
-    if NU > 300:  # full-size user tables holding the 300 small rows at their places
-        bigD = torch.zeros((NU, D), device=DEV)
+    named = np.unique(u)  # the user rows a triple names
+    if bands:
+        large_tables.assert_covers(named, NU, D)
+    if NU > 300:  # full-size user tables holding the 300 small rows at their places, random rows everywhere else
+        bigD = large_tables.fill(torch.empty((NU, D), device=DEV), seed=D)
         bigD[torch.from_numpy(urows).to(DEV)] = t["user.weight"]
-        big1 = torch.zeros((NU, 1), device=DEV)
+        big1 = large_tables.fill(torch.empty((NU, 1), device=DEV), seed=D + 1)
         big1[torch.from_numpy(urows).to(DEV)] = t[lin[0]]
         t["user.weight"], t[lin[0]] = bigD, big1
+        sums_before = {k: large_tables.row_checksums(t[k]) for k in ("user.weight", lin[0])}
     T, keep = ops.make_tables(t["user.weight"], t["item.weight"], t[lin[0]], t[lin[1]])
     err = torch.zeros(1, dtype=torch.int32, device=DEV)
     ordered = one_launch == "ordered"
@@ -1225,6 +1240,9 @@ def check_flag_mode(net, D, skew, n_users, one_launch, tune, first_stamp=1, prep
     ut = torch.from_numpy(urows).to(DEV)
     got = {k: (t[k][ut] if (NU > 300 and k in ("user.weight", lin[0])) else t[k]).cpu().numpy() for k in run.after}
     sens.criterion_for(case)(got, run.after, p)
+    if NU > 300:  # every row no triple names is bit-identical
+        for k, before in sums_before.items():
+            large_tables.assert_untouched(before, large_tables.row_checksums(t[k]), named, k)
     assert err.item() == 0
 
 
@@ -1423,8 +1441,11 @@ def test_presorted_adaptive_rules_match_the_oracle(net, D, skew, kind):
     check_presorted_adaptive_rules(net, D, skew, kind)
 
 
-def check_presorted_adaptive_rules(net, D, skew, kind, first_stamp=1, prepare_scratch=None):
-    """Returns the number of cut runs the last step listed."""
+def check_presorted_adaptive_rules(net, D, skew, kind, first_stamp=1, prepare_scratch=None, bands=False):
+    """Returns the number of cut runs the last step listed.  bands (tests/test_gpu_large_offsets.py): the same 300 users
+    sit at large_tables.band_rows of user tables with n_rows_for(D) rows — parameters AND state, random everywhere else
+    (the state non-negative, and zero on the rows that occur, as the oracle starts) — and every row no triple names
+    must come back bit-identical."""
     from torchrecsys_amd import _lib
     from oracle.nets import touched_rows
     ops = _ops()
@@ -1439,6 +1460,27 @@ def check_presorted_adaptive_rules(net, D, skew, kind, first_stamp=1, prepare_sc
     lin = ("user_bias.weight", "item_bias.weight") if net == "linear" else ("linear_user.weight", "linear_item.weight")
     names = ["user.weight", "item.weight", lin[0], lin[1]]
     t = {k: torch.from_numpy(v.copy()).to(DEV) for k, v in p.items()}
+    s1 = {k: torch.zeros_like(t[k]) for k in names}
+    s2 = {k: torch.zeros_like(t[k]) for k in names}
+    u_small, large = u, ()
+    if bands:
+        NU = large_tables.n_rows_for(D)
+        place = large_tables.band_places(u_small, 300, NU, D, seed=D + 1)  # small user j sits at row place[j]
+        u = place[u_small]
+        urows = np.unique(u)  # the rows a triple names: every other row stays as it is
+        large_tables.assert_covers(urows, NU, D)
+        ut, large = torch.from_numpy(place).to(DEV), (names[0], names[2])
+        for n_, k in enumerate(large):
+            w = t[k].shape[1]
+            small = t[k]
+            t[k] = large_tables.fill(torch.empty((NU, w), device=DEV), seed=10 * D + n_)
+            t[k][ut] = small
+            for m_, s_ in enumerate((s1, s2) if kind == "sparse_adam" else (s1,)):
+                s_[k] = large_tables.fill(torch.empty((NU, w), device=DEV), seed=10 * D + 2 + 2 * m_ + n_).abs_()
+                s_[k][ut] = 0.0
+        watched = {(name, k): tab[k] for name, tab in (("table", t), ("state 1", s1), ("state 2", s2)) for k in large
+                   if tab[k].shape[0] == NU}
+        sums_before = {key: large_tables.row_checksums(v) for key, v in watched.items()}
     T, keep = ops.make_tables(*(t[k] for k in names))
     err = torch.zeros(1, dtype=torch.int32, device=DEV)
     ps = ops.EpochPresort(nb, B, NU, NI, DEV)
@@ -1446,8 +1488,6 @@ def check_presorted_adaptive_rules(net, D, skew, kind, first_stamp=1, prepare_sc
     ids, sk, sv, udup, usorted, idup = ps.step_args(0)
     gz, du = torch.empty((2, B), device=DEV), torch.empty((B, D), device=DEV)
     losses = torch.zeros(nb, device=DEV)
-    s1 = {k: torch.zeros_like(t[k]) for k in names}
-    s2 = {k: torch.zeros_like(t[k]) for k in names}
     gacc, gacc_lin = torch.zeros_like(t["item.weight"]), torch.zeros_like(t[lin[1]])
     cut_rows = torch.empty(2 * B // 64 + 64, dtype=torch.int32, device=DEV)
     cut_count = torch.zeros(2, dtype=torch.int32, device=DEV)
@@ -1470,7 +1510,7 @@ def check_presorted_adaptive_rules(net, D, skew, kind, first_stamp=1, prepare_sc
     r1 = {k: np.zeros_like(v) for k, v in p.items()}
     r2 = {k: np.zeros_like(v) for k, v in p.items()}
     for b in range(nb):
-        batch = {"user_id": u[b * B:(b + 1) * B], "pos_item_id": i[b * B:(b + 1) * B], "neg_item_id": j[b * B:(b + 1) * B]}
+        batch = {"user_id": u_small[b * B:(b + 1) * B], "pos_item_id": i[b * B:(b + 1) * B], "neg_item_id": j[b * B:(b + 1) * B]}
         _, _, loss, grads = onets.train_forward_backward(net, ref, batch)
         rows = touched_rows(net, ref, batch)
         for k in names:
@@ -1483,6 +1523,12 @@ def check_presorted_adaptive_rules(net, D, skew, kind, first_stamp=1, prepare_sc
         """fraction of rows whose largest deviation is below tol * max|want|"""
         return float((np.abs(got - want).max(axis=1) <= tol * np.abs(want).max()).mean())
 
+    for key, v in (watched.items() if bands else ()):  # rows no triple names: bit-identical, parameters and state
+        large_tables.assert_untouched(sums_before.pop(key), large_tables.row_checksums(v), urows, " ".join(key))
+    for tab in ((t, s1, s2) if bands else ()):       # the compacted rows of the large tables, for the criteria below
+        for k in large:
+            if tab[k].shape[0] == NU:
+                tab[k] = tab[k][ut]
     for k in names:
         # Both rules divide by a norm of the row's own gradient history, so a coalesced gradient that cancels to rounding
         # noise (the skewed cases make a user meet the hot item as positive of one triple and negative of another) is
