@@ -102,7 +102,7 @@ const char* trs_last_error(void);
  *      trs_score_warp_fwd_bwd, TRS_LOSS_WARP, trs_stage_add_l2, trs_neighbour_fold, trs_neighbours_topk,
  *      trs_fold_in_users, trs_item_ranks, trs_item_ranks_workspace_bytes, trs_mmr_rerank, trs_list_ild,
  *      trs_fold_in_items, trs_als_gram, trs_als_gram_workspace_bytes, trs_als_solve, trs_ease_gram, trs_ease_invert,
- *      trs_ease_invert_workspace_bytes, trs_ease_weights, trs_ease_scores.) */
+ *      trs_ease_invert_workspace_bytes, trs_ease_weights, trs_ease_scores, trs_seq_fwd_bwd, trs_seq_user_rows.) */
 #define TRS_ABI_VERSION 6
 #define TRS_SYNC_WORDS 288
 #define TRS_SYNC_REBASE 0x40000000u /* arrivals after which trs_train_steps_sgd zeroes sync_dev and its host count */
@@ -647,6 +647,63 @@ int trs_mask_seen(float* scores_dev, int64_t n_rows, int64_t n_items, const int6
  * idcg = sum_{r<min(k,|T_u|)} 1/log2(r+2), n_rel = |T_u|), sums in ascending r. */
 int trs_rank_metrics(const int64_t* ids_dev, int64_t n_q, int32_t k, const int64_t* users_dev, const trs_csr* rel,
                      double* metrics_out_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------- sequence model */
+/* A factorised Markov model over the last L items of a user's ORDERED history (model.py fit_sequence, DESIGN.md 4.18;
+ * FPMC for L = 1, the Fossil family for L > 1; the reference names a sequence model as "yet to come" and has none, so
+ * this contract, not a reference output, pins it).  Added without touching an existing signature or struct.
+ * Tables: the Linear scorer's U = tables->user (n_users, D), V = tables->item (n_items, D), b = tables->item_lin
+ * (n_items, 1), without metadata (tables->M == 0), plus the context table C = ctx (n_items, D).  Fixed weights
+ * w_0 .. w_{L-1} (ctx_weight, L floats on the device); l = 0 is the most recent item.
+ * Sequences: a trs_csr whose rows are NOT sorted: items[off[u] .. off[u+1]) is user u's sequence s_u, oldest first,
+ * repeated items kept.  For position k of s_u slot l is present iff l < k (absent slots are always the oldest ones):
+ *   q(u, k)   = U[u] + sum_{l < min(L, k)} w_l * C[s_u[k-1-l]]     added in the order l = 0, 1, ...: per element the
+ *               product, then the sum, two fp32 roundings; an absent slot adds nothing (q keeps its bits)
+ *   z(u,k,i)  = <q(u, k), V[i]> + b[i]     (per lane the products of its columns summed in ascending column order from
+ *               0, the lanes of the group by the xor butterfly: trs_score_fwd_bwd's inner product, on q)
+ *   row loss  = pair(z(u,k,p), z(u,k,n)), p = s_u[k], n the given negative: trs_score_fwd_bwd's pair loss (hinge =
+ *               max(0, z_n - z_p + 1), bpr = -log sigmoid(z_p - z_n)).
+ * With gp = d loss / d z_p * inv_B and gn = -gp:  dU[u] = gp V[p] + gn V[n],  dV[p] = gp q,  dV[n] = gn q,  db[p] = gp,
+ * db[n] = gn,  dC[s_u[k-1-l]] = w_l * dU[u] for every present slot.  All rows are read from the PRE-update tables.  The
+ * user's 1-wide table (tables->user_lin) takes no part: it enters both z alike and its gradient is 0.  With C = 0 or
+ * L = 0 the staged user / item fields, grad_lin and the loss are trs_score_fwd_bwd(TRS_NET_LINEAR)'s on the same (user,
+ * positive, negative) with a zero user_lin, bit for bit. */
+#define TRS_SEQ_LMAX 16 /* largest context length L */
+/* trs_seq_fwd_bwd: one training pass over B triples (user[t], entry[t], neg[t]): entry[t] (int64) is a position in the
+ * CSR's item array, from which the kernel derives k = entry - off[user], p = items[entry] and the context ids
+ * items[entry-1-l] — no (N, L) context array exists.  loss_sum += the sum of the row losses (the caller divides by B);
+ * auc_count (may be NULL) += #(z_p > z_n).  Both are ACCUMULATED.  inv_B = 1/B of the mean.
+ * Staged gradients, field-major: grad_rows (3 + L, B, D) and grad_lin (3, B); field 0 the user, 1 the positive, 2 the
+ * negative (trs_score_fwd_bwd's order), field 3 + l context slot l.  ctx_ids_out (L, B) int32: the row of C each slot's
+ * gradient belongs to.  An absent slot gets id 0 and an all-zero gradient row, so a scatter adds -lr * 0 to row 0.
+ * grad_rows == NULL (then grad_lin must be NULL too): forward only — the same loss and AUC count, nothing staged.
+ * A user outside [0, min(n_users, seq->n_rows)), a negative, positive or present context id outside [0, n_items), or an
+ * entry outside its user's range [off[user], off[user+1]) is clamped for addressing, sets bit 0 of *err_flag_dev (may be
+ * NULL) and zeroes its row's loss and gradients.
+ * TRS_E_ARG, nothing launched: tables NULL or a NULL member (user, item and both 1-wide tables); tables->M != 0; a D the
+ * scorer kernels do not take; ctx NULL; seq NULL, without offsets or item ids, or with no rows; L outside
+ * 0..TRS_SEQ_LMAX; ctx_weight NULL with L > 0; a loss id other than TRS_LOSS_HINGE / TRS_LOSS_BPR; loss_sum NULL;
+ * grad_lin without grad_rows or the reverse; ctx_ids_out NULL while gradients of L > 0 slots are staged; B < 0; NULL
+ * ids with B > 0. */
+int trs_seq_fwd_bwd(const trs_tables* tables, const float* ctx_dev, const trs_csr* seq, const int32_t* user_dev,
+                    const int64_t* entry_dev, const int32_t* neg_dev, int64_t B, int32_t L,
+                    const float* ctx_weight_dev, int32_t loss, float inv_B, float* loss_sum_dev,
+                    int32_t* auc_count_dev, float* grad_rows_dev, float* grad_lin_dev, int32_t* ctx_ids_out_dev,
+                    int32_t* err_flag_dev, void* stream);
+/* trs_seq_user_rows: query rows for retrieval.  seq has one row per output row (seq->n_rows == n), oldest first; for
+ * r < n, with len = the row's length:
+ *   out[r*ld .. r*ld + D) = (U[users[r]], or 0 when users[r] < 0 or users_dev is NULL) + sum_{l < min(L, len)} w_l *
+ *   C[row r's item len-1-l], in the order and roundings of q above (l = 0, the row's LAST item, first).
+ * ld >= D floats is the caller's row stride (a multiple of 4 when D is); columns D .. ld-1 are not written.  No bias: b
+ * stays with the item side.  One launch, one writer per row, no atomics: a float32 loop on the host reproduces the rows
+ * bit for bit.  A user >= n_users or a context id outside [0, n_items) sets bit 0 of *err_flag_dev (may be NULL) and
+ * zeroes the row.
+ * TRS_E_ARG, nothing launched: the table, context, CSR, L and ctx_weight grounds of trs_seq_fwd_bwd (item ids may be
+ * NULL only with L == 0: the host cannot see that every row is empty, so a caller without any id passes a one-element
+ * buffer, which is never read); seq->n_rows != n; n < 0; ld < D, or not a multiple of 4 with D % 4 == 0; out NULL with n > 0. */
+int trs_seq_user_rows(const trs_tables* tables, const float* ctx_dev, const trs_csr* seq, const int64_t* users_dev,
+                      int64_t n, int32_t L, const float* ctx_weight_dev, float* out_dev, int64_t ld,
+                      int32_t* err_flag_dev, void* stream);
 
 /* ------------------------------------------------------------------- nearest neighbours (similar_items / _users) */
 /* Neighbour search over the rows of one table (model.py similar_items / similar_users): the similarity

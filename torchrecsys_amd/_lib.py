@@ -17,6 +17,7 @@ RETRIEVE_KMAX = 128  # TRS_RETRIEVE_KMAX: largest k of the fused retrieval kerne
 RETRIEVE_DMAX = 256  # TRS_RETRIEVE_DMAX: largest D of the fused retrieval kernel
 EASE_NB = 64  # TRS_EASE_NB: fp64 matrices of the EASE solver are padded to a multiple of it
 EASE_NMAX = 32768  # TRS_EASE_NMAX: largest catalogue of fit_ease
+SEQ_LMAX = 16  # TRS_SEQ_LMAX: largest context length of the sequence model
 ABI_VERSION = 6  # == TRS_ABI_VERSION of include/trs.h (tests/test_abi.py)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -190,6 +191,9 @@ PROTOTYPES = {
     "trs_ease_invert": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
     "trs_ease_weights": (C.c_int, [_vp, _i64, _vp, _vp]),
     "trs_ease_scores": (C.c_int, [_vp, _i64, C.POINTER(TrsCsr), _vp, _i64, _vp, _vp, _vp]),
+    "trs_seq_fwd_bwd": (C.c_int, [_T, _vp, C.POINTER(TrsCsr), _vp, _vp, _vp, _i64, _i32, _vp, _i32, _f, _vp, _vp, _vp,
+                                  _vp, _vp, _vp, _vp]),
+    "trs_seq_user_rows": (C.c_int, [_T, _vp, C.POINTER(TrsCsr), _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp]),
     "trs_item_ranks_workspace_bytes": (C.c_int64, [_i64, _i64]),
     "trs_item_ranks": (C.c_int, [C.c_int, _T, _vp, _i64, _vp, _i64, C.POINTER(TrsCsr), C.POINTER(TrsCsr), _vp, _vp, _vp,
                                  _i64, _vp]),

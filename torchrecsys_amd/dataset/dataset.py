@@ -105,8 +105,18 @@ class ProcessData(Data):
             tr, te = perm[n_test:], perm[:n_test]
         else:
             tr, te = np.arange(N), np.arange(0)
+        self.n_input_rows = N
         self.train_data = self._rows_to_tensor_dict(tr, has_meta)
         self.test_data = self._rows_to_tensor_dict(te, has_meta)
+
+    def train_rows(self):
+        """Input position of every train row, in train_data's order (the split's permutation, drawn again: it is not
+        kept).  int64 CPU tensor."""
+        N = self.n_input_rows
+        if self.split_ratio < 1:
+            n_test = int(math.ceil((1 - self.split_ratio) * N))
+            return torch.from_numpy(np.random.RandomState(42).permutation(N)[n_test:].astype(np.int64))
+        return torch.arange(N, dtype=torch.int64)
 
     def _rows_to_tensor_dict(self, rows, has_meta):
         d = {"user_id": torch.from_numpy(self._users[rows]).long(),
@@ -198,23 +208,31 @@ class TensorProcessData:
         self.item_to_metadata_map = None
         self.meta_data_df = None
 
+    def _split_rows(self, N, device, on_gpu):
+        """(train rows, test rows): input positions in the split's order (a permutation, not ascending)."""
+        if self.split_ratio < 1:
+            n_test = int(math.ceil((1 - self.split_ratio) * N))
+            if self.split == 'device' and on_gpu:
+                g = torch.Generator(device=device)
+                g.manual_seed(42)
+                perm = torch.randperm(N, device=device, generator=g)
+            else:  # the reference's permutation, drawn where numpy lives and applied where the ids live
+                perm = torch.from_numpy(np.random.RandomState(42).permutation(N))
+                if on_gpu:
+                    perm = (perm.to(torch.int32) if N < 2 ** 31 else perm).to(device).long()
+            return perm[n_test:], perm[:n_test]
+        tr = torch.arange(N, device=device)
+        return tr, tr[:0]
+
+    def train_rows(self):
+        """Input position of every train row, in train_data's order (the split drawn again: it is not kept)."""
+        return self._split_rows(self.n_input_rows, self._split_device, self._split_device.type == 'cuda')[0].to(torch.int64)
+
     def prepare_data(self):
         N = self._users.shape[0]
         self.config = {"num_users": self.num_users, "num_items": self.num_items, "num_metadata": self.metadata_size}
-        if self.split_ratio < 1:
-            n_test = int(math.ceil((1 - self.split_ratio) * N))
-            if self.split == 'device' and self._users.is_cuda:
-                g = torch.Generator(device=self._users.device)
-                g.manual_seed(42)
-                perm = torch.randperm(N, device=self._users.device, generator=g)
-            else:  # the reference's permutation, drawn where numpy lives and applied where the ids live
-                perm = torch.from_numpy(np.random.RandomState(42).permutation(N))
-                if self._users.is_cuda:
-                    perm = (perm.to(torch.int32) if N < 2 ** 31 else perm).to(self._users.device).long()
-            tr, te = perm[n_test:], perm[:n_test]
-        else:
-            tr = torch.arange(N, device=self._users.device)
-            te = tr[:0]
+        self.n_input_rows, self._split_device = N, self._users.device
+        tr, te = self._split_rows(N, self._users.device, self._users.is_cuda)
         self.train_data, self.test_data = self._rows(tr), self._rows(te)
         self._users = self._items = self._neg = None  # the split copies are the only ones kept
 

@@ -680,3 +680,53 @@ class SparseScorerTrainer:
 
 def net_has_meta_lin(net):
     return bool(getattr(net, "META_LIN_NAME", None))
+
+
+class SequenceTrainer:
+    """Plain-SGD steps of the sequence model (include/trs.h "sequence model") on a Linear net without
+    metadata: U, V and b are the net's tables, ctx the context table C (n_items, D), weights the (L,) fixed slot weights,
+    seq = (offsets, item ids) the ordered CSR on the device.  One step = trs_sample_neg, trs_seq_fwd_bwd, then each
+    table's block of the staging buffer through ops.rows_scatter_add at -lr (U: B rows, V and b: 2B, C: L * B).  No
+    optimiser object and no host sync: the loss is accumulated where the caller says."""
+
+    def __init__(self, net, ctx, weights, seq, batch_capacity, lr, loss_id):
+        ps = net.table_params()
+        self.net, self.ctx, self.weights, self.seq = net, ctx, weights, seq
+        self.user, self.item, self.item_lin = ps[0].data, ps[1].data, ps[3].data
+        self.dev, self.D, self.L = self.user.device, self.user.shape[1], int(weights.numel())
+        self.cap, self.lr, self.loss_id = int(batch_capacity), float(lr), int(loss_id)
+        self.n_items = self.item.shape[0]
+        F = 3 + self.L
+        self.grad_rows = torch.empty(F * self.cap * self.D, dtype=torch.float32, device=self.dev)
+        self.grad_lin = torch.empty(3 * self.cap, dtype=torch.float32, device=self.dev)
+        self.ctx_ids = torch.empty(max(self.L, 1) * self.cap, dtype=torch.int32, device=self.dev)
+        self.items2 = torch.empty(2 * self.cap, dtype=torch.int32, device=self.dev)
+        self.err = torch.zeros(1, dtype=torch.int32, device=self.dev)
+
+    def seq_step(self, user, entry, loss_slot, seed, offset, neg=None):
+        """One step on the triples (user[t], entry[t], a sampled negative): user (B,) int32, entry (B,) int64 positions
+        in the CSR's id array.  The negative is trs_sample_neg's draw (uniform, never the row's positive) under (seed,
+        offset + t) unless `neg` (B,) int32 is given.  loss_slot: 1-element fp32 view that receives the SUM of the row
+        losses (the caller divides by B)."""
+        B, D, L = user.shape[0], self.D, self.L
+        if B > self.cap:
+            raise ValueError(f"batch of {B} rows above the trainer's capacity {self.cap}")
+        pos = self.seq[1][entry]
+        if neg is None:
+            neg = ops.sample_neg(pos, self.n_items, seed, offset)
+        gr = self.grad_rows[:(3 + L) * B * D].view(3 + L, B, D)
+        gl = self.grad_lin[:3 * B].view(3, B)
+        cid = self.ctx_ids[:L * B].view(L, B)
+        ops.seq_fwd_bwd(self.net.tables(), self.ctx, self.seq, user, entry, neg, self.weights, self.loss_id, loss_slot,
+                        None, gr, gl, cid, self.err)
+        items = self.items2[:2 * B]
+        items[:B], items[B:] = pos, neg
+        ops.rows_scatter_add(self.user, user, gr[0], -self.lr, ld=D)
+        ops.rows_scatter_add(self.item, items, gr[1:3].view(2 * B, D), -self.lr, ld=D)
+        ops.rows_scatter_add(self.item_lin, items, gl[1:3].view(2 * B, 1), -self.lr, ld=1)
+        if L:
+            ops.rows_scatter_add(self.ctx, cid.view(-1), gr[3:].view(L * B, D), -self.lr, ld=D)
+
+    def check_errors(self):
+        from .collaborative._scorer import check_err_flag
+        check_err_flag(self.err, "fit_sequence")

@@ -118,6 +118,37 @@ def _check_l2(l2, net_type):
     return lam
 
 
+def ordered_sequences(users, items, rows, n_users, timestamps=None):
+    """The ordered per-user CSR of a set of interactions (fit_sequence): users / items (n,) dense ids, rows (n,) the
+    distinct input position of each interaction, timestamps None or one value per INPUT row (indexed by `rows`).
+    Returns (offsets int64 (n_users + 1,), item ids int32 (n,)): user u's items in ascending (timestamp, input
+    position), repeated items kept.  Runs where the tensors live (three stable sorts)."""
+    users = users.to(torch.int64)
+    order = torch.argsort(rows, stable=True)
+    if timestamps is not None:
+        ts = timestamps[rows]
+        order = order[torch.argsort(ts[order], stable=True)]
+    order = order[torch.argsort(users[order], stable=True)]
+    off = torch.zeros(int(n_users) + 1, dtype=torch.int64, device=users.device)
+    off[1:] = torch.cumsum(torch.bincount(users, minlength=int(n_users)), 0)
+    return off, items[order].to(torch.int32).contiguous()
+
+
+def sequence_entries(off, holdout_last):
+    """The positions of an ordered CSR that fit_sequence trains on: all of them, or with holdout_last all but the last
+    of every row with at least two.  Returns (entries int64, held-out users int64, held-out positions int64)."""
+    n = int(off[-1])
+    entries = torch.arange(n, dtype=torch.int64, device=off.device)
+    if not holdout_last:
+        return entries, entries[:0], entries[:0]
+    has = (off[1:] - off[:-1]) >= 2
+    held_users = torch.nonzero(has).reshape(-1)
+    held_pos = off[1:][has] - 1
+    keep = torch.ones(n, dtype=torch.bool, device=off.device)
+    keep[held_pos] = False
+    return entries[keep], held_users, held_pos
+
+
 # What fit() trains on, as its validation chose it: kind 'pair' (hinge / bpr on one negative) | 'softmax' (in-batch) |
 # 'multineg' (K sampled negatives) | 'warp'; loss_id the pair loss (_lib.LOSS_ID) of 'pair' and of 'multineg' (there
 # also _lib.LOSS_SAMPLED_SOFTMAX); logq the (n_items,) device table or None; rank_weight 'log' | 'harmonic'
@@ -1424,6 +1455,323 @@ class TorchRecSys(torch.nn.Module):
         r = torch.from_numpy(rank)
         ids = self._original_ids(ids.cpu()[r], getattr(self.data_processor, "item_index", None))
         return (ids, scores.cpu()[r]) if return_scores else ids
+
+    # ------------------------------------------------------------------------------------------------ sequence model
+    _SEQ_UNFITTED = "call fit_sequence() first"
+
+    def _check_sequence_model(self, what):
+        """What every sequence call needs of the model (before any device work): a Linear net without metadata, one
+        process, a row width the staging kernels take."""
+        if self.net_type != 'linear' or self.use_metadata:
+            kind = f"net_type={self.net_type!r}" + (" with metadata columns" if self.use_metadata else "")
+            raise ValueError(f"{what} needs net_type='linear' without metadata columns, not {kind}: the sequence model "
+                             "adds a context table to the Linear scorer's rows ('fm', 'mlp', 'ease' and metadata are "
+                             "out of scope)")
+        if tdist.world_info()[1] > 1:
+            raise NotImplementedError(f"{what} runs in a single process: under torch.distributed (world > 1) a rank "
+                                      "holds a shard of the interactions, not whole user sequences")
+        D = int(self.n_factors)
+        if D < 1 or D > 1024 or (D % 4 != 0 and D > 256):
+            raise ValueError(f"{what}: n_factors={D} is not a row width the kernels take (1..1024; not a multiple of 4 "
+                             "only up to 256)")
+
+    def _sequence_buffers(self, what):
+        C, w = getattr(self.net, "seq_context", None), getattr(self.net, "seq_weights", None)
+        if C is None or w is None:
+            raise RuntimeError(f"{what}: {self._SEQ_UNFITTED}")
+        return C, w
+
+    def _check_sequence_topk(self, what, top_k):
+        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)):
+            raise ValueError(f"{what}: top_k must be an integer, got {top_k!r}")
+        if int(top_k) > ops._lib.RETRIEVE_KMAX:
+            raise ValueError(f"{what} takes top_k <= {ops._lib.RETRIEVE_KMAX} (TRS_RETRIEVE_KMAX), got {top_k}")
+        if self.n_factors > ops._lib.RETRIEVE_DMAX:
+            raise ValueError(f"{what} takes n_factors <= {ops._lib.RETRIEVE_DMAX} (TRS_RETRIEVE_DMAX), got "
+                             f"{self.n_factors}")
+
+    def _check_timestamps(self, what, timestamps):
+        """timestamps as a 1-D CPU tensor with one finite number per INPUT row (None stays None); ValueError otherwise."""
+        if timestamps is None:
+            return None
+        timestamps = torch.as_tensor(np.asarray(timestamps.cpu() if hasattr(timestamps, "cpu") else timestamps))
+        n_in = self.data_processor.n_input_rows
+        if timestamps.dim() != 1 or timestamps.numel() != n_in or timestamps.dtype == torch.bool:
+            raise ValueError(f"{what}: timestamps must hold one number per input row ({n_in}), got shape "
+                             f"{tuple(timestamps.shape)}")
+        if timestamps.is_floating_point() and not bool(torch.isfinite(timestamps).all()):
+            raise ValueError(f"{what}: timestamps must be finite")
+        return timestamps
+
+    def _sequences(self, timestamps=None):
+        """The ordered per-user CSR of the train split on the device.  Built on first use, by input position or by the
+        timestamps given then; built again whenever timestamps are given.  The order is the MODEL OBJECT's, not the
+        tables': it is not part of state_dict() (set_sequence_order())."""
+        if 'sequences' not in self._dev_cache or timestamps is not None:
+            st = self._device_stream('train')
+            dev = st['user'].device
+            rows = self.data_processor.train_rows().to(dev)
+            ts = None if timestamps is None else timestamps.to(dev)
+            self._dev_cache['sequences'] = ordered_sequences(st['user'], st['pos'], rows, self.n_users, ts)
+        return self._dev_cache['sequences']
+
+    @_host_side
+    def set_sequence_order(self, timestamps=None):
+        """Fixes the order of every user's train sequence for the sequence calls: by `timestamps` (one number per INPUT
+        row, ties by input position), or with None by input position.  fit_sequence(timestamps=...) does the same.  The
+        order stays with this model object until it is set again: a later fit_sequence() without timestamps keeps
+        training on it, and recommend_next() / evaluate_next() read each user's last items from it.  It is NOT part of
+        state_dict(): a model restored from one orders by input position until this is called with the timestamps the
+        context table was fitted on.  A held-out set of an earlier fit_sequence(holdout_last=True) is dropped (its
+        positions belong to the old order)."""
+        what = "set_sequence_order"
+        self._check_sequence_model(what)
+        timestamps = self._check_timestamps(what, timestamps)
+        _device()
+        self._dev_cache.pop('sequences', None)
+        self._seq_holdout = None
+        self._sequences(timestamps)
+
+    @_host_side
+    def fit_sequence(self, epochs: int = 10, lr: float = 0.05, batch_size: int = 4096, context: int = 4,
+                     decay: float = 0.7, loss: str = 'bpr', seed: int = 0, timestamps=None, holdout_last: bool = False,
+                     return_loss: bool = False):
+        """Next-item training over each user's ORDERED train sequence: a factorised Markov model over the last `context`
+        items (FPMC for context = 1, the Fossil family beyond) on the Linear scorer's tables U, V, b plus one context
+        table C (n_items, n_factors).  For position k of user u's sequence s_u,
+            q = U[u] + sum_{l < min(context, k)} w_l C[s_u[k-1-l]],    z(i) = <q, V[i]> + b[i],
+        w_l = decay^l / sum_{j < context} decay^j (l = 0 the most recent item), and the row loss is 'bpr' or 'hinge' on
+        (z(s_u[k]), z(a sampled negative)); the exact rule is in include/trs.h "sequence model".  C starts as zeros: a
+        fresh model is exactly the Linear model it was.
+        Order: the input row position, ascending; `timestamps` (one number per INPUT row, train and test rows alike, of
+        either front door) overrides it, ties broken by row position.  Repeated items stay in the sequences.  The order
+        stays with the model object: a later call WITHOUT timestamps keeps the order of the last call that gave some,
+        and it is not part of state_dict() (set_sequence_order() sets it on a restored model, or resets it).
+        holdout_last keeps every user's last train interaction out of training and remembers it for evaluate_next();
+        users with fewer than two interactions hold out nothing.
+        Every epoch visits every remaining position once, in a permutation seeded by (seed, epoch); one step = a
+        negative per row (uniform, never the row's positive), one staging launch (trs_seq_fwd_bwd) and plain SGD at
+        `lr` on the rows it references.  No optimiser object, no host sync inside an epoch.
+        C and the weights become buffers of the net (state_dict() carries them).  A second call continues from the
+        current tables; another `context` or `decay` then raises.  U, V, b are written in place: recommend(),
+        similar_items(), evaluate() and the rest keep answering from the context-free Linear model those tables are.
+        Returns None, or with return_loss the (epochs,) float64 mean row loss of every epoch.
+        Before any device work: ValueError for another net_type, metadata, or a bad argument; NotImplementedError under
+        torch.distributed with more than one rank."""
+        what = "fit_sequence"
+        self._check_sequence_model(what)
+
+        def integer(v, name, lo, hi=None):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v > hi):
+                raise ValueError(f"{what}: {name} must be an integer in {lo}..{'' if hi is None else hi}, got {v!r}")
+            return int(v)
+
+        def positive(v, name):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or \
+                    not (math.isfinite(v) and v > 0):
+                raise ValueError(f"{what}: {name} must be a finite number > 0, got {v!r}")
+            return float(v)
+
+        epochs, batch_size = integer(epochs, "epochs", 1), integer(batch_size, "batch_size", 1)
+        L = integer(context, "context", 0, ops._lib.SEQ_LMAX)
+        seed = integer(seed, "seed", 0)
+        lr, decay = positive(lr, "lr"), positive(decay, "decay")
+        if loss not in ('bpr', 'hinge'):
+            raise ValueError(f"{what}: loss must be 'bpr' or 'hinge', got {loss!r}")
+        if self.n_items < 2:
+            raise ValueError(f"{what}: sampling a negative needs n_items >= 2")
+        timestamps = self._check_timestamps(what, timestamps)
+        weights = ops.seq_weights(L, decay)
+        C, w = getattr(self.net, "seq_context", None), getattr(self.net, "seq_weights", None)
+        if C is not None and w is not None and not (w.numel() == L and torch.equal(w.cpu(), weights)):
+            raise ValueError(f"{what}: the model already has a context table fitted with other slot weights "
+                             f"({w.cpu().tolist()}); context={L}, decay={decay} would give {weights.tolist()}")
+        dev = _device()
+        self.net = self.net.train()
+        off, ids = self._sequences(timestamps)
+        if C is None or w is None:
+            self.net.seq_context = torch.zeros((self.n_items, self.n_factors), dtype=torch.float32, device=dev)
+            self.net.seq_weights = weights.to(dev)
+        C, w = self.net.seq_context, self.net.seq_weights
+        entries, held_users, held_pos = sequence_entries(off, holdout_last)
+        self._seq_holdout = (held_users, held_pos) if holdout_last else None
+        n = int(entries.numel())
+        loss_sums = torch.zeros(epochs, dtype=torch.float32, device=dev)
+        if n:
+            from .engine import SequenceTrainer
+            B = min(batch_size, n)
+            trainer = SequenceTrainer(self.net, C, w, (off, ids), B, lr, ops._lib.LOSS_ID[loss])
+            user_of = torch.repeat_interleave(torch.arange(self.n_users, dtype=torch.int32, device=dev),
+                                              off[1:] - off[:-1])
+            done = getattr(self, "_seq_epochs_done", 0)
+            with torch.no_grad():
+                for ep in range(epochs):
+                    g = torch.Generator(device=dev)
+                    g.manual_seed(_mix64(seed, done + ep) & (2 ** 63 - 1))
+                    ent = entries[torch.randperm(n, device=dev, generator=g)]
+                    usr = user_of[ent]
+                    sample_seed = _mix64(seed ^ 0x5EC0DE, done + ep)
+                    for s in range(0, n, B):
+                        trainer.seq_step(usr[s:s + B], ent[s:s + B], loss_sums[ep:ep + 1], sample_seed, s)
+                    avg = float(loss_sums[ep].item()) / n  # the epoch's one read
+                    print(f'|--- Epoch {ep+1}/{epochs} --- Training Loss: {avg:.4f}')
+            self._seq_epochs_done = done + epochs
+            trainer.check_errors()
+        return (loss_sums.cpu().to(torch.float64) / max(n, 1)) if return_loss else None
+
+    @staticmethod
+    def _gather_csr(off, items, rows, drop_last=0):
+        """Rows `rows` (int64, same device) of a CSR as a CSR of their own, each without its last drop_last entries."""
+        cnt = (off[rows + 1] - off[rows] - int(drop_last)).clamp_(min=0)
+        noff = torch.zeros(rows.numel() + 1, dtype=torch.int64, device=off.device)
+        noff[1:] = torch.cumsum(cnt, 0)
+        within = torch.arange(int(noff[-1]), device=off.device) - torch.repeat_interleave(noff[:-1], cnt)
+        return noff, items[torch.repeat_interleave(off[rows], cnt) + within].contiguous()
+
+    @staticmethod
+    def _distinct_csr(off, items, n_items):
+        """The sorted, distinct items of every row of a CSR (what the retrieval kernels take as a seen list)."""
+        n = off.numel() - 1
+        row = torch.repeat_interleave(torch.arange(n, device=off.device), off[1:] - off[:-1])
+        key = torch.unique(row * int(n_items) + items.to(torch.int64))
+        r = torch.div(key, int(n_items), rounding_mode="floor")
+        noff = torch.zeros(n + 1, dtype=torch.int64, device=off.device)
+        noff[1:] = torch.cumsum(torch.bincount(r, minlength=n), 0)
+        return noff, (key - r * int(n_items)).to(torch.int32).contiguous()
+
+    def _sequence_query_tables(self, rows):
+        """A temporary table set whose user side is the composed query rows (n, D): the retrieval kernels read nothing
+        else of it but the item side, which is the model's."""
+        ps = self.net.table_params()
+        zero = torch.zeros((rows.shape[0], 1), dtype=torch.float32, device=rows.device)
+        return ops.make_tables(rows, ps[1].data, zero, ps[3].data)
+
+    def _sequence_topk(self, rows, k, seen, return_scores, order=None):
+        dev = rows.device
+        T, keep = self._sequence_query_tables(rows)
+        fold = ops.item_fold("linear", T, self.n_items, self.n_factors, dev, None)
+        q = torch.arange(rows.shape[0], dtype=torch.int64, device=dev)
+        ids, scores, _ = self._chunked(lambda us: ops.retrieve_topk("linear", T, fold, us, k, seen), q)
+        ids, scores = ids.cpu(), scores.cpu()
+        if order is not None:
+            ids, scores = ids[order], scores[order]
+        ids = self._original_ids(ids, getattr(self.data_processor, "item_index", None))
+        return (ids, scores) if return_scores else ids
+
+    @_host_side
+    def recommend_next(self, user_ids, top_k: int = 10, exclude_seen: bool = True, return_scores: bool = False):
+        """recommend() under the sequence model: each user's query row is U[u] plus the weighted context rows of the
+        LAST items of the user's full train sequence (trs_seq_user_rows), ranked against every item by <q, V[i]> + b[i]
+        with recommend()'s fused top-k.  Conventions as recommend(): original ids in and out, (n, k) int64 CPU tensor,
+        k = min(top_k, n_items), with return_scores also the (n, k) fp32 scores; exclude_seen drops the user's train
+        items; id -1 / score -inf beyond the candidates; ties by ascending item row.  top_k <= TRS_RETRIEVE_KMAX and
+        n_factors <= TRS_RETRIEVE_DMAX (ValueError); RuntimeError before fit_sequence().  A user without train rows is
+        ranked by U[u] alone.  The sequences are in the model object's order (set_sequence_order()): after
+        load_state_dict() that is the input position until the timestamps are given again."""
+        what = "recommend_next"
+        self._check_sequence_model(what)
+        self._check_sequence_topk(what, top_k)
+        C, w = self._sequence_buffers(what)
+        ulist = user_ids.tolist() if hasattr(user_ids, "tolist") else list(user_ids)
+        k = min(int(top_k), self.n_items)
+        if k <= 0 or not ulist:
+            return self._empty_topk(len(ulist), k, return_scores)
+        users = self._dense_users(ulist).to(_device())
+        self.net = self.net.eval()
+        off, ids = self._sequences()
+        err = torch.zeros(1, dtype=torch.int32, device=users.device)
+        rows = ops.seq_user_rows(self.net.tables(), C, self._gather_csr(off, ids, users), users, w, err_flag=err)
+        seen = self._gather_csr(*self._seen_csr(), users) if exclude_seen else None
+        if seen is not None and seen[1].numel() == 0:
+            seen = None
+        out = self._sequence_topk(rows, k, seen, return_scores)
+        check_err_flag(err, what)
+        return out
+
+    @_host_side
+    def recommend_for_sequences(self, sequences, top_k: int = 10, exclude_seen: bool = True,
+                                return_scores: bool = False):
+        """recommend_next() for anonymous sessions: `sequences` is a sequence of sequences / 1-D arrays of original item
+        ids, oldest first (an unknown id raises IndexError).  The query row is the weighted context rows of the session's
+        last items alone (no user row); nothing is fitted.  An empty session ranks by b.  exclude_seen drops the
+        session's own items.  Output and limits as recommend_next()."""
+        what = "recommend_for_sequences"
+        self._check_sequence_model(what)
+        self._check_sequence_topk(what, top_k)
+        C, w = self._sequence_buffers(what)
+        hs = [np.asarray(h.tolist() if hasattr(h, "tolist") else list(h), dtype=np.int64).reshape(-1) for h in sequences]
+        n = len(hs)
+        lens = np.array([h.size for h in hs], dtype=np.int64)
+        flat = np.concatenate(hs) if n and lens.sum() else np.zeros(0, dtype=np.int64)
+        dense = self._dense_rows(flat, getattr(self.data_processor, "item_index", None), self.n_items, 'item')
+        k = min(int(top_k), self.n_items)
+        if k <= 0 or n == 0:
+            return self._empty_topk(n, k, return_scores)
+        dev = _device()
+        self.net = self.net.eval()
+        off = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)).to(dev)
+        ids = dense.to(torch.int32).to(dev)
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        rows = ops.seq_user_rows(self.net.tables(), C, (off, ids), None, w, err_flag=err)
+        seen = self._distinct_csr(off, ids, self.n_items) if exclude_seen and ids.numel() else None
+        out = self._sequence_topk(rows, k, seen, return_scores)
+        check_err_flag(err, what)
+        return out
+
+    @_host_side
+    def evaluate_next(self, k: int = 10, users=None):
+        """Next-item metrics after fit_sequence(holdout_last=True): for every user with a held-out last interaction
+        (or those of `users`, original ids), the exact rank (trs_item_ranks; rank_items()'s definition) of the held-out
+        item among all items but the user's EARLIER train items, given the context that precedes it.  Returns
+        {'hit_rate@k', 'ndcg@k', 'mrr@k'} and the same three for the context-free row U[u] alone under
+        '..._no_context', plus 'n_users'; hit = rank < k, ndcg = 1 / log2(rank + 2) and mrr = 1 / (rank + 1) where it
+        hits, 0 otherwise, averaged in float64 over the evaluated users."""
+        what = "evaluate_next"
+        self._check_sequence_model(what)
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+            raise ValueError(f"{what}: k must be an integer >= 1, got {k!r}")
+        if self.n_factors > ops._lib.RETRIEVE_DMAX:
+            raise ValueError(f"{what} takes n_factors <= {ops._lib.RETRIEVE_DMAX} (TRS_RETRIEVE_DMAX), got "
+                             f"{self.n_factors}")
+        C, w = self._sequence_buffers(what)
+        held = getattr(self, "_seq_holdout", None)
+        if held is None:
+            raise RuntimeError(f"{what}: nothing is held out; call fit_sequence(holdout_last=True) first")
+        dense = None if users is None else torch.unique(self._dense_users(users))
+        k = int(k)
+        dev = _device()
+        self.net = self.net.eval()
+        off, ids = self._sequences()
+        hu, hp = held
+        if dense is not None:
+            pick = torch.isin(hu, dense.to(dev))
+            hu, hp = hu[pick], hp[pick]
+        names = [f"{m}@{k}" for m in ("hit_rate", "ndcg", "mrr")]
+        out = {name + sfx: 0.0 for sfx in ("", "_no_context") for name in names}
+        n = int(hu.numel())
+        if n:
+            prefix = self._gather_csr(off, ids, hu, drop_last=1)  # what precedes the held-out item
+            err = torch.zeros(1, dtype=torch.int32, device=dev)
+            rows = ops.seq_user_rows(self.net.tables(), C, prefix, hu, w, err_flag=err)
+            seen = self._distinct_csr(*prefix, self.n_items)
+            targets = (torch.arange(n + 1, dtype=torch.int64, device=dev), ids[hp].contiguous())
+            q = torch.arange(n, dtype=torch.int64, device=dev)
+            for sfx, qrows in (("", rows), ("_no_context", self.net.table_params()[0].data[hu].contiguous())):
+                T, keep = self._sequence_query_tables(qrows)
+                fold = ops.item_fold("linear", T, self.n_items, self.n_factors, dev, None)
+                ranks = torch.cat([ops.item_ranks("linear", T, fold, q[s:s + self.RECOMMEND_CHUNK],
+                                                  (targets[0][s:s + self.RECOMMEND_CHUNK + 1] - s,
+                                                   targets[1][s:s + self.RECOMMEND_CHUNK]), seen)[0]
+                                   for s in range(0, n, self.RECOMMEND_CHUNK)]).cpu().numpy().astype(np.float64)
+                hit = ranks < k
+                out[names[0] + sfx] = float(hit.mean())
+                out[names[1] + sfx] = float(np.where(hit, 1.0 / np.log2(ranks + 2.0), 0.0).mean())
+                out[names[2] + sfx] = float(np.where(hit, 1.0 / (ranks + 1.0), 0.0).mean())
+            check_err_flag(err, what)
+        for name, value in out.items():
+            print(f'|--- Testing {name}: {value:.4f}')
+        out['n_users'] = n
+        return out
 
     # ------------------------------------------------------------------------------------------------ item fold-in
     def _new_item_metadata(self, what, metadata, n):

@@ -1012,6 +1012,95 @@ def ease_scores(B, hist_csr, rows, err_flag=None):
     return out
 
 
+def seq_weights(context, decay, device=None):
+    """The fixed slot weights of the sequence model, w_l = decay^l / sum_{j < L} decay^j (float64 arithmetic, rounded to
+    fp32 once): an (L,) fp32 tensor, slot 0 the most recent item."""
+    w = [float(decay) ** l for l in range(int(context))]
+    return torch.tensor([x / sum(w) for x in w], dtype=torch.float32, device=device)
+
+
+def _seq_csr(seq):
+    """(trs_csr, keepalive) of an ordered sequence CSR (offsets int64 (n + 1,), item ids int32 in order; rows are not
+    sorted).  An empty id tensor (every row empty: nothing is ever read) is replaced by a one-element buffer: the entry
+    points refuse NULL item ids, since they cannot see from the host that every row is empty."""
+    off, items = seq
+    _dev(off, "sequence offsets", torch.int64)
+    _dev(items, "sequence item ids", torch.int32)
+    if items.numel() == 0:
+        items = torch.zeros(1, dtype=torch.int32, device=off.device)
+    c = _lib.TrsCsr()
+    c.off, c.items, c.n_rows = ptr(off), ptr(items), off.numel() - 1
+    return c, items
+
+
+def seq_fwd_bwd(T, ctx, seq, user, entry, neg, weights, loss, loss_sum, auc_count=None, grad_rows=None, grad_lin=None,
+                ctx_ids=None, err_flag=None, forward_only=False, inv_B=None):
+    """One pass of the sequence model over B triples (trs_seq_fwd_bwd; the model is in include/trs.h "sequence model").
+    T: the Linear tables (no metadata); ctx (n_items, D) fp32; seq = (offsets int64 (n_users + 1,), item ids int32 in
+    order); user (B,) int32, entry (B,) int64 positions in the id array, neg (B,) int32; weights (L,) fp32; loss a
+    _lib.LOSS_ID.  loss_sum / auc_count are accumulated in place.  Returns (grad_rows (3 + L, B, D), grad_lin (3, B),
+    ctx_ids (L, B) int32), field-major: user, positive, negative, then the context slots; (None, None, None) with
+    forward_only."""
+    for t, name, dtype in ((ctx, "context table", torch.float32), (user, "user ids", torch.int32),
+                           (entry, "entries", torch.int64), (neg, "negative ids", torch.int32),
+                           (weights, "context weights", torch.float32), (loss_sum, "loss_sum", torch.float32),
+                           (auc_count, "auc_count", torch.int32), (grad_rows, "grad_rows", torch.float32),
+                           (grad_lin, "grad_lin", torch.float32), (ctx_ids, "ctx_ids", torch.int32),
+                           (err_flag, "err_flag", torch.int32)):
+        _dev(t, name, dtype)
+    B, D, L = user.shape[0], T.D, int(weights.numel())
+    if entry.shape[0] != B or neg.shape[0] != B:
+        raise ValueError("user / entry / neg must have the same length")
+    if ctx.dim() != 2 or ctx.shape[0] != T.n_items or ctx.shape[1] != D:
+        raise ValueError(f"the context table must be (n_items, D) = ({T.n_items}, {D}), got {tuple(ctx.shape)}")
+    if forward_only:
+        grad_rows = grad_lin = ctx_ids = None
+    else:
+        dev = user.device
+        if grad_rows is None:
+            grad_rows = torch.empty((3 + L, B, D), dtype=torch.float32, device=dev)
+        if grad_lin is None:
+            grad_lin = torch.empty((3, B), dtype=torch.float32, device=dev)
+        if ctx_ids is None:
+            ctx_ids = torch.empty((L, B), dtype=torch.int32, device=dev)
+        if grad_rows.numel() < (3 + L) * B * D or grad_lin.numel() < 3 * B or ctx_ids.numel() < L * B:
+            raise ValueError("staging buffers are smaller than (3 + L, B, D) / (3, B) / (L, B)")
+    if inv_B is None:
+        inv_B = 1.0 / B if B > 0 else 0.0
+    cs, keep = _seq_csr(seq)
+    check(_lib.load().trs_seq_fwd_bwd(C.byref(T), ptr(ctx), C.byref(cs), ptr(user), ptr(entry), ptr(neg), B, L,
+                                      ptr(weights) if L else None, int(loss), float(inv_B), ptr(loss_sum),
+                                      ptr(auc_count), ptr(grad_rows), ptr(grad_lin), ptr(ctx_ids) if L else None,
+                                      ptr(err_flag), _stream()), "trs_seq_fwd_bwd")
+    return grad_rows, grad_lin, ctx_ids
+
+
+def seq_user_rows(T, ctx, seq, users, weights, ld=None, out=None, err_flag=None):
+    """Query rows of the sequence model (trs_seq_user_rows): out[r, :D] = (U[users[r]], or 0 for users[r] < 0 or users
+    None) + sum_l w_l C[row r's item len-1-l].  seq = (offsets int64 (n + 1,), item ids int32, oldest first), one row
+    per output row; users (n,) int64 or None.  Returns the (n, ld) fp32 rows (ld defaults to D; columns beyond D are 0
+    in a buffer made here)."""
+    for t, name, dtype in ((ctx, "context table", torch.float32), (users, "users", torch.int64),
+                           (weights, "context weights", torch.float32), (out, "out", torch.float32),
+                           (err_flag, "err_flag", torch.int32)):
+        _dev(t, name, dtype)
+    n, D, L = seq[0].numel() - 1, T.D, int(weights.numel())
+    if users is not None and users.numel() != n:
+        raise ValueError(f"{users.numel()} users for {n} sequences")
+    if ctx.dim() != 2 or ctx.shape[0] != T.n_items or ctx.shape[1] != D:
+        raise ValueError(f"the context table must be (n_items, D) = ({T.n_items}, {D}), got {tuple(ctx.shape)}")
+    ld = D if ld is None else int(ld)
+    if out is None:
+        out = torch.zeros((n, ld), dtype=torch.float32, device=ctx.device)
+    elif out.dim() != 2 or out.shape[0] != n or out.stride(0) != ld:
+        raise ValueError(f"out must be (n, ld) = ({n}, {ld})")
+    cs, keep = _seq_csr(seq)
+    check(_lib.load().trs_seq_user_rows(C.byref(T), ptr(ctx), C.byref(cs), ptr(users), n, L,
+                                        ptr(weights) if L else None, ptr(out), ld, ptr(err_flag), _stream()),
+          "trs_seq_user_rows")
+    return out
+
+
 def item_ranks(net, T, fold, users, targets_csr, seen=None, want_values=False):
     """Exact ranks of each query's target items over the catalogue (trs_item_ranks; the definition is in
     include/trs.h "exact ranks").  users: dense int64 GPU tensor; targets_csr: (offsets int64 (n + 1,), items int32) GPU
