@@ -102,7 +102,8 @@ const char* trs_last_error(void);
  *      trs_score_warp_fwd_bwd, TRS_LOSS_WARP, trs_stage_add_l2, trs_neighbour_fold, trs_neighbours_topk,
  *      trs_fold_in_users, trs_item_ranks, trs_item_ranks_workspace_bytes, trs_mmr_rerank, trs_list_ild,
  *      trs_fold_in_items, trs_als_gram, trs_als_gram_workspace_bytes, trs_als_solve, trs_ease_gram, trs_ease_invert,
- *      trs_ease_invert_workspace_bytes, trs_ease_weights, trs_ease_scores, trs_seq_fwd_bwd, trs_seq_user_rows.) */
+ *      trs_ease_invert_workspace_bytes, trs_ease_weights, trs_ease_scores, trs_seq_fwd_bwd, trs_seq_user_rows,
+ *      trs_lgcn_propagate, trs_lgcn_adam.) */
 #define TRS_ABI_VERSION 6
 #define TRS_SYNC_WORDS 288
 #define TRS_SYNC_REBASE 0x40000000u /* arrivals after which trs_train_steps_sgd zeroes sync_dev and its host count */
@@ -866,6 +867,49 @@ int trs_als_gram(const float* rows_dev, int64_t n, int32_t D, int64_t ld, float*
 int trs_als_solve(const float* other_rows_dev, int64_t n_other, int32_t D, const float* G_dev, const trs_csr* nbr,
                   float lambda, float alpha, int32_t cg_steps, float* rows_inout_dev, int64_t n_rows,
                   int32_t* err_flag_dev, void* stream);
+
+/* ------------------------------------------------------------------- LightGCN (fit_lightgcn) */
+/* LightGCN (He et al., SIGIR 2020) on the train split's distinct (user, item) pairs: with A^ the symmetric normalised
+ * bipartite adjacency, A^[u][i] = dinv_u * dinv_i on a pair (dinv = 1 / sqrt(degree), 0 for degree 0), and E0 = [U0; V0]
+ * the base tables,  Final = 1/(K+1) * sum_{k=0..K} A^^k E0,  score = <Final_u, Final_i>.  The sum is evaluated in Horner
+ * form, F_K = E0, F_k = E0 + A^ F_{k+1}, Final = 1/(K+1) * F_0; the gradient of a loss with G = dL/dFinal is the same
+ * recurrence on G (A^ is symmetric).  One Horner step is two calls of trs_lgcn_propagate: user rows from item rows
+ * through the by-user CSR, item rows from user rows through the by-item CSR.  Added without touching an existing
+ * signature or struct.
+ *
+ * trs_lgcn_propagate: in_rows (n_in, D, row stride D); nbr the CSR of the n_out rows to write (off int64 (n_out + 1),
+ *   items int32: rows of in_rows); dinv_out (n_out), dinv_in (n_in); add_rows (n_out, D, row stride D) or NULL; out_rows
+ *   (n_out, D, row stride D).  One launch.  For row r with list N = items[off[r] .. off[r+1]) and column d:
+ *     segments   N is cut into segments of TRS_LGCN_SEG neighbours in CSR order; the last may be shorter.
+ *     partial_j  = sum over segment j's neighbours c, in CSR order, from 0, of  dinv_in[c] * in[c][d]
+ *     s          = the sum of the partials in ascending segment order, from 0 (a list of at most TRS_LGCN_SEG
+ *                  neighbours is therefore one straight sum; an empty list has s = 0)
+ *     p          = dinv_out[r] * s
+ *     v          = scale * (add_rows ? add_rows[r][d] + p : p)
+ *     out[r][d]  = accumulate ? out[r][d] + v : v          (every row is written, also one with an empty list)
+ *   sums       every product and every sum is rounded to fp32 on its own (no fused multiply-add): a float32 loop on the
+ *              host reproduces the rows bit for bit, whatever the launch shape.
+ *   purity     a row's result depends on its own list, its add / out / dinv_out value, the rows it names (with their
+ *              dinv_in) and scale only: not on r, not on the other rows of the call.
+ *   aliasing   out_rows may be add_rows.  out_rows == in_rows is TRS_E_ARG.
+ * A neighbour id outside [0, n_in) is never used as an address (into in_rows or dinv_in): that neighbour is skipped (it
+ * keeps its place in its segment) and bit 0 of *err_flag_dev (may be NULL) is set.
+ * TRS_E_ARG, nothing launched: D outside 1..TRS_RETRIEVE_DMAX; scale not finite; accumulate outside {0, 1}; n_out < 0 or
+ * n_in < 0; nbr NULL or nbr->n_rows != n_out; with n_out > 0 a NULL in_rows / dinv_out / dinv_in / out_rows or CSR array,
+ * or n_in outside 1..2^31-1.  n_out == 0: TRS_OK, nothing launched.
+ *
+ * trs_lgcn_adam: torch.optim.Adam's rule (no amsgrad, no weight decay) on every one of the n elements of a dense table,
+ *   one launch:  m += (1-b1)(g-m);  v = v*b2 + ((1-b2) g) g;  p += (-(lr / (1-b1^t)) m) / (sqrt(v) / sqrt(1-b2^t) + eps),
+ *   t = step_count >= 1.  1 - beta, lr / (1 - b1^t) and sqrt(1 - b2^t) are formed on the host in double from the
+ *   hyper-parameters as written (as trs_rows_apply_sparse_adam forms its constants), then rounded to fp32.
+ *   TRS_E_ARG, nothing launched: n < 0; step_count < 1; lr or eps not finite or < 0; a beta outside [0, 1); with n > 0 a
+ *   NULL array.  n == 0: TRS_OK, nothing launched. */
+#define TRS_LGCN_SEG 512 /* neighbours per segment of trs_lgcn_propagate */
+int trs_lgcn_propagate(const float* in_rows_dev, int64_t n_in, int32_t D, const trs_csr* nbr,
+                       const float* dinv_out_dev, const float* dinv_in_dev, const float* add_rows_dev, float scale,
+                       float* out_rows_dev, int64_t n_out, int32_t accumulate, int32_t* err_flag_dev, void* stream);
+int trs_lgcn_adam(float* param_dev, const float* grad_dev, float* exp_avg_dev, float* exp_avg_sq_dev, int64_t n,
+                  float lr, float beta1, float beta2, float eps, int64_t step_count, void* stream);
 
 /* ------------------------------------------------------------------- EASE (fit_ease) */
 /* Embarrassingly shallow autoencoder (Steck, WWW 2019): an item-item model with a closed form.  Added without touching

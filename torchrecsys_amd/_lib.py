@@ -18,6 +18,8 @@ RETRIEVE_DMAX = 256  # TRS_RETRIEVE_DMAX: largest D of the fused retrieval kerne
 EASE_NB = 64  # TRS_EASE_NB: fp64 matrices of the EASE solver are padded to a multiple of it
 EASE_NMAX = 32768  # TRS_EASE_NMAX: largest catalogue of fit_ease
 SEQ_LMAX = 16  # TRS_SEQ_LMAX: largest context length of the sequence model
+LGCN_SEG = 512  # TRS_LGCN_SEG: neighbours per segment of trs_lgcn_propagate
+LGCN_LAYERS_MAX = 8  # most propagation layers fit_lightgcn takes
 ABI_VERSION = 6  # == TRS_ABI_VERSION of include/trs.h (tests/test_abi.py)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -186,6 +188,8 @@ PROTOTYPES = {
     "trs_als_gram_workspace_bytes": (C.c_int64, [_i64, _i32]),
     "trs_als_gram": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _vp, _vp]),
     "trs_als_solve": (C.c_int, [_vp, _i64, _i32, _vp, C.POINTER(TrsCsr), _f, _f, _i32, _vp, _i64, _vp, _vp]),
+    "trs_lgcn_propagate": (C.c_int, [_vp, _i64, _i32, C.POINTER(TrsCsr), _vp, _vp, _vp, _f, _vp, _i64, _i32, _vp, _vp]),
+    "trs_lgcn_adam": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _i64, _vp]),
     "trs_ease_gram": (C.c_int, [C.POINTER(TrsCsr), _i64, _i64, C.c_double, _vp, _vp, _vp]),
     "trs_ease_invert_workspace_bytes": (C.c_int64, [_i64]),
     "trs_ease_invert": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),

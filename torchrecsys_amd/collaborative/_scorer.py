@@ -30,6 +30,32 @@ class SparseScorer(torch.nn.Module):
     META_LIN_NAME = None            # ModuleList attribute of the 1-wide metadata tables (FM) or None
     META_NAME = "metadata"
 
+    def __init__(self):
+        super().__init__()
+        # LightGCN (TorchRecSys.fit_lightgcn): the base tables the propagated user / item tables are the forward of, and
+        # the layer count as a 1-element int64 tensor; persistent buffers once fitted so that state_dict() carries
+        # them; None (and absent from it) before
+        self.register_buffer("lgcn_user_base", None)
+        self.register_buffer("lgcn_item_base", None)
+        self.register_buffer("lgcn_layers", None)
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
+                              error_msgs):
+        names = ("lgcn_user_base", "lgcn_item_base", "lgcn_layers")
+        got = [state_dict.get(prefix + n) for n in names]
+        if all(t is not None for t in got) and self.lgcn_user_base is None:  # a fresh model takes the fitted one's
+            want = (tuple(self.user.weight.shape), tuple(self.item.weight.shape), (1,))
+            for n, t, shape in zip(names, got, want):
+                if tuple(t.shape) != shape:
+                    error_msgs.append(f"size mismatch for {prefix}{n}: {tuple(t.shape)} for {shape}")
+                    return
+            dev = self.item.weight.device
+            self.lgcn_user_base = torch.empty(want[0], dtype=torch.float32, device=dev)
+            self.lgcn_item_base = torch.empty(want[1], dtype=torch.float32, device=dev)
+            self.lgcn_layers = torch.empty(1, dtype=torch.int64, device=dev)
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
+                                      error_msgs)
+
     # -------------------------------------------------------------------------------------------- structs
     def table_params(self):
         """[user, item, user_lin, item_lin, meta_0.., meta_lin_0..] weights, the order used by the autograd bridge."""

@@ -730,3 +730,131 @@ class SequenceTrainer:
     def check_errors(self):
         from .collaborative._scorer import check_err_flag
         check_err_flag(self.err, "fit_sequence")
+
+
+class LightGCNTrainer:
+    """Training steps of LightGCN (include/trs.h "LightGCN") on a Linear / FM net without metadata.
+    base = (U0, V0) are the trained tables; the net's own user / item tables always hold Final = the Horner forward of
+    the base tables, and its 1-wide tables stay zero.  graph = (by_user CSR, by_item CSR) of the distinct train pairs on
+    the device.  One step = forward (2 * layers launches of trs_lgcn_propagate), trs_score_fwd_bwd as the Linear scorer
+    on the propagated tables, the row gradients scatter-added into a zeroed dense G, the backward (the same recurrence
+    on G), and the update: plain SGD leaves the last backward launches to add -lr * alpha * H_0 straight into the base
+    tables, Adam lets them write the gradient and runs trs_lgcn_adam on each table.  No optimiser object and no host
+    sync: the loss is accumulated where the caller says.
+
+    Besides the base tables the trainer holds G (both sides), an item-side and two user-side work tables — 4 buffers of
+    the size of both tables together at most (BUFFERS['sgd']) — and for Adam the two moments of each table on top
+    (BUFFERS['adam'] = 6)."""
+
+    BUFFERS = {'sgd': 4, 'adam': 6}  # table-pair-sized buffers a fit needs, the base tables included
+    BETAS, EPS = (0.9, 0.999), 1e-8  # torch.optim.Adam's defaults
+
+    def __init__(self, net, base, graph, layers, batch_capacity, lr, loss_id, optimizer='adam', l2=0.0):
+        ps = net.table_params()
+        self.net = net
+        self.user, self.item, self.user_lin, self.item_lin = (p.data for p in ps[:4])
+        self.base_user, self.base_item = base
+        self.by_user, self.by_item = graph
+        self.dev, self.D = self.user.device, self.user.shape[1]
+        self.K, self.cap, self.lr, self.loss_id = int(layers), int(batch_capacity), float(lr), int(loss_id)
+        self.optimizer, self.l2 = optimizer, float(l2)
+        self.alpha = float(torch.tensor(1.0 / (self.K + 1), dtype=torch.float32))  # float32(1 / (K + 1))
+        self.dinv_user, self.dinv_item = ops.lgcn_dinv(self.by_user[0]), ops.lgcn_dinv(self.by_item[0])
+        # the propagated tables scored as the Linear scorer: <Final_u, Final_i> + 0 + 0
+        self.tables, self._keep = ops.make_tables(self.user, self.item, self.user_lin, self.item_lin)
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        self.g_user, self.g_item = torch.zeros_like(self.user), torch.zeros_like(self.item)
+        self.w_user = [torch.empty_like(self.user) for _ in range(min(self.K, 2))]  # the user side ping-pongs
+        self.w_item = torch.empty_like(self.item) if self.K >= 2 else None
+        self.grad_rows = torch.empty(3 * self.cap * self.D, **f32)
+        self.grad_lin = torch.empty(3 * self.cap, **f32)
+        self.l2_rows = torch.empty(3 * self.cap * self.D, **f32) if self.l2 else None
+        self.l2_lin = torch.empty(3 * self.cap, **f32) if self.l2 else None
+        self.items2 = torch.empty(2 * self.cap, dtype=torch.int32, device=self.dev)
+        self.err = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        self.steps = 0
+        if optimizer == 'adam':
+            self.moments = [torch.zeros_like(t) for t in (self.user, self.user, self.item, self.item)]
+        if self.l2:  # the base tables as a scorer's tables: trs_stage_add_l2 reads the rows it penalises from them
+            self.base_tables, self._keep_base = ops.make_tables(self.base_user, self.base_item, self.user_lin,
+                                                                self.item_lin)
+
+    def _horner(self, e_user, e_item, out_user, out_item, scale, accumulate=False):
+        """scale * F_0 of F_K = E, F_k = E + A^ F_{k+1} for E = (e_user, e_item), written (or with accumulate: added)
+        to (out_user, out_item); K >= 1.  The user side of step j goes to a work table, the item side is formed in
+        place from the user side of the step before; only the last step writes the outputs.  out may be E."""
+        K = self.K
+        fu, fv = e_user, e_item
+        for j in range(K):
+            last = j == K - 1
+            nu = out_user if last else self.w_user[j % 2]
+            nv = out_item if last else self.w_item
+            if last and nu is e_user and fu is e_user:  # K == 1 written over E: the item launch still reads e_user
+                nu = self.w_user[0]
+            sc, acc = (scale, accumulate) if last else (1.0, False)
+            ops.lgcn_propagate(fv, self.by_user, self.dinv_user, self.dinv_item, nu, add=e_user, scale=sc,
+                               accumulate=acc, err_flag=self.err)
+            ops.lgcn_propagate(fu, self.by_item, self.dinv_item, self.dinv_user, nv, add=e_item, scale=sc,
+                               accumulate=acc, err_flag=self.err)
+            fu, fv = nu, nv
+        return fu, fv
+
+    def forward(self):
+        """The net's user / item tables = Final of the base tables."""
+        if self.K == 0:
+            self.user.copy_(self.base_user)
+            self.item.copy_(self.base_item)
+        else:
+            self._horner(self.base_user, self.base_item, self.user, self.item, self.alpha)
+
+    def lgcn_step(self, user, pos, neg, loss_slot):
+        """One step on the triples (user, pos, neg), (B,) int32 on the device.  loss_slot: 1-element fp32 view that
+        receives the SUM of the row losses (the caller divides by B).  The net's tables hold Final of the base tables
+        on entry (forward()) and again on return."""
+        B, D, K = user.shape[0], self.D, self.K
+        if B > self.cap:
+            raise ValueError(f"batch of {B} rows above the trainer's capacity {self.cap}")
+        gr = self.grad_rows[:3 * B * D].view(3, B, D)
+        gl = self.grad_lin[:3 * B].view(3, B)
+        Bt, keep = ops.make_batch(user, pos, neg, None, None, self.err)
+        ops.score_fwd_bwd('linear', self.tables, Bt, B, D, 0, self.dev, loss_slot, None, want_scores=False, grad_rows=gr,
+                          grad_lin=gl, loss=self.loss_id)
+        items = self.items2[:2 * B]
+        items[:B], items[B:] = pos, neg
+        lr, sgd = self.lr, self.optimizer == 'sgd'
+        if self.l2:  # lambda / B times the PRE-update base row of every reference, staged before any update
+            lrw = self.l2_rows[:3 * B * D].view(3, B, D)
+            llin = self.l2_lin[:3 * B].view(3, B)
+            lrw.zero_()
+            llin.zero_()
+            c = self.l2 / B
+            ops.stage_add_l2('linear', self.base_tables, user, items.view(2, B), None, (c, c, 0.0), lrw, llin, self.err)
+        if K == 0 and sgd:  # plain matrix factorisation: the row gradients go straight into the base tables
+            ops.rows_scatter_add(self.base_user, user, gr[0], -lr, ld=D)
+            ops.rows_scatter_add(self.base_item, items, gr[1:3].view(2 * B, D), -lr, ld=D)
+        else:
+            self.g_user.zero_()
+            self.g_item.zero_()
+            ops.rows_scatter_add(self.g_user, user, gr[0], 1.0, ld=D)
+            ops.rows_scatter_add(self.g_item, items, gr[1:3].view(2 * B, D), 1.0, ld=D)
+        if sgd:
+            if K:
+                self._horner(self.g_user, self.g_item, self.base_user, self.base_item, -lr * self.alpha, accumulate=True)
+            if self.l2:
+                ops.rows_scatter_add(self.base_user, user, lrw[0], -lr, ld=D)
+                ops.rows_scatter_add(self.base_item, items, lrw[1:3].view(2 * B, D), -lr, ld=D)
+        else:
+            gu, gv = (self.g_user, self.g_item) if K == 0 else \
+                self._horner(self.g_user, self.g_item, self.g_user, self.g_item, self.alpha)
+            if self.l2:
+                ops.rows_scatter_add(gu, user, lrw[0], 1.0, ld=D)
+                ops.rows_scatter_add(gv, items, lrw[1:3].view(2 * B, D), 1.0, ld=D)
+            self.steps += 1
+            b1, b2 = self.BETAS
+            ops.lgcn_adam(self.base_user, gu, self.moments[0], self.moments[1], lr, b1, b2, self.EPS, self.steps)
+            ops.lgcn_adam(self.base_item, gv, self.moments[2], self.moments[3], lr, b1, b2, self.EPS, self.steps)
+        self.forward()
+
+    def check_errors(self):
+        from .collaborative._scorer import check_err_flag
+        check_err_flag(self.err, "fit_lightgcn")

@@ -785,6 +785,148 @@ class TorchRecSys(torch.nn.Module):
         check_err_flag(err, "fit_als")
         return torch.tensor(losses, dtype=torch.float64) if return_loss else None
 
+    # ------------------------------------------------------------------------------------------------ LightGCN
+    def _check_fit_lightgcn(self, epochs, lr, batch_size, layers, optimizer, loss, l2, seed, max_tries):
+        """Argument checks of fit_lightgcn (before any device work)."""
+        what = "fit_lightgcn"
+        self._refuse_ease("fit_lightgcn()", "call fit_ease()", ValueError)
+        if self.net_type not in ('linear', 'fm'):
+            raise ValueError(f"{what} needs net_type 'linear' or 'fm': with net_type={self.net_type!r} (mlp) a score is "
+                             "not the inner product of a user row and an item row")
+        if self.use_metadata:
+            raise ValueError(f"{what} takes a model without metadata columns: the graph it propagates over has user and "
+                             "item nodes only")
+        if self.n_factors > ops._lib.RETRIEVE_DMAX:
+            raise ValueError(f"{what} takes n_factors <= {ops._lib.RETRIEVE_DMAX} (TRS_RETRIEVE_DMAX), got "
+                             f"{self.n_factors}")
+        if tdist.world_info()[1] > 1:
+            raise NotImplementedError(f"{what} runs in a single process: under torch.distributed (world > 1) every rank "
+                                      "holds a shard of the interactions, and a row's propagation needs all of its pairs")
+
+        def integer(v, name, lo, hi=None):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v > hi):
+                raise ValueError(f"{what}: {name} must be an integer in {lo}..{'' if hi is None else hi}, got {v!r}")
+
+        def number(v, name, positive):
+            ok = isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and math.isfinite(v)
+            f = float(np.float32(v)) if ok and abs(v) <= 3.4e38 else float("nan")  # the kernels take it as fp32
+            if not (f > 0 if positive else f >= 0):
+                raise ValueError(f"{what}: {name} must be a finite number {'> 0' if positive else '>= 0'}, got {v!r}")
+        integer(epochs, "epochs", 1)
+        integer(batch_size, "batch_size", 1)
+        integer(layers, "layers", 0, ops._lib.LGCN_LAYERS_MAX)
+        integer(seed, "seed", 0)
+        integer(max_tries, "max_tries", 1, 1 << 20)
+        number(lr, "lr", True)
+        number(l2, "l2", False)
+        if optimizer not in ('adam', 'sgd'):
+            raise ValueError(f"{what}: optimizer must be 'adam' or 'sgd', got {optimizer!r}")
+        if loss not in ('bpr', 'hinge'):
+            raise ValueError(f"{what}: loss must be 'bpr' or 'hinge', got {loss!r}")
+        if self.n_items < 2:
+            raise ValueError(f"{what}: sampling a negative needs n_items >= 2")
+
+    @_host_side
+    def fit_lightgcn(self, epochs: int = 10, lr: float = 1e-3, batch_size: int = 16384, layers: int = 3,
+                     optimizer: str = 'adam', loss: str = 'bpr', l2: float = 1e-4, seed: int = 0,
+                     reject_seen: bool = True, max_tries: int = 8, restart: bool = False, return_loss: bool = False):
+        """LightGCN (He et al., SIGIR 2020) on the graph of the train split's distinct (user, item) pairs.  With A^ the
+        symmetric normalised adjacency (A^[u][i] = 1 / sqrt(deg_u deg_i) on a pair) and E0 = [U0; V0] the base tables,
+            Final = 1/(layers + 1) * sum_{k = 0..layers} A^^k E0,        score(u, i) = <Final_u, Final_i>;
+        no weights beyond the two tables.  The sum is evaluated in Horner form (F_K = E0, F_k = E0 + A^ F_{k+1}), the
+        gradient is the same recurrence on dL/dFinal; every hop is one launch of trs_lgcn_propagate per side (the exact
+        rule is in include/trs.h "LightGCN").  layers = 0 is plain matrix factorisation with the pairwise loss.
+
+        Every epoch visits every train row once, in a permutation seeded by (seed, epoch); the last partial batch runs.
+        One step = one negative per row from the device sampler (uniform over the items other than the row's positive;
+        with reject_seen an item the user has a train pair with is redrawn, at most max_tries candidates), the forward,
+        the 'bpr' or 'hinge' loss on (score of the positive, score of the negative), the backward, and the update of
+        the base tables: optimizer 'sgd' is plain SGD at `lr`; 'adam' is torch.optim.Adam's rule at its default betas
+        and eps on every element of both tables (LightGCN's gradient is dense).  l2: l2 / B times the pre-update base
+        row is added to the gradient of every reference (user, positive, negative) of a batch of B rows, as fit(l2=)
+        means it.  No optimiser object, no host sync inside an epoch.
+
+        The base tables and the layer count become buffers of the net (lgcn_user_base, lgcn_item_base, lgcn_layers;
+        state_dict() carries them).  The net's user / item tables are left holding Final and its 1-wide tables are
+        zeroed, so recommend(), rank_items(), similar_items(), recommend_diverse(), evaluate_ranking(),
+        evaluate_ranks(), evaluate() and the fold-in calls answer from the LightGCN score.
+        A later call continues from the base tables when `layers` is the same, restart is false and the tables still
+        equal the forward of the buffers bit for bit (the check costs one forward; the operator is deterministic, so a
+        fit() or fit_als() in between is seen).  Otherwise the current tables become the new base.  Adam's moments do
+        NOT survive a call: every call starts them from zero.  The count of epochs done, which keys the permutations
+        and the sampler, stays with this model object: a model restored from a state_dict() continues from the
+        restored tables but draws the permutations and negatives of epochs 0, 1, ... again.
+        The buffers are a second pair of tables.  A later fit() or fit_als() leaves them in the net and in
+        state_dict() (the next fit_lightgcn() re-bases over them); to drop them set net.lgcn_user_base,
+        net.lgcn_item_base and net.lgcn_layers to None.
+
+        Memory: besides the net's tables a call holds buffers of the size of both tables together — 4 of them with
+        'sgd' (the base tables, the dense gradient, the work tables of the recurrence), 6 with 'adam' (the two moments
+        on top); it raises RuntimeError when the device has less free memory than that.
+        Returns None, or with return_loss the (epochs,) float64 mean row loss of every epoch.
+        Before any device work: ValueError for another net_type, metadata columns, n_factors > TRS_RETRIEVE_DMAX, layers
+        outside 0..8, n_items < 2 or a bad argument; NotImplementedError under torch.distributed with more than one
+        rank."""
+        what = "fit_lightgcn"
+        self._check_fit_lightgcn(epochs, lr, batch_size, layers, optimizer, loss, l2, seed, max_tries)
+        epochs, batch_size, layers, seed, max_tries = int(epochs), int(batch_size), int(layers), int(seed), int(max_tries)
+        lr, l2 = float(lr), float(l2)
+        from .engine import LightGCNTrainer
+        dev = _device()
+        net = self.net = self.net.train()
+        ps = net.table_params()
+        U, V = ps[0].data, ps[1].data
+        have = net.lgcn_user_base is not None and net.lgcn_item_base is not None and net.lgcn_layers is not None
+        pair_bytes = 4 * (self.n_users + self.n_items) * int(self.n_factors)
+        need = (LightGCNTrainer.BUFFERS[optimizer] - (1 if have else 0)) * pair_bytes
+        free = torch.cuda.mem_get_info(dev)[0]
+        if free < need:
+            raise RuntimeError(f"{what}: optimizer={optimizer!r} needs {LightGCNTrainer.BUFFERS[optimizer]} buffers of "
+                               f"the size of both tables ({pair_bytes} bytes each); the device has {free} bytes free")
+        graph = self._als_csrs()
+        st = self._device_stream('train')
+        n = int(st['user'].numel())
+        with torch.no_grad():
+            ps[2].data.zero_()
+            ps[3].data.zero_()
+            resume = have and not restart and int(net.lgcn_layers.item()) == layers
+            if not have:
+                net.lgcn_user_base, net.lgcn_item_base = U.clone(), V.clone()
+                net.lgcn_layers = torch.tensor([layers], dtype=torch.int64, device=dev)
+            trainer = LightGCNTrainer(net, (net.lgcn_user_base, net.lgcn_item_base), graph, layers,
+                                      max(min(batch_size, n), 1), lr, ops._lib.LOSS_ID[loss], optimizer, l2)
+            if resume:  # do the tables still hold the forward of the buffers?
+                keep_u, keep_v = U.clone(), V.clone()
+                trainer.forward()
+                resume = torch.equal(U, keep_u) and torch.equal(V, keep_v)
+                if not resume:
+                    U.copy_(keep_u)
+                    V.copy_(keep_v)
+                del keep_u, keep_v
+            if not resume:  # the current tables are the new base
+                net.lgcn_user_base.copy_(U)
+                net.lgcn_item_base.copy_(V)
+                net.lgcn_layers.fill_(layers)
+                trainer.forward()
+                self._lgcn_epochs_done = 0
+            loss_sums = torch.zeros(epochs, dtype=torch.float32, device=dev)
+            if n:
+                B = min(batch_size, n)
+                sampler = ops.Sampler(seen=self._seen_csr() if reject_seen else None, max_tries=max_tries)
+                done = getattr(self, "_lgcn_epochs_done", 0)
+                for ep in range(epochs):
+                    shuffle_key = _mix64(seed, done + ep)
+                    sample_seed = _mix64(seed ^ 0x16C7, done + ep)
+                    for s in range(0, n, B):
+                        ids = ops.batch_prepare(st['user'], st['pos'], None, shuffle_key, s, min(B, n - s), self.n_items,
+                                                sample_seed, s, sampler=sampler)
+                        trainer.lgcn_step(ids['user'], ids['pos'], ids['neg'], loss_sums[ep:ep + 1])
+                    avg = float(loss_sums[ep].item()) / n  # the epoch's one read
+                    print(f'|--- Epoch {ep+1}/{epochs} --- Training Loss: {avg:.4f}')
+                self._lgcn_epochs_done = done + epochs
+            trainer.check_errors()
+        return (loss_sums.cpu().to(torch.float64) / max(n, 1)) if return_loss else None
+
     # ------------------------------------------------------------------------------------------------ EASE
     @_host_side
     def fit_ease(self, regularization: float = 0.5):

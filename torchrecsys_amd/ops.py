@@ -932,6 +932,53 @@ def als_solve(other, G, nbr, regularization, alpha, cg_steps, rows_inout, err_fl
     return rows_inout
 
 
+def lgcn_dinv(off):
+    """float32(1 / sqrt(float64(degree))) of every row of a CSR, 0 where the list is empty (include/trs.h "LightGCN")."""
+    deg = (off[1:] - off[:-1]).to(torch.float64)
+    return torch.where(deg > 0, 1.0 / deg.clamp(min=1).sqrt(), torch.zeros_like(deg)).to(torch.float32).contiguous()
+
+
+def lgcn_propagate(in_rows, nbr, dinv_out, dinv_in, out, add=None, scale=1.0, accumulate=False, err_flag=None):
+    """One launch of the LightGCN operator (trs_lgcn_propagate; the rule is in include/trs.h "LightGCN"):
+        out[r] = [out[r] +] scale * ([add[r] +] dinv_out[r] * sum_{c in nbr[r]} dinv_in[c] * in_rows[c]).
+    in_rows (n_in, D), out and add (n_out, D) fp32 GPU matrices; nbr = (offsets int64 (n_out + 1,), ids int32) GPU CSR of
+    rows of in_rows; out may be add, never in_rows.  err_flag: optional int32 GPU tensor whose bit 0 is set by an id
+    outside [0, n_in).  Returns out."""
+    off, items = nbr
+    _dev(in_rows, "input rows", torch.float32)
+    _dev(out, "output rows", torch.float32)
+    _dev(add, "rows to add", torch.float32)
+    _dev(dinv_out, "dinv_out", torch.float32)
+    _dev(dinv_in, "dinv_in", torch.float32)
+    if in_rows.dim() != 2 or out.dim() != 2 or in_rows.shape[1] != out.shape[1]:
+        raise ValueError("the input and the output rows must be (n, D) with the same D")
+    n_out, D = out.shape
+    if add is not None and tuple(add.shape) != (n_out, D):
+        raise ValueError(f"add must be ({n_out}, {D}), got {tuple(add.shape)}")
+    if off.numel() != n_out + 1 or dinv_out.numel() != n_out or dinv_in.numel() != in_rows.shape[0]:
+        raise ValueError("the CSR and dinv_out must have one entry per output row, dinv_in one per input row")
+    if items.numel() == 0:  # every list empty: the kernel reads no id, but the CSR may not carry a NULL array
+        items = torch.zeros(1, dtype=torch.int32, device=out.device)
+    cs = csr(off, items)
+    check(_lib.load().trs_lgcn_propagate(ptr(in_rows), in_rows.shape[0], D, C.byref(cs), ptr(dinv_out), ptr(dinv_in),
+                                         ptr(add), float(scale), ptr(out), n_out, int(bool(accumulate)),
+                                         ptr(_dev(err_flag, "err_flag", torch.int32)), _stream()),
+          "trs_lgcn_propagate")
+    return out
+
+
+def lgcn_adam(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step_count):
+    """torch.optim.Adam's rule on every element of the dense fp32 GPU table `param`, in place (trs_lgcn_adam, one
+    launch); exp_avg / exp_avg_sq are the moments, step_count the 1-based step."""
+    for t, name in ((param, "param"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        _dev(t, name, torch.float32)
+        if t.shape != param.shape:
+            raise ValueError(f"{name} must have the parameter's shape {tuple(param.shape)}, got {tuple(t.shape)}")
+    check(_lib.load().trs_lgcn_adam(ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), float(lr),
+                                    float(beta1), float(beta2), float(eps), int(step_count), _stream()),
+          "trs_lgcn_adam")
+
+
 def ease_padded(n):
     """Row count and row stride of the fp64 matrices of the EASE solver: n rounded up to a multiple of TRS_EASE_NB."""
     return -(-int(n) // _lib.EASE_NB) * _lib.EASE_NB
