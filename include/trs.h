@@ -103,7 +103,7 @@ const char* trs_last_error(void);
  *      trs_fold_in_users, trs_item_ranks, trs_item_ranks_workspace_bytes, trs_mmr_rerank, trs_list_ild,
  *      trs_fold_in_items, trs_als_gram, trs_als_gram_workspace_bytes, trs_als_solve, trs_ease_gram, trs_ease_invert,
  *      trs_ease_invert_workspace_bytes, trs_ease_weights, trs_ease_scores, trs_seq_fwd_bwd, trs_seq_user_rows,
- *      trs_lgcn_propagate, trs_lgcn_adam.) */
+ *      trs_lgcn_propagate, trs_lgcn_adam, trs_knn_build, trs_knn_build_workspace_bytes, trs_knn_scores.) */
 #define TRS_ABI_VERSION 6
 #define TRS_SYNC_WORDS 288
 #define TRS_SYNC_REBASE 0x40000000u /* arrivals after which trs_train_steps_sgd zeroes sync_dev and its host count */
@@ -960,6 +960,59 @@ int trs_ease_invert(double* A_inout_dev, int64_t n, void* workspace_dev, int64_t
 int trs_ease_weights(const double* P_dev, int64_t n, float* B_out_dev, void* stream);
 int trs_ease_scores(const float* B_dev, int64_t n, const trs_csr* hist, const int64_t* rows_dev, int64_t n_rows,
                     float* out_dev, int32_t* err_flag_dev, void* stream);
+
+/* ------------------------------------------------------------------- item kNN (fit_itemknn) */
+/* Sparse item-item neighbourhood model: co-occurrence similarities, K neighbours kept per item.  Nothing of size n^2 is
+ * allocated, so it takes catalogues EASE cannot.  Added without touching an existing signature or struct.
+ *
+ *   X        the binary n_users x n matrix of the DISTINCT (user, item) pairs, as for EASE
+ *   U_i      the users of item i, n_i = |U_i|
+ *   c(i, j)  = |U_i and U_j|, an exact integer
+ *   sim(i, j) from the integers (c, n_i, n_j) and the shrinkage h >= 0, in fp64 with every operation rounded once
+ *            (IEEE division and square root, no fast-math intrinsic, no fused multiply-add), then rounded to fp32 once;
+ *            a float64 numpy expression reproduces it bit for bit:
+ *     TRS_KNN_COSINE       c / (sqrt((double)n_i * (double)n_j) + h)       (the product is exact below 2^53)
+ *     TRS_KNN_JACCARD      c / ((double)(n_i + n_j - c) + h)
+ *     TRS_KNN_CONDITIONAL  c / ((double)n_i + h)                           (P(j | i): not symmetric)
+ *     TRS_KNN_COUNT        c                                               (h is ignored)
+ *   neighbours of i: the candidates are the j != i with c(i, j) > 0; row i keeps the K candidates with the largest key,
+ *            key = (fp32 similarity descending, j ascending): the key of trs_topk.
+ *   THIS PROJECT PRUNES PER ROW: row i votes for its own K nearest items.  (Some libraries keep, per column j, the K
+ *   rows with the largest sim(i, j) instead; with a symmetric similarity that is the transposed lists, and the scores
+ *   differ.)
+ *   score(u, j) = sum of W[i][j] over the items i of hist(u) whose list holds j, accumulated in fp32 from 0, in
+ *            ascending CSR position of i, one add per term (no float atomics): a sequential float32 loop reproduces it
+ *            bit for bit.  An empty history gives zeros.
+ *
+ * trs_knn_build: hist = user -> sorted distinct items (n_users rows), inv = item -> sorted distinct users (n rows), the
+ *   two CSRs of the same pairs.  Outputs in ELL form, in key order: nbr_ids_out (n, K) int32 with -1 beyond the row's
+ *   candidates, nbr_w_out (n, K) fp32 with 0 there.  One launch on `stream` behind a memset of the workspace
+ *   (trs_knn_build_workspace_bytes(n, K) bytes: a counter that hands out the items).  The columns are processed in
+ *   tiles of TRS_KNN_TILE ids whose 32-bit counters live in LDS; the columns a tile sees are remembered in a list of
+ *   TRS_KNN_TOUCHED entries, beyond which the tile is swept.  The counts are integer adds and the selection is by a
+ *   total order: the same input gives the same bits, call after call.  An item id outside [0, n) or a user id outside
+ *   [0, n_users) is never used as an address: it is skipped and bit 0 of *err_flag_dev (may be NULL) is set.
+ * trs_knn_scores: out (n_rows, n) fp32 dense score rows of the rows rows[r] of hist, by the rule above; rows may
+ *   repeat.  A row of nbr_ids must list a column at most once (trs_knn_build's output does).  A row index outside the
+ *   CSR counts as an empty history; an item id outside [0, n) and a neighbour id other than -1 outside [0, n) are
+ *   skipped; all three set bit 0 of *err_flag_dev (may be NULL).
+ * TRS_E_ARG, nothing launched: n outside 1..2^31-1 (trs_knn_scores: more than 65 535 column tiles of 8 192); K outside
+ *   1..TRS_KNN_KMAX; an unknown kind; a shrinkage that is not finite or < 0; a NULL array, CSR or CSR array;
+ *   hist->n_rows != n_users or inv->n_rows != n (trs_knn_build); a NULL or too small workspace.  trs_knn_scores with
+ *   n_rows == 0: TRS_OK, nothing launched. */
+#define TRS_KNN_COSINE 0
+#define TRS_KNN_JACCARD 1
+#define TRS_KNN_CONDITIONAL 2
+#define TRS_KNN_COUNT 3
+#define TRS_KNN_KMAX 128      /* largest K: the bound of trs_topk's kin, the retrieval kernels */
+#define TRS_KNN_TILE 16384    /* column ids per tile of trs_knn_build: 64 KiB of 32-bit counters in LDS */
+#define TRS_KNN_TOUCHED 512   /* entries of the touched list of a tile; a tile that sees more columns is swept */
+int64_t trs_knn_build_workspace_bytes(int64_t n, int32_t K);
+int trs_knn_build(const trs_csr* hist, const trs_csr* inv, int64_t n_users, int64_t n, int32_t kind, double shrinkage,
+                  int32_t K, int32_t* nbr_ids_out_dev, float* nbr_w_out_dev, void* workspace_dev,
+                  int64_t workspace_bytes, int32_t* err_flag_dev, void* stream);
+int trs_knn_scores(const int32_t* nbr_ids_dev, const float* nbr_w_dev, int64_t n, int32_t K, const trs_csr* hist,
+                   const int64_t* rows_dev, int64_t n_rows, float* out_dev, int32_t* err_flag_dev, void* stream);
 
 /* ------------------------------------------------- exact ranks (rank_items / evaluate_ranks) */
 /* Where given items land in a user's full ranking.  Added without touching an existing signature or struct.

@@ -20,6 +20,10 @@ EASE_NMAX = 32768  # TRS_EASE_NMAX: largest catalogue of fit_ease
 SEQ_LMAX = 16  # TRS_SEQ_LMAX: largest context length of the sequence model
 LGCN_SEG = 512  # TRS_LGCN_SEG: neighbours per segment of trs_lgcn_propagate
 LGCN_LAYERS_MAX = 8  # most propagation layers fit_lightgcn takes
+KNN_KIND = {"cosine": 0, "jaccard": 1, "conditional": 2, "count": 3}  # TRS_KNN_COSINE .. TRS_KNN_COUNT
+KNN_KMAX = 128  # TRS_KNN_KMAX: most neighbours per item of fit_itemknn
+KNN_TILE = 16384  # TRS_KNN_TILE: column ids per LDS tile of trs_knn_build
+KNN_TOUCHED = 512  # TRS_KNN_TOUCHED: entries of a tile's touched list, beyond which the tile is swept
 ABI_VERSION = 6  # == TRS_ABI_VERSION of include/trs.h (tests/test_abi.py)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -195,6 +199,10 @@ PROTOTYPES = {
     "trs_ease_invert": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
     "trs_ease_weights": (C.c_int, [_vp, _i64, _vp, _vp]),
     "trs_ease_scores": (C.c_int, [_vp, _i64, C.POINTER(TrsCsr), _vp, _i64, _vp, _vp, _vp]),
+    "trs_knn_build_workspace_bytes": (C.c_int64, [_i64, _i32]),
+    "trs_knn_build": (C.c_int, [C.POINTER(TrsCsr), C.POINTER(TrsCsr), _i64, _i64, _i32, C.c_double, _i32, _vp, _vp, _vp,
+                                _i64, _vp, _vp]),
+    "trs_knn_scores": (C.c_int, [_vp, _vp, _i64, _i32, C.POINTER(TrsCsr), _vp, _i64, _vp, _vp, _vp]),
     "trs_seq_fwd_bwd": (C.c_int, [_T, _vp, C.POINTER(TrsCsr), _vp, _vp, _vp, _i64, _i32, _vp, _i32, _f, _vp, _vp, _vp,
                                   _vp, _vp, _vp, _vp]),
     "trs_seq_user_rows": (C.c_int, [_T, _vp, C.POINTER(TrsCsr), _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp]),

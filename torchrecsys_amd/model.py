@@ -253,8 +253,8 @@ class TorchRecSys(torch.nn.Module):
 
     # ------------------------------------------------------------------------------------------------ net
     def _init_net(self, net_type='linear'):
-        assert net_type in ('linear', 'mlp', 'neucf', 'fm', 'lstm', 'ease'), \
-            'Net type must be one of "linear", "mlp", "neu", "ease" or "lstm"'
+        assert net_type in ('linear', 'mlp', 'neucf', 'fm', 'lstm', 'ease', 'itemknn'), \
+            'Net type must be one of "linear", "mlp", "neu", "ease", "itemknn" or "lstm"'
         kw = dict(n_users=self.n_users, n_items=self.n_items, n_metadata=self.metadata_size,
                   n_factors=self.n_factors, use_metadata=self.use_metadata, use_cuda=self.use_cuda)
         if net_type == 'linear':
@@ -275,6 +275,14 @@ class TorchRecSys(torch.nn.Module):
                                  "over the interactions alone")
             from .collaborative.ease import EASE
             self.net = EASE(n_users=self.n_users, n_items=self.n_items)  # n_factors is ignored
+            self.net.bind_history(self._seen_csr)
+        elif net_type == 'itemknn':
+            print('Item k-Nearest Neighbours')
+            if self.use_metadata:
+                raise ValueError("net_type='itemknn' takes no metadata columns: the model is item-item neighbour lists "
+                                 "over the interactions alone")
+            from .collaborative.itemknn import ItemKNN
+            self.net = ItemKNN(n_users=self.n_users, n_items=self.n_items)  # n_factors is ignored
             self.net.bind_history(self._seen_csr)
         else:  # the reference silently leaves self.net undefined here (model.py:162-166)
             raise NotImplementedError(f'{net_type} is not implemented (nor is it in the reference)')
@@ -427,10 +435,17 @@ class TorchRecSys(torch.nn.Module):
             self._dev_cache['item_meta'] = torch.from_numpy(tab).to(torch.int32).to(_device())
         return self._dev_cache['item_meta']
 
+    _ITEM_ITEM = {'ease': ("a closed-form item-item model", "fit_ease", "EASE"),
+                  'itemknn': ("an item-item neighbourhood model", "fit_itemknn", "item kNN")}
+
     def _refuse_ease(self, what, instead, exc=NotImplementedError):
-        """net_type='ease' has no embedding rows, no gradient steps and no pairwise loss: say what to call instead."""
-        if self.net_type == 'ease':
-            raise exc(f"{what} does not apply to net_type='ease' (a closed-form item-item model without embedding "
+        """net_type 'ease' / 'itemknn' have no embedding rows, no gradient steps and no pairwise loss: say what to call
+        instead.  `instead` is worded for 'ease'; for 'itemknn' its fit_ease / EASE become fit_itemknn / item kNN."""
+        if self.net_type in self._ITEM_ITEM:
+            kind, fit, name = self._ITEM_ITEM[self.net_type]
+            if self.net_type != 'ease':
+                instead = instead.replace("fit_ease", fit).replace("EASE", name)
+            raise exc(f"{what} does not apply to net_type={self.net_type!r} ({kind} without embedding "
                       f"rows): {instead}")
 
     def _make_trainer(self, optimizer, batch_size):
@@ -980,22 +995,64 @@ class TorchRecSys(torch.nn.Module):
                                "Cholesky factorisation was not positive and finite); raise regularization")
         self.net.set_weights(B, seen)
 
-    def _ease_recommend_for_histories(self, histories, top_k, exclude_seen, return_scores):
-        """recommend_for_histories on an EASE model: score rows of the histories' own CSR, mask, top-k, ids back."""
+    # ------------------------------------------------------------------------------------------------ item kNN
+    @_host_side
+    def fit_itemknn(self, neighbours: int = 100, similarity: str = 'cosine', shrinkage: float = 0.0):
+        """Sparse item-kNN on the train split's distinct (user, item) pairs: c(i, j) = the users who hold both items,
+        similarity 'cosine' c / (sqrt(n_i n_j) + h), 'jaccard' c / (n_i + n_j - c + h), 'conditional' c / (n_i + h) or
+        'count' c, with h = shrinkage; every item keeps its `neighbours` most similar items (ties by ascending item
+        row), and a user's scores are the sums over the neighbour lists of the user's train items.  The lists are pruned
+        per row: item i votes for its own nearest items.  No learning rate, no sampler; the counts are integers and the
+        similarity is formed in fp64 and rounded to fp32 once, so two calls give the same lists bit for bit (the rule is
+        in include/trs.h "item kNN").
+        Device work: one launch of trs_knn_build over the two CSRs of the train pairs; nothing of size n_items^2 is
+        allocated, the model is 8 * n_items * neighbours bytes (buffers of the net, in state_dict()).
+        Afterwards predict(), predict_many(), recommend(), rank_items(), evaluate_ranking(), evaluate_ranks(),
+        recommend_for_histories() and item_weights() answer from the lists.
+        Before any device work: ValueError for another net_type, an unknown similarity, neighbours outside
+        1..TRS_KNN_KMAX or a shrinkage that is not a finite number >= 0; NotImplementedError under torch.distributed
+        with more than one rank (the CSRs are this rank's shard)."""
+        if self.net_type != 'itemknn':
+            raise ValueError(f"fit_itemknn needs net_type='itemknn', not {self.net_type!r}: call fit(), fit_als() or "
+                             f"fit_ease()")
+        kinds = ops._lib.KNN_KIND
+        if not isinstance(similarity, str) or similarity not in kinds:
+            raise ValueError(f"similarity must be one of {sorted(kinds)}, got {similarity!r}")
+        kmax = ops._lib.KNN_KMAX
+        if isinstance(neighbours, bool) or not isinstance(neighbours, (int, np.integer)) or \
+                not 1 <= int(neighbours) <= kmax:
+            raise ValueError(f"neighbours must be an integer in 1..{kmax} (TRS_KNN_KMAX), got {neighbours!r}")
+        h = shrinkage
+        ok = isinstance(h, (int, float, np.integer, np.floating)) and not isinstance(h, bool) and math.isfinite(h)
+        if not ok or not h >= 0:
+            raise ValueError(f"shrinkage must be a finite number >= 0, got {shrinkage!r}")
+        if tdist.world_info()[1] > 1:
+            raise NotImplementedError("fit_itemknn runs in a single process: under torch.distributed (world > 1) the "
+                                      "CSRs are this rank's shard of the interactions, and a co-occurrence count needs "
+                                      "all of them")
+        _device()
+        by_user, by_item = self._als_csrs()
+        err = torch.zeros(1, dtype=torch.int32, device=by_user[0].device)
+        ids, w = ops.knn_build(by_user, by_item, self.n_items, similarity, float(h), int(neighbours), err)
+        check_err_flag(err, "fit_itemknn")
+        self.net.set_neighbours(ids, w, by_user, kinds[similarity], float(h))
+
+    def _item_item_recommend_for_histories(self, score_csr_rows, dev, histories, top_k, exclude_seen, return_scores):
+        """recommend_for_histories on an item-item model (EASE, item kNN): score rows of the histories' own CSR
+        (score_csr_rows(hist, rows) -> (len(rows), n_items) fp32 on `dev`), mask, top-k, ids back."""
         off, items, rank = self._history_csr(histories)
         n = rank.size
         k = min(int(top_k), self.n_items)
         if k <= 0 or n == 0:
             return self._empty_topk(n, k, return_scores)
-        B = self.net.weights()
-        dev = B.device
+        dev = dev()
         hist = (torch.from_numpy(off).to(dev), torch.from_numpy(items).to(dev))
         mask = bool(exclude_seen) and items.size > 0  # every history empty: nothing to exclude
         ids = torch.empty((n, k), dtype=torch.int64, device=dev)
         scores = torch.empty((n, k), dtype=torch.float32, device=dev)
         for s in range(0, n, self.GENERIC_CHUNK):
             us = torch.arange(s, min(s + self.GENERIC_CHUNK, n), dtype=torch.int64, device=dev)
-            rows = ops.ease_scores(B, hist, us)
+            rows = score_csr_rows(hist, us)
             if mask:
                 ops.mask_seen(rows, us, hist)
                 n_seen = hist[0][us + 1] - hist[0][us]
@@ -1012,14 +1069,28 @@ class TorchRecSys(torch.nn.Module):
         (n, k) int64 CPU tensor of original item ids, k = min(top_k, n_items); with return_scores also the (n, k) fp32
         weights.  Order: weight descending, ties by ascending item row; the item itself is never returned, so the
         positions beyond the n_items - 1 other items hold id -1 and weight -inf.  B[i, j] is what having item i adds to
-        the score of item j.  An unknown id raises IndexError; another net_type ValueError."""
-        if self.net_type != 'ease':
-            raise ValueError(f"item_weights needs net_type='ease', not {self.net_type!r}: call similar_items()")
+        the score of item j.  On an itemknn model the rows are the stored neighbour lists (already in that order): k
+        beyond the model's K gives id -1 / weight -inf.  An unknown id raises IndexError; another net_type ValueError."""
+        if self.net_type not in ('ease', 'itemknn'):
+            raise ValueError(f"item_weights needs net_type='ease' or 'itemknn', not {self.net_type!r}: call "
+                             f"similar_items()")
         index = getattr(self.data_processor, "item_index", None)
         qlist = item_ids.tolist() if hasattr(item_ids, "tolist") else list(item_ids)
         k = min(int(top_k), self.n_items)
         if k <= 0 or not qlist:
             return self._empty_topk(len(qlist), k, return_scores)
+        if self.net_type == 'itemknn':  # the stored lists are already in key order, without the item itself
+            nbr_ids, nbr_w = self.net.neighbours()
+            queries = self._dense_rows(qlist, index, self.n_items, 'item').to(nbr_ids.device)
+            K = nbr_ids.shape[1]
+            ids = torch.full((queries.numel(), k), -1, dtype=torch.int64)
+            scores = torch.full((queries.numel(), k), float('-inf'), dtype=torch.float32)
+            got = nbr_ids[queries, :min(k, K)].cpu().to(torch.int64)
+            ids[:, :got.shape[1]] = got
+            scores[:, :got.shape[1]] = torch.where(got >= 0, nbr_w[queries, :min(k, K)].cpu(),
+                                                   torch.full((), float('-inf')))
+            ids = self._original_ids(ids, index)
+            return (ids, scores) if return_scores else ids
         B = self.net.weights()
         dev = B.device
         queries = self._dense_rows(qlist, index, self.n_items, 'item').to(dev)
@@ -1569,7 +1640,17 @@ class TorchRecSys(torch.nn.Module):
                 raise ValueError(f"recommend_for_histories with net_type='ease' takes no fold-in options (nothing is "
                                  f"fitted: a history's scores are the sum of its items' rows of B), got "
                                  f"{sorted(fold_in_options)}")
-            return self._ease_recommend_for_histories(histories, top_k, exclude_seen, return_scores)
+            return self._item_item_recommend_for_histories(
+                lambda hist, us: ops.ease_scores(self.net.weights(), hist, us), lambda: self.net.weights().device,
+                histories, top_k, exclude_seen, return_scores)
+        if self.net_type == 'itemknn':
+            if fold_in_options:
+                raise ValueError(f"recommend_for_histories with net_type='itemknn' takes no fold-in options (nothing is "
+                                 f"fitted: a history's scores are the sums over its items' neighbour lists), got "
+                                 f"{sorted(fold_in_options)}")
+            return self._item_item_recommend_for_histories(
+                self.net.score_csr_rows, lambda: self.net.neighbours()[0].device, histories, top_k, exclude_seen,
+                return_scores)
         unknown = set(fold_in_options) - {'epochs', 'lr', 'loss', 'l2', 'seed', 'shuffle', 'reject_seen', 'max_tries'}
         if unknown:
             raise ValueError(f"unknown fold-in options {sorted(unknown)}")

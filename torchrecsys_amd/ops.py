@@ -1059,6 +1059,71 @@ def ease_scores(B, hist_csr, rows, err_flag=None):
     return out
 
 
+def _knn_kind(kind):
+    if isinstance(kind, str):
+        if kind not in _lib.KNN_KIND:
+            raise ValueError(f"similarity must be one of {sorted(_lib.KNN_KIND)}, got {kind!r}")
+        return _lib.KNN_KIND[kind]
+    if isinstance(kind, bool) or not isinstance(kind, int) or kind not in _lib.KNN_KIND.values():
+        raise ValueError(f"similarity must be one of {sorted(_lib.KNN_KIND)} (or its TRS_KNN_* id), got {kind!r}")
+    return kind
+
+
+def knn_build(seen_csr, inv_csr, n_items, kind, shrinkage, K, err_flag=None):
+    """The K nearest items of every item (trs_knn_build; include/trs.h "item kNN"): (ids (n_items, K) int32 with -1
+    beyond a row's candidates, w (n_items, K) fp32 with 0 there), rows in key order.  seen_csr: user -> sorted distinct
+    items, inv_csr: item -> sorted distinct users, both (offsets int64, ids int32) GPU CSRs of the same pairs.  kind:
+    'cosine' | 'jaccard' | 'conditional' | 'count'.  Exact and deterministic: the counts are integers, the similarity
+    is formed in fp64 and rounded to fp32 once."""
+    off, items = seen_csr
+    ioff, iusers = inv_csr
+    for t, name in ((off, "CSR offsets"), (ioff, "inverse CSR offsets")):
+        _dev(t, name, torch.int64)
+    for t, name in ((items, "CSR items"), (iusers, "inverse CSR users")):
+        _dev(t, name, torch.int32)
+    n, K = int(n_items), int(K)
+    if n < 1 or ioff.numel() != n + 1:
+        raise ValueError(f"the inverse CSR must have n_items={n} >= 1 rows, got {ioff.numel() - 1}")
+    if not 1 <= K <= _lib.KNN_KMAX:
+        raise ValueError(f"K={K} outside 1..{_lib.KNN_KMAX} (TRS_KNN_KMAX)")
+    h = float(shrinkage)
+    if not (h >= 0.0 and h != float("inf")):
+        raise ValueError(f"shrinkage must be a finite number >= 0, got {shrinkage!r}")
+    kind = _knn_kind(kind)
+    lib = _lib.load()
+    ids = torch.empty((n, K), dtype=torch.int32, device=off.device)
+    w = torch.empty((n, K), dtype=torch.float32, device=off.device)
+    ws = torch.empty(lib.trs_knn_build_workspace_bytes(n, K), dtype=torch.uint8, device=off.device)
+    cs, keep = _csr_nonnull(off, items)
+    ci, keep_i = _csr_nonnull(ioff, iusers)
+    check(lib.trs_knn_build(C.byref(cs), C.byref(ci), off.numel() - 1, n, kind, h, K, ptr(ids), ptr(w), ptr(ws),
+                            ws.numel(), ptr(_dev(err_flag, "err_flag", torch.int32)), _stream()), "trs_knn_build")
+    return ids, w
+
+
+def knn_scores(ids, w, hist_csr, rows, err_flag=None):
+    """Score rows (len(rows), n) fp32 of the rows `rows` of hist_csr under the neighbour lists ids / w (n, K): entry j =
+    the sum of w[i][s] over the history's items i, in CSR order, whose list holds j at slot s (trs_knn_scores).
+    hist_csr (offsets int64, items int32) GPU CSR; rows int64 GPU tensor."""
+    _dev(ids, "nbr_ids", torch.int32)
+    _dev(w, "nbr_w", torch.float32)
+    _dev(rows, "rows", torch.int64)
+    off, items = hist_csr
+    _dev(off, "CSR offsets", torch.int64)
+    _dev(items, "CSR items", torch.int32)
+    if ids.dim() != 2 or ids.shape != w.shape or not 1 <= ids.shape[1] <= _lib.KNN_KMAX or ids.shape[0] < 1:
+        raise ValueError(f"nbr_ids / nbr_w must both be (n, K) with n >= 1 and K in 1..{_lib.KNN_KMAX}, got "
+                         f"{tuple(ids.shape)} / {tuple(w.shape)}")
+    n, K = ids.shape
+    out = torch.empty((rows.numel(), n), dtype=torch.float32, device=ids.device)
+    if rows.numel() == 0:
+        return out
+    cs, keep = _csr_nonnull(off, items)
+    check(_lib.load().trs_knn_scores(ptr(ids), ptr(w), n, K, C.byref(cs), ptr(rows), rows.numel(), ptr(out),
+                                     ptr(_dev(err_flag, "err_flag", torch.int32)), _stream()), "trs_knn_scores")
+    return out
+
+
 def seq_weights(context, decay, device=None):
     """The fixed slot weights of the sequence model, w_l = decay^l / sum_{j < L} decay^j (float64 arithmetic, rounded to
     fp32 once): an (L,) fp32 tensor, slot 0 the most recent item."""
